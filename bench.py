@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- measures BASELINE.json's metric ("culled objects/s + shaded Mpixels/s @4K, Bistro scene") on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   (N > 1: launched as python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...)
 
 A "step" is one whole frame of the hot path over the synthetic Bistro-like scene of BASELINE.json configs[2]
@@ -12,10 +12,13 @@ so the residual pass has real work; --instanced is the round-1 variant whose 11 
   viewport: bake -> raster predicted -> Hi-Z -> cull -> raster residual -> PBR resolve -> tonemap.
 All inputs are resident in HBM before the timed region; per-frame camera blocks (a few KB) are precomputed on the
 host and uploaded through the C ABI exactly as the Rust side would.  value = W*H*K / time (whole job, all ranks).
-At N=1 the first two frames (camera steps 0 and 1) are rendered with a read-back of step 1, and the CPU oracle -- which
-renders the same steps for the `cpu_baseline` figure anyway -- checks that frame: visible-object sets, per-triangle
-pass / residual sets, visibility keys, shadow atlas and the Rgba16Float target bit for bit, the tonemapped framebuffer
-within 1e-3 (`"parity"` in the JSON line).  Prints ONE JSON line on rank 0.
+A plain run sets up, warms up, times the K steps and prints the line; --dump-outputs DIR also writes what the last timed
+frame computed (dump_outputs).  Everything else is --full: at N=1 the first two frames (camera steps 0 and 1) are
+rendered with a read-back of step 1, and the CPU oracle -- which renders the same steps for the `cpu_baseline` figure
+anyway -- checks that frame: visible-object sets, per-triangle pass / residual sets, visibility keys, shadow atlas and
+the Rgba16Float target bit for bit, the tonemapped framebuffer within 1e-3 (`"parity"` in the JSON line); then the
+host cost per frame, the instrumented pass (stage table, rooflines) and the oracle's op tally.  Prints ONE JSON line
+on rank 0.
 """
 import hashlib
 import argparse
@@ -74,6 +77,57 @@ def compare_frames(fo, fp, fast=False):
     if fast:
         out["note"] = "shade_mode fast: sets, keys and atlas bit-exact; the HDR target differs by rounding, the framebuffer is held to 1e-3"
     return out
+
+
+DUMP_SAMPLE = 1 << 18  # entries kept of every per-pixel / per-triangle / per-texel array: under 64 MB in all, MSAA x4 at 4K included
+DUMP_SEED = 0xB157
+
+
+def dump_outputs(r, out_dir, samples):
+    """--dump-outputs: the last timed frame as render(readback=True) hands it to a caller -- the tonemapped framebuffer, the
+    Rgba16Float target, the visibility keys, the viewport's visible-object and per-triangle sets, the shadow atlas -- read back after
+    the timed region and written as out_dir/<name>.npy in float32 / float64 (a 64-bit key as its two 32-bit halves in float64).  The
+    full arrays are ~0.5 GB at 4K, so every array longer than DUMP_SAMPLE keeps a fixed sample of its entries (DUMP_SEED, the same
+    positions in every run of the same arguments); <name>_index.npy holds the flat indices sampled."""
+    import numpy as np
+    import rend3_amd as r3
+    from rend3_amd.renderer import EvalOutput
+    r.sync()
+    if r._fc is not None:  # the one-call frame path: the layout r3n_host_evaluate_frame gave the last frame
+        hf = r._fc["frame"]
+        size, shadows = (hf.shadow_atlas_width, hf.shadow_atlas_height), [None] * hf.n_shadow_views
+    else:  # the node-by-node path (R3N_FRAME_NODES=1) evaluates the lights on the host, as here
+        size, shadows, _ = r3.host.evaluate_directional_lights(r.dir_lights, r.camera)
+    w, h = r.current_resolution()
+    fr = r.readback_frame(EvalOutput(shadows, size), w, h, samples, owned_views=set())  # viewport sets only
+    rng = np.random.default_rng(DUMP_SEED)
+
+    def pick(n):
+        return np.arange(n) if n <= DUMP_SAMPLE else np.sort(rng.choice(n, DUMP_SAMPLE, replace=False))
+
+    px = pick(w * h)
+    keys = fr["vis"].reshape(w * h, -1)[px]
+    tri = pick(len(fr["pass"]))
+    atlas = fr["atlas"].reshape(-1)
+    tex = pick(len(atlas))
+    arrays = {
+        "framebuffer_rgba": fr["rgba_f32"].reshape(-1, 4)[px],
+        "hdr_rgba": fr["hdr16"].reshape(-1, 4)[px].view(np.float16).astype(np.float32),
+        "visibility_key_hi": (keys >> np.uint64(32)).astype(np.float64),
+        "visibility_key_lo": (keys & np.uint64(0xFFFFFFFF)).astype(np.float64),
+        "pixel_index": px.astype(np.float64),
+        "visible_objects": fr["visible"].astype(np.float32),
+        "pass_triangles": fr["pass"][tri].astype(np.float32),
+        "residual_triangles": fr["residual"][tri].astype(np.float32),
+        "triangle_index": tri.astype(np.float64),
+        "shadow_atlas": atlas[tex].astype(np.float32),
+        "shadow_atlas_index": tex.astype(np.float64),
+    }
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= 64_000_000, f"--dump-outputs: {total} bytes"
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
 
 
 def camera_path(hm, view0, step):
@@ -210,6 +264,13 @@ def main():
                          "below; `data` becomes \"asset\"): hand it Bistro.glb with tools/scene_viewer.py's --bistro flags and the line is "
                          "the reference's own configs[2]")
     ap.add_argument("--resolution", default=None, help="WxH of the target (default 3840x2160, the metric's)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: the parity frames and the CPU oracle's baseline (`parity`, `cpu_baseline`, unless "
+                         "--no-cpu-baseline), the oracle's op tally, the host cost per frame, the instrumented single-stream pass (stage table, "
+                         "rooflines, exchange timings) and the HBM copy rate.  Default: set up, warm up, time --steps frames, print the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed frame computed as DIR/<name>.npy (float32 / float64; a fixed, "
+                         "seeded sample of every per-pixel, per-triangle and per-texel array: see dump_outputs)")
     from rend3_amd import scene_viewer as sv
     sv.add_arguments(ap)
     args = ap.parse_args(sv.normalize_argv(sys.argv[1:]))
@@ -258,7 +319,7 @@ def main():
     ambient, clear = info["ambient"], info["clear"]
     if args.shade_mode == "fast":
         r.set_shade_mode(1)
-    hbm_measured = r.hbm_copy_rate(1 << 30, 5)
+    hbm_measured = r.hbm_copy_rate(1 << 30, 5) if args.full else None
     exchange, native_comm, comm_note, split = None, False, None, None
     if distributed:
         r.evaluate_instructions()  # flush the world: the object buffer's capacity is final
@@ -334,14 +395,14 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    # ---------------------------------------------------------------- parity frames (N=1): camera steps 0 and 1, read-back of step 1
+    # ---------------------------------------------------------------- parity frames (N=1, --full): camera steps 0 and 1, read-back of step 1
+    # The warmup starts at camera step 2 whether or not they are rendered: a plain run times the same camera steps as --full.
     check = world == 1 and not args.no_cpu_baseline and not args.force_exchange
     hip_frame1 = None
-    step0 = 0
-    if check:
+    step0 = 2 if check else 0
+    if check and args.full:
         frame(0)
         hip_frame1 = frame(1, readback=True)
-        step0 = 2
     # ---------------------------------------------------------------- warmup + timed region
     for k in range(args.warmup):
         frame(step0 + k)
@@ -356,6 +417,52 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
+    # ---------------------------------------------------------------- what the last timed frame computed (--dump-outputs, rank 0)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(r, args.dump_outputs, args.samples)
+
+    def headline():
+        """The line every run prints: the metric over the timed steps and the workload it was measured on."""
+        cameras = 1 + len([l for l in r.dir_lights if l is not None])
+        return {
+            "metric": "shaded Mpixels/s @4K (whole frame: cull+compact all cameras, 4 shadow views, PBR opaque, tonemap)",
+            "value": round(WIDTH * HEIGHT * args.steps / elapsed / 1e6, 2), "unit": "Mpixels/s", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": round(1e3 * elapsed / args.steps, 4), "higher_is_better": True, "scaling": "strong",
+            "vs_baseline": None, "dtype": "f32", "data": info["data"],
+            "config": {"workload": info["workload"],
+                       "shade_mode": args.shade_mode,
+                       "objects": info["objects"], "triangles": info["triangles"], "cameras": cameras,
+                       "split_model": split,
+                       "parallelism": "single GPU" if world == 1 else (
+                           f"object-range split issued by the library (r3n_comm_init + r3n_comm_set_split): viewport objects by contiguous slot range balanced by "
+                           f"triangles x{world}, shadow views by view (broadcast on a shadow lane's stream), RCCL MAX all-reduce of the pass-1 depth plane in front "
+                           f"of Hi-Z, MAX reduce-scatter of the pass-2 keys onto the bands of {HEIGHT // world} rows, image rows all-gathered"
+                           + ("" if split is None else f"; chosen by the cost model: predicted {split['predicted_speedup']['objects']}x against {split['predicted_speedup']['rows']}x for rows")
+                           if native_comm and args.partition == "objects" else
+                           f"sort-first: every rank culls + draws every object into its band of {HEIGHT // world} rows (x{world}), shadow views by view "
+                           "(broadcast on a shadow lane's stream), pass-1 depth bands all-gathered over RCCL in front of Hi-Z, no key exchange, image rows all-gathered"
+                           + (" -- exchanges issued by the library itself (r3n_comm_init)" if native_comm else " -- exchanges through torch.distributed")
+                           + ("" if split is None else f"; chosen by the cost model: predicted {split['predicted_speedup']['rows']}x against {split['predicted_speedup']['objects']}x for objects")
+                           if native_comm or (exchange is not None and exchange.by_rows) else
+                           f"viewport objects by spatial partition (Morton order, owner bytes) x{world}, shadow views by view (broadcast), pass-1 depth and pass-2 keys "
+                           "MAX-reduced onto the row-band owners over RCCL all-to-all limited to each rank's screen-row extent, depth bands + image rows all-gathered"
+                           if exchange is not None and exchange.sparse is not None else
+                           f"viewport objects by slot range x{world}, shadow views by view (broadcast), RCCL MAX all-reduce of the pass-1 depth plane, MAX reduce-scatter of "
+                           "the pass-2 keys, row all-gather")},
+            "fps": round(args.steps / elapsed, 2),
+            "exchange_note": comm_note,
+            "mesh_buffer_bytes": info.get("mesh_bytes"), "unique_triangles": info.get("unique_triangles"),
+        }
+
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(headline()))
+        r.close()
+        if distributed:
+            dist.destroy_process_group()
+        return
+
+    # ---------------------------------------------------------------- --full: everything below is outside the headline figure
     # ---------------------------------------------------------------- host cost of a frame (outside the timed region)
     # In the timed loop the host runs ahead of the GPU until it waits for a pinned frame image still in flight, so its enqueue time
     # converges to the GPU's frame time.  Its OWN time per frame (Python glue + r3n_host_evaluate_frame + r3n_render_frame + the HIP
@@ -430,7 +537,6 @@ def main():
         pass
     if rank == 0:
         ms_per_step = 1e3 * elapsed / args.steps
-        mpix = WIDTH * HEIGHT * args.steps / elapsed / 1e6
         cameras = 1 + len([l for l in r.dir_lights if l is not None])
         stage_ms = {s: (ms / n_inst) for s, (ms, _n) in stages.items()}
         launches = {s: n / n_inst for s, (_ms, n) in stages.items()}
@@ -600,32 +706,8 @@ def main():
                           "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(frame_bytes / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
                           "note": "sum over the frame of every stage's algorithmic bytes (triangle culls, shadow rasterisers, resolve, object passes, Hi-Z) / "
                                   "ms_per_step; the frame is not one streaming kernel -- its largest stage is VALU-bound, the geometry stages issue- / latency-bound"}
-        result = {
-            "metric": "shaded Mpixels/s @4K (whole frame: cull+compact all cameras, 4 shadow views, PBR opaque, tonemap)",
-            "value": round(mpix, 2), "unit": "Mpixels/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
-            "dtype": "f32", "data": info["data"],
-            "config": {"workload": info["workload"],
-                       "shade_mode": args.shade_mode,
-                       "objects": info["objects"], "triangles": info["triangles"], "cameras": cameras,
-                       "split_model": split,
-                       "parallelism": "single GPU" if world == 1 else (
-                           f"object-range split issued by the library (r3n_comm_init + r3n_comm_set_split): viewport objects by contiguous slot range balanced by "
-                           f"triangles x{world}, shadow views by view (broadcast on a shadow lane's stream), RCCL MAX all-reduce of the pass-1 depth plane in front "
-                           f"of Hi-Z, MAX reduce-scatter of the pass-2 keys onto the bands of {HEIGHT // world} rows, image rows all-gathered"
-                           + ("" if split is None else f"; chosen by the cost model: predicted {split['predicted_speedup']['objects']}x against {split['predicted_speedup']['rows']}x for rows")
-                           if native_comm and args.partition == "objects" else
-                           f"sort-first: every rank culls + draws every object into its band of {HEIGHT // world} rows (x{world}), shadow views by view "
-                           "(broadcast on a shadow lane's stream), pass-1 depth bands all-gathered over RCCL in front of Hi-Z, no key exchange, image rows all-gathered"
-                           + (" -- exchanges issued by the library itself (r3n_comm_init)" if native_comm else " -- exchanges through torch.distributed")
-                           + ("" if split is None else f"; chosen by the cost model: predicted {split['predicted_speedup']['rows']}x against {split['predicted_speedup']['objects']}x for objects")
-                           if native_comm or (exchange is not None and exchange.by_rows) else
-                           f"viewport objects by spatial partition (Morton order, owner bytes) x{world}, shadow views by view (broadcast), pass-1 depth and pass-2 keys "
-                           "MAX-reduced onto the row-band owners over RCCL all-to-all limited to each rank's screen-row extent, depth bands + image rows all-gathered"
-                           if exchange is not None and exchange.sparse is not None else
-                           f"viewport objects by slot range x{world}, shadow views by view (broadcast), RCCL MAX all-reduce of the pass-1 depth plane, MAX reduce-scatter of "
-                           "the pass-2 keys, row all-gather")},
-            "fps": round(args.steps / elapsed, 2),
+        result = headline()
+        result.update({
             "host_ms_per_frame": host_ms,
             "culled_objects_per_s": round(info["objects"] * cameras / (cull_ms * 1e-3), 1) if cull_ms > 0 else None,
             "culled_mtris_per_s": round(info["triangles"] * cameras / (cull_ms * 1e-3) / 1e6, 1) if cull_ms > 0 else None,
@@ -641,9 +723,7 @@ def main():
             "hbm_copy_rate_measured_GBps": round(hbm_measured, 1),
             "exchange_ms_per_frame": exchange_ms,
             "exchange_bytes_per_frame": exchange_bytes,
-            "exchange_note": comm_note,
-            "mesh_buffer_bytes": info.get("mesh_bytes"), "unique_triangles": info.get("unique_triangles"),
-        }
+        })
 
     # ---------------------------------------------------------------- CPU baseline: the oracle ("port"), rank 0, N=1 only
     if rank == 0 and world == 1 and not args.no_cpu_baseline:

@@ -115,7 +115,7 @@ def test_gpu_bench_scene_line():
     the benchmarked frame and the CPU baseline of the same asset."""
     file, flags = ASSETS["static_gltf"]
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--scene", os.path.join(GOLD, file), "--resolution", "1280x720", "--steps", "6",
-           "--warmup", "2", "--cpu-sample-frames", "2"] + flags
+           "--warmup", "2", "--cpu-sample-frames", "2", "--full"] + flags
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
     assert res.returncode == 0, res.stderr[-2000:]
     d = json.loads(res.stdout.strip().splitlines()[-1])

@@ -30,7 +30,7 @@ def _run(extra, n=2, size=("1280x720", 1280 * 720)):
     env = dict(os.environ, R3N_BENCH_SHARE_GPU="1", R3N_RCCL_LIB=rccl_shim.build(), HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n), "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "4", "--warmup", "2",
-           "--objects", "300", "--tris", "150000", "--resolution", size[0], "--no-cpu-baseline"] + extra
+           "--objects", "300", "--tris", "150000", "--resolution", size[0], "--no-cpu-baseline", "--full"] + extra
     # its own session: on a time-out the launcher AND every rank are killed (nothing keeps the GPU or the suite)
     limit = float(os.environ.get("R3N_MP_LIMIT", "150")) + 30.0 * (n > 2)
     proc = subprocess.Popen(cmd, env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, start_new_session=True)

@@ -6,7 +6,7 @@ lib=$(python -c "import sys; sys.path.insert(0,'tests'); import rccl_shim; print
 for part in auto objects; do
   for cfg in 3 4; do
     R3N_BENCH_SHARE_GPU=1 R3N_RCCL_LIB=$lib timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 \
-      bench.py --gpus 2 --steps 10 --warmup 3 --partition $part --config $cfg > $out/bench_n2_${part}_cfg$cfg.json 2> $out/bench_n2_${part}_cfg$cfg.err
+      bench.py --full --gpus 2 --steps 10 --warmup 3 --partition $part --config $cfg > $out/bench_n2_${part}_cfg$cfg.json 2> $out/bench_n2_${part}_cfg$cfg.err
     python - $out/bench_n2_${part}_cfg$cfg.json <<'PY'
 import json,sys
 try:

@@ -7,7 +7,7 @@ timeout 900 python -m pytest tests -m gpu -x -q -k "two_process or exchange or s
 fi
 for part in "rows" "rows --python-exchange" "slots"; do
   tag=$(echo $part | tr -d ' -')
-  timeout 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29611 bench.py --gpus 1 --force-exchange --partition $part --steps 60 --warmup 8 > $out/bench_ex_$tag.json 2> $out/bench_ex_$tag.err; echo "exchange $part rc=$?"
+  timeout 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29611 bench.py --full --gpus 1 --force-exchange --partition $part --steps 60 --warmup 8 > $out/bench_ex_$tag.json 2> $out/bench_ex_$tag.err; echo "exchange $part rc=$?"
   python - $out/bench_ex_$tag.json <<'PY'
 import json,sys
 try:
@@ -16,5 +16,5 @@ except Exception as e: print("FAILED", e)
 PY
   tail -3 $out/bench_ex_$tag.err | cut -c1-300
 done
-timeout 300 python bench.py --no-cpu-baseline --steps 60 --warmup 8 > $out/bench_plain.json 2>/dev/null; python -c "
+timeout 300 python bench.py --full --no-cpu-baseline --steps 60 --warmup 8 > $out/bench_plain.json 2>/dev/null; python -c "
 import json;d=json.load(open('$out/bench_plain.json'));print('plain',d['ms_per_step'],'host',d['host_ms_per_frame'])"

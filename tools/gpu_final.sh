@@ -12,7 +12,7 @@ root=$(pwd)
 out=$root/gpurun_out/$tag
 mkdir -p "$out"
 export TMPDIR=/tmp
-B="python $root/bench.py"
+B="python $root/bench.py --full"
 line() { python - "$1" <<'PY'
 import json,sys
 try:

@@ -10,7 +10,7 @@ out=$root/gpurun_out/$tag
 mkdir -p "$out"
 export TMPDIR=/tmp
 cd /tmp
-B="python $root/bench.py --no-cpu-baseline --steps 6 --warmup 2 $extra"
+B="python $root/bench.py --full --no-cpu-baseline --steps 6 --warmup 2 $extra"
 rocprofv3 -L > "$out/counters_avail.txt" 2>&1
 grep -i -o "SQC_[A-Z_0-9]*\|SQ_IFETCH[A-Z_0-9]*\|SQ_INST[A-Z_0-9]*" "$out/counters_avail.txt" | sort -u | tr '\n' ' ' | head -c 3000; echo
 run() {  # name, counters...

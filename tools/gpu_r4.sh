@@ -21,7 +21,7 @@ PY
 }
 pmc() {  # name, env, counters...
   local name=$1 envs=$2; shift 2
-  ( cd /tmp; env $envs timeout 300 rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d "$out/pmc_$name" -o "$name" -- python $root/bench.py --no-cpu-baseline --steps 6 --warmup 2 > /dev/null 2> "$out/pmc_$name.err" ) || echo "pmc $name failed: $(tail -2 $out/pmc_$name.err)"
+  ( cd "$(mktemp -d)"; env $envs timeout 300 rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d "$out/pmc_$name" -o "$name" -- python $root/bench.py --full --no-cpu-baseline --steps 6 --warmup 2 > /dev/null 2> "$out/pmc_$name.err" ) || echo "pmc $name failed: $(tail -2 $out/pmc_$name.err)"
   find "$out/pmc_$name" -name "*_kernel_trace.csv" -delete
 }
 for w in "$@"; do
@@ -40,20 +40,20 @@ for w in "$@"; do
       done;;
     quick_texf) R3N_LIB=$root/variants/lib_texf.so timeout 900 python -m pytest tests -m gpu -x -q -k "textured or bistro or golden_static or float_textures or encoded or scene_viewer" > "$out/pytest_texf.log" 2>&1; echo "pytest texf rc=$?"; tail -4 "$out/pytest_texf.log"; grep -E '^E ' "$out/pytest_texf.log" | head -8;;
     tests) timeout 1500 python -m pytest tests -m gpu -q --durations=8 > "$out/pytest.log" 2>&1; echo "pytest rc=$?"; tail -15 "$out/pytest.log"; grep -E '^E ' "$out/pytest.log" | head -8;;
-    bench) python bench.py --steps 100 --warmup 10 > "$out/bench.json" 2> "$out/bench.err"; line "$out/bench.json"; tail -3 "$out/bench.err";;
+    bench) python bench.py --full --steps 100 --warmup 10 > "$out/bench.json" 2> "$out/bench.err"; line "$out/bench.json"; tail -3 "$out/bench.err";;
     classes)
       for rep in 1 2; do
-        R3N_RESOLVE_CLASSES=0 python bench.py --steps 100 --warmup 10 --no-cpu-baseline > "$out/bench_general_$rep.json" 2>/dev/null; line "$out/bench_general_$rep.json"
-        python bench.py --steps 100 --warmup 10 --no-cpu-baseline > "$out/bench_classes_$rep.json" 2>/dev/null; line "$out/bench_classes_$rep.json"
+        R3N_RESOLVE_CLASSES=0 python bench.py --full --steps 100 --warmup 10 --no-cpu-baseline > "$out/bench_general_$rep.json" 2>/dev/null; line "$out/bench_general_$rep.json"
+        python bench.py --full --steps 100 --warmup 10 --no-cpu-baseline > "$out/bench_classes_$rep.json" 2>/dev/null; line "$out/bench_classes_$rep.json"
       done
-      python bench.py --steps 100 --warmup 10 --no-cpu-baseline --shade-mode fast > "$out/bench_fast.json" 2>/dev/null; line "$out/bench_fast.json"
-      python bench.py --steps 100 --warmup 10 --no-cpu-baseline --untextured > "$out/bench_untextured.json" 2>/dev/null; line "$out/bench_untextured.json";;
+      python bench.py --full --steps 100 --warmup 10 --no-cpu-baseline --shade-mode fast > "$out/bench_fast.json" 2>/dev/null; line "$out/bench_fast.json"
+      python bench.py --full --steps 100 --warmup 10 --no-cpu-baseline --untextured > "$out/bench_untextured.json" 2>/dev/null; line "$out/bench_untextured.json";;
     variants) python tools/variants.py run --steps 120 > "$out/variants.txt" 2>&1; cat "$out/variants.txt"; python tools/variants.py run --steps 120 > "$out/variants2.txt" 2>&1; cat "$out/variants2.txt";;
     serial)
       cd /tmp
       for lib in $root/variants/lib_*.so; do
         name=$(basename $lib .so)
-        R3N_LIB=$lib R3N_SINGLE_STREAM=1 R3N_PIPELINE=0 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/ser_$name -o k -- python $root/bench.py --no-cpu-baseline --steps 30 --warmup 5 > $out/ser_$name.json 2> $out/ser_$name.err
+        R3N_LIB=$lib R3N_SINGLE_STREAM=1 R3N_PIPELINE=0 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/ser_$name -o k -- python $root/bench.py --full --no-cpu-baseline --steps 30 --warmup 5 > $out/ser_$name.json 2> $out/ser_$name.err
         f=$(find $out/ser_$name -name "*kernel_stats.csv" | head -1)
         echo "== $name"; head -14 "$f" | cut -c1-150
         find $out/ser_$name -name "*_kernel_trace.csv" -delete

@@ -30,7 +30,7 @@ for w in "$@"; do
       timeout 1500 python tools/soak_native.py --shim async --serial "$ser" --repeat "$rep" --limit 90 --out "$out/async_serial$ser" > "$out/async_serial${ser}_stdout.log" 2>&1; echo "async serial=$ser rc=$?"; tail -2 "$out/async_serial${ser}_stdout.log" | cut -c1-500
       timeout 1500 python tools/soak_native.py --shim async --serial "$ser" --many --repeat "$rep" --limit 90 --out "$out/async_many_serial$ser" > "$out/async_many_serial${ser}_stdout.log" 2>&1; echo "async many serial=$ser rc=$?"; tail -2 "$out/async_many_serial${ser}_stdout.log" | cut -c1-500;;
     bench:*)  # bench:NAME:FLAGS -- one bench.py line, stage table printed
-      IFS=: read -r _ bname bflags <<< "$w"; timeout 1200 python bench.py $bflags > "$out/bench_$bname.json" 2> "$out/bench_$bname.err"; python - "$out/bench_$bname.json" <<'PY'
+      IFS=: read -r _ bname bflags <<< "$w"; timeout 1200 python bench.py --full $bflags > "$out/bench_$bname.json" 2> "$out/bench_$bname.err"; python - "$out/bench_$bname.json" <<'PY'
 import json,sys
 try:
     l=[x for x in open(sys.argv[1]).read().splitlines() if x.startswith("{")][-1]

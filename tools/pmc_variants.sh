@@ -5,7 +5,7 @@ set -u
 root=$(pwd); out=$root/gpurun_out/${1:-pmcv}; mkdir -p $out; export TMPDIR=/tmp
 for lib in $root/variants/lib_*.so; do
   name=$(basename $lib .so)
-  ( cd /tmp; R3N_LIB=$lib R3N_SINGLE_STREAM=1 timeout 300 rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_INSTS_LDS SQ_ACTIVE_INST_VALU SQ_BUSY_CYCLES SQ_WAVE_CYCLES --output-format csv -d $out/$name -o p -- python $root/bench.py --no-cpu-baseline --steps 6 --warmup 2 > /dev/null 2> $out/$name.err )
+  ( cd "$(mktemp -d)"; R3N_LIB=$lib R3N_SINGLE_STREAM=1 timeout 300 rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_INSTS_LDS SQ_ACTIVE_INST_VALU SQ_BUSY_CYCLES SQ_WAVE_CYCLES --output-format csv -d $out/$name -o p -- python $root/bench.py --full --no-cpu-baseline --steps 6 --warmup 2 > /dev/null 2> $out/$name.err )
   find $out/$name -name "*_kernel_trace.csv" -delete
   f=$(find $out/$name -name "*counter_collection.csv" | head -1)
   python - "$f" "$name" <<'PY'

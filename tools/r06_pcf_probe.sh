@@ -7,7 +7,7 @@ for v in pcfocc4 occ4 pcf; do
 done
 echo "=== MSAA bench, occupancy target 4 against 5"
 for v in base occ4; do
-  R3N_LIB=$PWD/variants/lib_$v.so python bench.py --samples 4 --no-cpu-baseline --steps 30 --warmup 5 2>/dev/null | python -c "
+  R3N_LIB=$PWD/variants/lib_$v.so python bench.py --full --samples 4 --no-cpu-baseline --steps 30 --warmup 5 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$v', d['ms_per_step'], {k:round(v*1e3,1) for k,v in d['stage_ms_per_frame'].items() if v})"
 done
