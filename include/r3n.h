@@ -236,7 +236,8 @@ typedef struct r3n_pose_request16 {
 
 typedef struct r3n_config {
     uint32_t struct_size;      /* sizeof(r3n_config) */
-    uint32_t max_big_items;    /* raster work-queue capacity (0 = default 4 Mi items) */
+    uint32_t max_big_items;    /* raster work-queue capacity in items (0 = default 2 Mi: 32 sub-queues of 65 536).  Divided by 32 and
+                                * raised to the floor of 1 024 per sub-queue; only the test hook R3N_BIG_CAPACITY goes below it */
     uint32_t shade_mode;       /* R3N_SHADE_EXACT | R3N_SHADE_FAST */
     uint32_t _pad;
     uint64_t reserved[2];

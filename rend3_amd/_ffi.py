@@ -142,9 +142,14 @@ class FrameDesc(ctypes.Structure):
                 ("exchange", EXCHANGE_FN), ("exchange_user", vp)]
 
 
+class Config(ctypes.Structure):
+    """r3n_config"""
+    _fields_ = [("struct_size", u32), ("max_big_items", u32), ("shade_mode", u32), ("_pad", u32), ("reserved", u64 * 2)]
+
+
 # sizes the C side pins with static_asserts (rend3_amd/csrc/layouts.h)
 assert ctypes.sizeof(ShadowView272) == 272 and ctypes.sizeof(HostCamera144) == 144 and ctypes.sizeof(FrameDesc) == 152
-assert ctypes.sizeof(HostFrame) == 26712
+assert ctypes.sizeof(HostFrame) == 26712 and ctypes.sizeof(Config) == 32
 
 _LIB = None
 
@@ -184,11 +189,16 @@ def ptr(a):
     return a.ctypes.data_as(vp)
 
 
+ERR_CAPACITY = -6  # R3N_ERR_CAPACITY
+
+
 class R3nError(RuntimeError):
-    pass
+    def __init__(self, message, code=None):
+        super().__init__(message)
+        self.code = code  # the r3n_* return code, None for errors raised on the Python side
 
 
 def check(ctx, code, what):
     if code != 0:
         msg = lib().r3n_last_error(ctx)
-        raise R3nError(f"{what} failed ({code}): {msg.decode() if msg else ''}")
+        raise R3nError(f"{what} failed ({code}): {msg.decode() if msg else ''}", code)

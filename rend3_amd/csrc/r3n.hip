@@ -808,6 +808,12 @@ r3n_ctx *r3n_create(int hip_device, const r3n_config *config) {
     if (const char *e5 = std::getenv("R3N_RESOLVE_CLASSES")) c->resolve_classes = !(e5[0] == '0');
     if (const char *e6 = std::getenv("R3N_ALWAYS_FORK")) c->always_fork = e6[0] == '1';
     if (const char *e3 = std::getenv("R3N_EDGE_CAPACITY")) c->edge_capacity_override = (uint32_t)std::strtoul(e3, nullptr, 10);
+    // test hooks of the overflow paths (tests/test_capacity_gpu.py): entries per work sub-queue, below the ABI's floor of 1024, and
+    // blend fragment nodes.  0 or a value that does not parse keeps the size.  Set before the work queues are allocated below.
+    if (const char *e7 = std::getenv("R3N_BIG_CAPACITY"))
+        if (const uint32_t n = (uint32_t)std::strtoul(e7, nullptr, 10)) c->big_capacity = n;
+    if (const char *e8 = std::getenv("R3N_FRAG_CAPACITY"))
+        if (const uint32_t n = (uint32_t)std::strtoul(e8, nullptr, 10)) c->frag_capacity = n;
     if (hipStreamCreateWithPriority(&c->shade, hipStreamNonBlocking, (int)c->tune.prio_shade - 1) != hipSuccess ||
         hipEventCreateWithFlags(&c->vp_ev, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&c->shade_done[0], hipEventDisableTiming) != hipSuccess ||
@@ -2656,12 +2662,18 @@ int r3n_output_work_enqueued(r3n_ctx *c) {
 }
 
 // ------------------------------------------------------------------------------------------------ readbacks
-static int d2h(r3n_ctx *c, void *dst, const void *src, size_t bytes) {
+// A read-back reports the status word (R3N_ERR_CAPACITY of an earlier frame) only after it has filled every output: a read-back of
+// several copies copies with copy_d2h and reports at its end -- one that stopped at its first copy would hand out raw device data.
+static int copy_d2h(r3n_ctx *c, void *dst, const void *src, size_t bytes) {
     HIP_TRY(c, hipSetDevice(c->device));
     TRY(join_lanes(c));
     TRY(join_shade(c));
     HIP_TRY(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_WAIT(c, hipStreamSynchronize(c->stream));
+    return R3N_OK;
+}
+static int d2h(r3n_ctx *c, void *dst, const void *src, size_t bytes) {
+    TRY(copy_d2h(c, dst, src, bytes));
     return check_async_status(c);
 }
 
@@ -2669,9 +2681,9 @@ int r3n_readback_visible_objects(r3n_ctx *c, r3n_camera cam, uint8_t *flags, uin
     CamState *s = c ? find_cam(c, cam, false) : nullptr;
     if (!s || s->last < 0 || !flags) return fail(c, R3N_ERR_STATE, "readback_visible_objects: camera never culled");
     if (capacity < c->capacity) return fail(c, R3N_ERR_INVALID_ARG, "readback_visible_objects: buffer too small");
-    TRY(d2h(c, flags, s->vis_flags.p, c->capacity));
+    TRY(copy_d2h(c, flags, s->vis_flags.p, c->capacity));
     for (uint32_t i = 0; i < c->capacity; ++i) flags[i] &= (uint8_t)R3N_VIS_DRAWN;  // (bit 1: frustum test alone, kernels_cull.h R3N_VIS_INSIDE)
-    return R3N_OK;
+    return check_async_status(c);
 }
 
 int r3n_readback_draw_calls(r3n_ctx *c, r3n_camera cam, r3n_indirect_call calls[6]) {
@@ -2679,8 +2691,8 @@ int r3n_readback_draw_calls(r3n_ctx *c, r3n_camera cam, r3n_indirect_call calls[
     if (!s || s->last < 0) return fail(c, R3N_ERR_STATE, "readback_draw_calls: camera never culled");
     r3n_sub_counts sc;
     r3n_cull_counts counts;
-    TRY(d2h(c, &sc, s->sub_counts[s->last].p, sizeof sc));
-    TRY(d2h(c, &counts, s->counts[s->last].p, sizeof counts));
+    TRY(copy_d2h(c, &sc, s->sub_counts[s->last].p, sizeof sc));
+    TRY(copy_d2h(c, &counts, s->counts[s->last].p, sizeof counts));
     for (int list = 0; list < 2; ++list)
         for (int k = 0; k < 3; ++k) {
             uint32_t n = 0;
@@ -2688,7 +2700,7 @@ int r3n_readback_draw_calls(r3n_ctx *c, r3n_camera cam, r3n_indirect_call calls[
             // cull.wgsl:47-73: vertex_count = 3 per appended triangle, instance_count 1, base_index = first slot * 3
             calls[list * 3 + k] = {n * 3u, 1u, counts.region_base[k] * 3u, 0, 0u};
         }
-    return R3N_OK;
+    return check_async_status(c);
 }
 
 int r3n_readback_triangle_sets(r3n_ctx *c, r3n_camera cam, uint8_t *pass, uint8_t *residual, uint64_t n) {
@@ -2698,12 +2710,12 @@ int r3n_readback_triangle_sets(r3n_ctx *c, r3n_camera cam, uint8_t *pass, uint8_
     const int idx = s->last;
     const uint32_t cap = c->capacity;
     r3n_cull_counts counts;
-    TRY(d2h(c, &counts, s->counts[idx].p, sizeof counts));
+    TRY(copy_d2h(c, &counts, s->counts[idx].p, sizeof counts));
     std::vector<uint32_t> slot_base(cap), tri_base(cap);
-    TRY(d2h(c, slot_base.data(), s->slot_base[idx].p, (size_t)cap * 4));
-    TRY(d2h(c, tri_base.data(), c->tri_base.p, (size_t)cap * 4));
+    TRY(copy_d2h(c, slot_base.data(), s->slot_base[idx].p, (size_t)cap * 4));
+    TRY(copy_d2h(c, tri_base.data(), c->tri_base.p, (size_t)cap * 4));
     std::vector<unsigned long long> mask(std::max(1u, counts.total_waves));
-    if (counts.total_waves) TRY(d2h(c, mask.data(), s->mask[idx].p, (size_t)counts.total_waves * 8));
+    if (counts.total_waves) TRY(copy_d2h(c, mask.data(), s->mask[idx].p, (size_t)counts.total_waves * 8));
     if (pass) {
         std::memset(pass, 0, n);
         for (uint32_t o = 0; o < cap; ++o) {
@@ -2718,19 +2730,19 @@ int r3n_readback_triangle_sets(r3n_ctx *c, r3n_camera cam, uint8_t *pass, uint8_
         std::memset(residual, 0, n);
         if (cam == R3N_CAMERA_VIEWPORT) {
             r3n_sub_counts sc;
-            TRY(d2h(c, &sc, s->sub_counts[idx].p, sizeof sc));
+            TRY(copy_d2h(c, &sc, s->sub_counts[idx].p, sizeof sc));
             for (uint32_t k = 0; k < 3; ++k)
                 for (uint32_t q = 0; q < R3N_SUBQ; ++q) {
                     const uint32_t cnt = sc.n[1][k][q];
                     if (!cnt) continue;
                     std::vector<r3n_tri_ref> refs(cnt);
-                    TRY(d2h(c, refs.data(), s->residual.as<r3n_tri_ref>() + (size_t)(k * R3N_SUBQ + q) * s->subcap[idx],
+                    TRY(copy_d2h(c, refs.data(), s->residual.as<r3n_tri_ref>() + (size_t)(k * R3N_SUBQ + q) * s->subcap[idx],
                             (size_t)cnt * sizeof(r3n_tri_ref)));
                     for (const auto &r : refs) residual[(uint64_t)tri_base[r.object] + r.triangle] = 1;
                 }
         }
     }
-    return R3N_OK;
+    return check_async_status(c);
 }
 
 int r3n_readback_raster_stats(r3n_ctx *c, uint32_t big_items[64]) {
@@ -2739,12 +2751,12 @@ int r3n_readback_raster_stats(r3n_ctx *c, uint32_t big_items[64]) {
     std::vector<uint32_t> raw(64 * R3N_BIGQ);
     for (int f = 0; f < 64; ++f) big_items[f] = 0;
     for (int lane = 0; lane < 1 + R3N_QLANES; ++lane) {
-        TRY(d2h(c, raw.data(), c->big_count[lane].p, raw.size() * 4));
+        TRY(copy_d2h(c, raw.data(), c->big_count[lane].p, raw.size() * 4));
         const int base = lane == 0 ? 0 : 16 + 12 * (lane - 1), n = lane == 0 ? 16 : 12;
         for (int f = 0; f < n; ++f)
             for (int q = 0; q < R3N_BIGQ; ++q) big_items[base + f] += raw[f * R3N_BIGQ + q];
     }
-    return R3N_OK;
+    return check_async_status(c);
 }
 
 int r3n_readback_baked(r3n_ctx *c, r3n_camera cam, float *out, uint32_t capacity) {
@@ -2778,7 +2790,7 @@ int r3n_readback_depth(r3n_ctx *c, float *depth) {
     if (!c || !c->vis.p || !depth) return fail(c, R3N_ERR_STATE, "readback_depth: no frame");
     const size_t n = (size_t)c->width * c->height, S = c->samples;
     std::vector<uint64_t> keys(n * S);
-    TRY(d2h(c, keys.data(), c->vis.p, n * S * 8));
+    TRY(copy_d2h(c, keys.data(), c->vis.p, n * S * 8));
     for (size_t i = 0; i < n; ++i) {
         if (S == 1) {
             const uint32_t zb = (uint32_t)(keys[i] >> 32);
@@ -2794,7 +2806,7 @@ int r3n_readback_depth(r3n_ctx *c, float *depth) {
             depth[i] = nearest;
         }
     }
-    return R3N_OK;
+    return check_async_status(c);
 }
 
 int r3n_readback_hiz(r3n_ctx *c, float *pyr, uint64_t count) {
@@ -2821,10 +2833,10 @@ int r3n_readback_output(r3n_ctx *c, uint8_t *rgba8, float *rgba_f32) {
         TRY(join_shade(c));
         TRY(ensure(c, c->out_f32, n * 16, false, -1));
         TRY(launch_tonemap(c, c->out_f32.as<float4>()));
-        TRY(d2h(c, rgba_f32, c->out_f32.p, n * 16));
+        TRY(copy_d2h(c, rgba_f32, c->out_f32.p, n * 16));
     }
-    if (rgba8) TRY(d2h(c, rgba8, c->out8.p, n * 4));
-    return R3N_OK;
+    if (rgba8) TRY(copy_d2h(c, rgba8, c->out8.p, n * 4));
+    return check_async_status(c);
 }
 
 // ------------------------------------------------------------------------------------------------ timing

@@ -175,9 +175,12 @@ class EvalOutput:
 class Renderer:
     """World bookkeeping feeding the object/mesh/material/light buffers of the C ABI."""
 
-    def __init__(self, handedness=host.LEFT, aspect_ratio=None, device=0):
+    def __init__(self, handedness=host.LEFT, aspect_ratio=None, device=0, max_big_items=None):
         self.lib = _ffi.lib()
-        self.ctx = self.lib.r3n_create(device, None)
+        config = None
+        if max_big_items is not None:  # r3n_config.max_big_items: raster work-queue capacity (the library keeps a floor, r3n.h)
+            config = _ffi.Config(struct_size=ctypes.sizeof(_ffi.Config), max_big_items=int(max_big_items))
+        self.ctx = self.lib.r3n_create(device, ctypes.byref(config) if config is not None else None)
         if not self.ctx:
             raise _ffi.R3nError("r3n_create failed: " + self.lib.r3n_create_error().decode())
         self.handedness = handedness
@@ -213,6 +216,9 @@ class Renderer:
         self._lights_version = 0
         self._capacity_sent = None
         self._resolution = (0, 0)
+        # None: an R3N_ERR_CAPACITY return raises like every other error.  A list: it is recorded there as (call, code) instead -- the
+        # report names an EARLIER frame, the call itself did its work (a read-back has filled its buffer) and no frame is refused
+        self.capacity_reports = None
         self._write_objects([], force_capacity=True)
 
     def close(self):
@@ -227,6 +233,9 @@ class Renderer:
             pass
 
     def _check(self, code, what):
+        if code == _ffi.ERR_CAPACITY and self.capacity_reports is not None:
+            self.capacity_reports.append((what, code))
+            return
         _ffi.check(self.ctx, code, what)
 
     # ------------------------------------------------------------------ world edits
@@ -839,6 +848,13 @@ class Renderer:
         rgba_f = np.zeros((height, width, 4), dtype=f32)
         self._check(lib.r3n_readback_output(ctx, _ffi.ptr(rgba8), _ffi.ptr(rgba_f)), "readback_output")
         out.update(vis=vis, atlas=atlas, atlas_size=(aw, ah), hdr16=hdr16, rgba8=rgba8, rgba_f32=rgba_f)
+        return out
+
+    def raster_stats(self):
+        """r3n_readback_raster_stats: work items each r3n_forward call of the last frame queued, [0..16) the viewport's, then 12 per
+        shadow lane -- counted as requested, so a call above 32 x the sub-queue capacity overflowed a sub-queue."""
+        out = np.zeros(64, dtype=np.uint32)
+        self._check(self.lib.r3n_readback_raster_stats(self.ctx, _ffi.ptr(out)), "r3n_readback_raster_stats")
         return out
 
     def readback_mesh_words(self, byte_offset, n_words):

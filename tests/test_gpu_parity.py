@@ -1327,6 +1327,7 @@ RUNTIME_SWITCHES = [
     {"R3N_FRAME_NODES": "1"},        # the host mirror issues the frame node by node (one C call per reference node) instead of r3n_render_frame
     {"R3N_ALWAYS_FORK": "1"},        # the shadow lanes wait for the main stream at every fork (no epoch gate): a main-stream producer that forgot its epoch bump would differ from the default run
     {"R3N_RESOLVE_CLASSES": "0"},    # the general resolve kernel for every tile instead of one kernel per material class (kernels_shade.h R3N_CLS_*)
+    {"R3N_BIG_CAPACITY": "1"},       # one entry per raster work sub-queue: the producers scan what does not fit themselves (kernels_raster.h raster_small_body)
     # launch parameters (r3n.hip Tune: dynamic-LDS occupancy caps and grid sizes; tools/tune_caps.py searches them): results never depend on them
     {"R3N_TUNE": "big_lds=16384 vp_big_lds=0 small_lds=0 vp_small_lds=32768 cut_big_lds=49152 vp_cut_big_lds=32768 cut_small_lds=8192 "
                  "vp_cut_small_lds=16384 cull_lds=32768 vp_cull_lds=16384 resolve_lds=8192 big_grid=1024 small_grid=512"},
@@ -1340,8 +1341,12 @@ def test_runtime_switches(r3, monkeypatch, env, scenario):
     path: all of compare_frames -- sets of every camera, keys, shadow atlas, HDR bit-identical to the oracle."""
     for k, v in env.items():
         monkeypatch.setenv(k, v)
-    for f, fo, fp in _scenario_frames(r3, scenario, lambda hand, aspect: r3.Renderer(hand, aspect)):
+    made = []
+    for f, fo, fp in _scenario_frames(r3, scenario, lambda hand, aspect: made.append(r3.Renderer(hand, aspect)) or made[-1]):
         compare_frames(fo, fp, f"{scenario} {env} frame {f}")
+        if "R3N_BIG_CAPACITY" in env:  # the queue-full path ran: a call queued more items than the 32 sub-queues hold
+            assert made[0].raster_stats().max() > 32 * int(env["R3N_BIG_CAPACITY"]), f"{scenario} frame {f}: no sub-queue overflowed"
+            made[0].sync()  # (a capacity report would raise here)
     if scenario == "bistro":
         assert len(fo["shadows"]) == 4 and all(s["pass"].sum() > 200 for s in fo["shadows"]) and (fo["atlas"] != 0).mean() > 0.05
 

@@ -243,6 +243,8 @@ def flip_key(st, pair):
     m = rng.randint(len(o.materials))
     key = (o.materials[m][1] + 1 + rng.randint(2)) % 3
     cutout = rng.uniform(0.1, 0.9) if key == scenes.CUTOUT else 0.0
+    if key == scenes.BLEND and not st.get("blend_flips", True):
+        key = scenes.OPAQUE  # same draws; a slice without translucent objects (tests/test_capacity_gpu.py)
     for r, _hm, _mk in pair:
         rec = np.array(r.materials[m][0], dtype=f32, copy=True)
         rec[50] = f32(cutout)
@@ -259,7 +261,8 @@ def run_mutating_case(r3, c):
         hp = build(p, r3.host, r3.material_record, c)
         assert ho == hp
         pair = ((o, oh, omk), (p, r3.host, r3.material_record))
-        st = dict(live=list(ho), w=c["w"], h=c["h"], samples=c["samples"], dir=c["lights"], point=c["point_lights"], mesh=[], mat=[])
+        st = dict(live=list(ho), w=c["w"], h=c["h"], samples=c["samples"], dir=c["lights"], point=c["point_lights"], mesh=[], mat=[],
+                  blend_flips=c.get("blend_flips", True))
         for r, hm, mk in pair:
             pos, idx, nrm = scenes.icosphere(1)
             if c["handedness"] == oh.LEFT:
