@@ -93,7 +93,8 @@ pub const R3N_STAGE_EXCHANGE_ROWS: i32 = 16;
 pub const R3N_STAGE_EXCHANGE_KEYS: i32 = 17;
 pub const R3N_STAGE_RASTER_CUT: i32 = 18;
 pub const R3N_STAGE_RASTER_BIG_CUT: i32 = 19;
-pub const R3N_STAGE_COUNT: i32 = 20;
+pub const R3N_STAGE_SKYBOX: i32 = 20;
+pub const R3N_STAGE_COUNT: i32 = 21;
 
 #[repr(C)]
 pub struct r3n_ctx {
@@ -350,6 +351,8 @@ extern "C" {
     pub fn r3n_materials_write(ctx: *mut r3n_ctx, slots: *const u32, records: *const r3n_material208, keys: *const u8, n: u32) -> c_int;
     pub fn r3n_textures_write(ctx: *mut r3n_ctx, descs: *const r3n_texture_desc32, n_textures: u32, texels: *const u32, n_texels: u64) -> c_int;
     pub fn r3n_textures_write_encoded(ctx: *mut r3n_ctx, descs: *const r3n_texture_desc32, n_textures: u32, payload: *const c_void, payload_bytes: u64) -> c_int;
+    pub fn r3n_texture_cubes_write(ctx: *mut r3n_ctx, descs: *const r3n_texture_desc32, n_cubes: u32, texels: *const u32, n_texels: u64) -> c_int;
+    pub fn r3n_skybox_set(ctx: *mut r3n_ctx, cube_id: u32) -> c_int;
     pub fn r3n_blend_order_write(ctx: *mut r3n_ctx, objects_back_to_front: *const u32, n: u32) -> c_int;
     pub fn r3n_lights_write(ctx: *mut r3n_ctx, directional_buffer: *const c_void, directional_bytes: u64, point_buffer: *const c_void, point_bytes: u64) -> c_int;
     pub fn r3n_set_output_format(ctx: *mut r3n_ctx, format: u32) -> c_int;
@@ -365,6 +368,7 @@ extern "C" {
     pub fn r3n_shadow_viewport(ctx: *mut r3n_ctx, shadow_camera: u32, x: u32, y: u32, size: u32) -> c_int;
     pub fn r3n_forward(ctx: *mut r3n_ctx, camera: u32, pass: u32, source: u32, material_key: u32) -> c_int;
     pub fn r3n_resolve_opaque(ctx: *mut r3n_ctx) -> c_int;
+    pub fn r3n_skybox(ctx: *mut r3n_ctx) -> c_int;
     pub fn r3n_tonemap(ctx: *mut r3n_ctx, host_rgba8: *mut c_void, pitch_bytes: u64) -> c_int;
     pub fn r3n_hdr_write(ctx: *mut r3n_ctx, rgba16f: *const u16, first_pixel: u64, n_pixels: u64) -> c_int;
     pub fn r3n_frame_end(ctx: *mut r3n_ctx) -> c_int;

@@ -277,6 +277,18 @@ int r3n_textures_write(r3n_ctx *ctx, const r3n_texture_desc32 *descs, uint32_t n
  *      150).  Snorm / float / 16-bit / ETC2 / ASTC / BC6H formats -> R3N_ERR_UNSUPPORTED. */
 int r3n_textures_write_encoded(r3n_ctx *ctx, const r3n_texture_desc32 *descs, uint32_t n_textures, const void *payload,
                                uint64_t payload_bytes);
+/*      The cube textures (the reference's d2c_texture_manager, rend3/src/managers/texture.rs; Renderer::add_texture_cube): replaces
+ *      the context's whole cube array, which is separate from the bindless 2D array.  A cube is six square faces of width x width
+ *      RGBA8 texels, contiguous from desc.offset (in texels) in `texels`, in layer order +X, -X, +Y, -Y, +Z, -Z (what scene_viewer
+ *      uploads as right, left, top, bottom, front, back).  width != height, width == 0 or > 16384, faces outside `texels`
+ *      -> R3N_ERR_INVALID_ARG; formats other than R3N_TEXTURE_RGBA8_UNORM / _SRGB, or mips != 1 -> R3N_ERR_UNSUPPORTED (a cube's mip
+ *      level would follow from the derivatives of the direction; scene_viewer uploads MipmapCount::ONE).  stored_mips is ignored.
+ *      Synchronises.  A skybox bound to a cube that no longer exists (r3n_skybox_set) is unbound. */
+int r3n_texture_cubes_write(r3n_ctx *ctx, const r3n_texture_desc32 *descs, uint32_t n_cubes, const uint32_t *texels,
+                            uint64_t n_texels);
+/*      SkyboxRoutine::set_background_texture (rend3-routine/src/skybox.rs): cube_id 0 = no skybox, i + 1 = cube i of the array
+ *      above; an id past the array -> R3N_ERR_INVALID_ARG.  Between frames only (R3N_ERR_STATE inside one). */
+int r3n_skybox_set(r3n_ctx *ctx, uint32_t cube_id);
 /*      Draw order of the blend-key objects for the transparent pass: object slots back to front, as the CPU batcher
  *      sorts them every frame (rend3-routine/src/culling/batching.rs:146-176, Sorting::BLENDING: -distance^2 from the
  *      camera location to the object location).  Call once per frame before r3n_resolve_opaque (n may be 0). */
@@ -354,6 +366,11 @@ int r3n_forward(r3n_ctx *ctx, r3n_camera camera, uint32_t pass, uint32_t source,
  * r3n_blend_order_write, depth-tested against the opaque depth (no depth write) and alpha-blended into the HDR target
  * (pbr/routine.rs:113-118). */
 int r3n_resolve_opaque(r3n_ctx *ctx);
+/* SkyboxRoutine::add_to_graph (rend3-routine/src/skybox.rs, skybox.wgsl; base.rs:175): every sample whose depth the sky's 0.0
+ * passes GreaterEqual -- the cleared ones, and a triangle at depth exactly 0.0 -- takes the bound cube's colour in the direction of
+ * its PIXEL CENTRE (bilinear, level 0, seamless across faces; alpha 1).  Legal after r3n_resolve_opaque and before the transparent
+ * r3n_forward / r3n_tonemap of the same frame (else R3N_ERR_STATE); with no skybox bound it returns R3N_OK and enqueues nothing. */
+int r3n_skybox(r3n_ctx *ctx);
 /* TonemappingRoutine::add_to_graph (tonemapping.rs:108-147) + blit.wgsl into an Rgba8UnormSrgb target.
  * If `host_rgba8` is non-NULL the image is also copied out (synchronises), `pitch_bytes` per row. */
 int r3n_tonemap(r3n_ctx *ctx, void *host_rgba8, uint64_t pitch_bytes);
@@ -368,8 +385,8 @@ int r3n_frame_end(r3n_ctx *ctx);
  * (rend3-routine/src/base.rs:129-185, executed by RenderGraph::execute, rend3/src/graph/graph.rs:265-518) in the reference's
  * order -- exactly the sequence of the per-node entry points above: r3n_frame_begin, r3n_shadow_viewport, r3n_skinning, per shadow
  * view r3n_uniform_bake / r3n_cull / r3n_forward(DEPTH, RESIDUAL, OPAQUE | CUTOUT), the viewport's r3n_uniform_bake,
- * r3n_forward(FORWARD, PREDICTED, ..), r3n_hi_z, r3n_cull, r3n_forward(FORWARD, RESIDUAL, ..), r3n_resolve_opaque, the transparent
- * r3n_forward, r3n_tonemap, r3n_frame_end.  The per-node entry points stay (a Rust integration calls them from its node closures);
+ * r3n_forward(FORWARD, PREDICTED, ..), r3n_hi_z, r3n_cull, r3n_forward(FORWARD, RESIDUAL, ..), r3n_resolve_opaque, r3n_skybox, the
+ * transparent r3n_forward, r3n_tonemap, r3n_frame_end.  The per-node entry points stay (a Rust integration calls them from its node closures);
  * this one is for hosts that do not need a graph between the nodes: one FFI crossing per frame instead of ~45.
  * `desc` carries what Renderer::evaluate_instructions + the node closures compute on the CPU in the reference: the FrameUniforms
  * (uniforms.rs:28-48), the viewport's PerCameraUniform header (culler.rs:485-502), one header + atlas viewport per shadow map
@@ -543,7 +560,8 @@ int r3n_readback_output(r3n_ctx *ctx, uint8_t *rgba8, float *rgba_f32); /* eithe
 #define R3N_STAGE_EXCHANGE_KEYS 17   /* object-range split: MAX reduce-scatter of the visibility keys onto the row bands (main stream) */
 #define R3N_STAGE_RASTER_CUT 18      /* viewport, CUTOUT key: per-triangle pass (alpha test per fragment; the opaque key's launches stay under RASTER) */
 #define R3N_STAGE_RASTER_BIG_CUT 19  /* viewport, CUTOUT key: work-item pass */
-#define R3N_STAGE_COUNT 20
+#define R3N_STAGE_SKYBOX 20          /* the skybox node (r3n_skybox) */
+#define R3N_STAGE_COUNT 21
 int r3n_timing_enable(r3n_ctx *ctx, int enable);
 /* What a timed span holds besides its kernels -- two event packets and a launch's dispatch, measured around an empty kernel when
  * timing is first enabled (median of 32) -- and already taken off every span r3n_stage_times reports. */

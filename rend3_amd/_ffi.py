@@ -19,7 +19,7 @@ SOURCE_PREDICTED, SOURCE_RESIDUAL = 0, 1
 KEY_OPAQUE, KEY_CUTOUT, KEY_BLEND = 0, 1, 2
 STAGES = ["bake", "object_cull", "triangle_cull", "hiz", "raster", "shade", "tonemap", "clear", "raster_big",
           "shadow_raster", "shadow_raster_big", "skinning", "vertex", "pose", "exchange_shadow", "exchange_depth", "exchange_rows", "exchange_keys",
-          "raster_cut", "raster_big_cut"]
+          "raster_cut", "raster_big_cut", "skybox"]
 
 COMM_ID_BYTES, COMM_IDS = 128, 3  # R3N_COMM_ID_BYTES, R3N_COMM_IDS
 
@@ -36,6 +36,8 @@ SIGNATURES = {
     "r3n_materials_write": (cint, [vp, vp, vp, vp, u32]),
     "r3n_textures_write": (cint, [vp, vp, u32, vp, u64]),
     "r3n_textures_write_encoded": (cint, [vp, vp, u32, vp, u64]),
+    "r3n_texture_cubes_write": (cint, [vp, vp, u32, vp, u64]),
+    "r3n_skybox_set": (cint, [vp, u32]),
     "r3n_animation_write": (cint, [vp, vp, u32, vp, u32, vp, u32, vp, u32, vp, u32, vp, u32]),
     "r3n_pose_skeletons": (cint, [vp, vp, u32]),
     "r3n_set_output_format": (cint, [vp, u32]),
@@ -51,6 +53,7 @@ SIGNATURES = {
     "r3n_shadow_viewport": (cint, [vp, u32, u32, u32, u32]),
     "r3n_forward": (cint, [vp, u32, u32, u32, u32]),
     "r3n_resolve_opaque": (cint, [vp]),
+    "r3n_skybox": (cint, [vp]),
     "r3n_tonemap": (cint, [vp, vp, u64]),
     "r3n_hdr_write": (cint, [vp, vp, u64, u64]),
     "r3n_frame_end": (cint, [vp]),

@@ -880,10 +880,14 @@ static __global__ __launch_bounds__(256) void k_stage_view_lights(ShadeArgs a, V
 // CLS / VARIANT (S == 1 with records): the material class this instantiation is compiled for and its place in the chain
 // (R3N_CLS_*).  With more than one variant in flight (a.variants) a workgroup first ORs its pixels' features and leaves
 // unless the tile is its own: the smallest launched variant that covers the tile.
-template <int S, bool TEX, bool REC = false, bool SPLIT = false, bool FAST = false, uint32_t CLS = R3N_CLS_ALL, uint32_t VARIANT = 3u>
+// PARK (SPLIT only; the skybox node, skybox.hip): a pixel that did not fit the edge queue and shades all its triangles here ALSO
+// parks its samples, so that every pixel with more than one triangle has its samples in a.samples_out whatever the queue held.
+// Its own instantiation: frames without a skybox run the kernels they always ran.
+template <int S, bool TEX, bool REC = false, bool SPLIT = false, bool FAST = false, uint32_t CLS = R3N_CLS_ALL, uint32_t VARIANT = 3u, bool PARK = false>
 __global__ __launch_bounds__(256, (S == 1 && !TEX) ? 5 : (REC ? (S == 1 ? (CLS == R3N_CLS_PBR3 ? R3N_BATCH_OCC : R3N_TEX_OCC) : R3N_MS_OCC) : 1)) void k_resolve_opaque(ShadeArgs a) {
     typedef typename std::conditional<FAST, MathFast, MathExact>::type M;
     static_assert(CLS == R3N_CLS_ALL || (S == 1 && REC), "material classes exist for the single-sample record-based resolve");
+    static_assert(!PARK || SPLIT, "PARK extends the split resolve");
     __shared__ LdsDirLight s_dir[R3N_MAX_DIR_LIGHTS];
     __shared__ LdsPointLight s_point[R3N_MAX_POINT_LIGHTS];
     __shared__ float s_decode[512];
@@ -1063,7 +1067,7 @@ __global__ __launch_bounds__(256, (S == 1 && !TEX) ? 5 : (REC ? (S == 1 ? (CLS =
                     for (int c = 0; c < 4; ++c) col[sm][c] = (float)(_Float16)v[c];
                 }
         }
-        if (!SPLIT && a.samples_out != nullptr) {
+        if ((!SPLIT || PARK) && a.samples_out != nullptr) {
 #pragma unroll
             for (int sm = 0; sm < S; ++sm) a.samples_out[pix * (size_t)S + (size_t)sm] = pack_half4(col[sm]);
         }
@@ -1265,6 +1269,7 @@ int r3n_internal_build_srgb_lut(unsigned char *lut, hipStream_t stream);
 // k_mark_visible over keys [first_key, first_key + n_keys) + k_vertex_stage over a.total_tris slots
 int r3n_internal_shade_prepass(const ShadeArgs *a, int tex, size_t first_key, size_t n_keys, hipStream_t stream);
 // the resolve of rows [a.row_begin, a.row_end): samples 1 | 4; rec = a.tri_rec holds this frame's records; split = three-pass MSAA resolve
+// (split == 2: its PARK form, for frames with a skybox)
 // fast: R3N_SHADE_FAST (honoured by the single-sample record-based resolve; the other variants always run the exact arithmetic)
 // single-sample record-based resolve: one launch per variant in a->variants (0: the general kernel alone)
 int r3n_internal_resolve(const ShadeArgs *a, uint32_t samples, int tex, int rec, int split, int fast, hipStream_t stream);

@@ -19,6 +19,7 @@
 #include "kernels_raster.h"
 #define R3N_SHADE_DECL_ONLY
 #include "kernels_shade.h"
+#include "skybox.h"
 
 namespace {
 
@@ -198,6 +199,14 @@ struct r3n_ctx {
     DevBuf tex_descs, tex_texels, tex_level_off, srgb8_decode;  // bindless texture array (row N2): descriptors, RGBA8 texel pool, decode tables  // bindless texture array (row N2) + sRGB8 -> linear table
     uint32_t n_textures = 0;
     uint64_t n_texels = 0;
+    // cube textures + the skybox node (skybox.h): the bordered faces of every cube, where each cube starts, which one is bound
+    struct Cube { size_t first_word; uint32_t n, srgb; };
+    DevBuf cube_texels;
+    std::vector<Cube> cubes;
+    uint32_t sky_cube = 0;            // r3n_skybox_set: 0 = none, i + 1 = cubes[i]
+    bool sky_window = false;          // between r3n_resolve_opaque and the transparent pass / tonemap: where r3n_skybox is legal
+    bool resolve_on_shade = false;    // the stream this frame's resolve went to (the sky follows it there)
+    uint32_t sky_samples_form = R3N_SKY_SAMPLES_ALL;  // four samples: where this frame's resolve left the per-sample colours
     // rend3-anim tables (row N4) and the pose requests queued for the next r3n_skinning
     DevBuf edge_list, edge_count;  // split MSAA resolve (kernels_raster.h k_resolve_edges)
     uint32_t edge_capacity_override = 0;
@@ -381,7 +390,7 @@ int check_async_status(r3n_ctx *c) {
 
 static const char *const kStageNames[R3N_STAGE_COUNT] = {"bake", "object_cull", "triangle_cull", "hiz", "raster", "shade", "tonemap", "clear",
     "raster_big", "shadow_raster", "shadow_raster_big", "skinning", "vertex", "pose", "exchange_shadow", "exchange_depth",
-    "exchange_rows", "exchange_keys", "raster_cut", "raster_big_cut"};
+    "exchange_rows", "exchange_keys", "raster_cut", "raster_big_cut", "skybox"};
 static void crumb(const r3n_ctx *c, const char *what, long long a, long long b) {
     if (c->crumb_fd < 0) return;
     char line[160];
@@ -932,7 +941,7 @@ void r3n_destroy(r3n_ctx *c) {
                       &c->tri_rec, &c->tri_seen, &c->blend_order, &c->blend_rank_base, &c->frag_keys, &c->frag_vals, &c->frag_head,
                       &c->frag_count, &c->samples16, &c->anim_rigs, &c->anim_joints, &c->anim_clips, &c->anim_tracks,
                       &c->anim_times, &c->anim_values, &c->pose_requests, &c->edge_list, &c->edge_count, &c->material_feat, &c->view_lights[0],
-                      &c->view_lights[1]};
+                      &c->view_lights[1], &c->cube_texels};
     for (DevBuf *b : bufs)
         if (b->p) (void)hipFree(b->p);
     free_cam(c->canon);
@@ -1361,6 +1370,7 @@ static int frame_begin_impl(r3n_ctx *c, const r3n_frame_uniforms496 *u, uint32_t
     for (auto &f : c->forward_index_lane) f = 0;
     c->resolved_this_frame = false;
     c->blended_this_frame = false;
+    c->sky_window = false;
     c->hiz_plane_ready = false;
     c->viewport.culled = false;
     for (auto &kv : c->shadows) kv.second.culled = false;
@@ -1739,6 +1749,7 @@ int r3n_forward(r3n_ctx *c, r3n_camera cam, uint32_t pass, uint32_t source, uint
     if (!c || pass > R3N_PASS_FORWARD || source > R3N_SOURCE_RESIDUAL || key > R3N_KEY_BLEND)
         return fail(c, R3N_ERR_INVALID_ARG, "forward: bad args");
     if (!c->in_frame) return fail(c, R3N_ERR_STATE, "forward: outside a frame");
+    if (key == R3N_KEY_BLEND) c->sky_window = false;  // the transparent pass: the skybox node comes before it (base.rs:175,181)
     CamState *s = find_cam(c, cam, false);
     if (!s || !s->has_hdr || c->capacity == 0) return R3N_OK;  // nothing baked / culled yet: forward.rs:214-242
     key_census(c);
@@ -1914,6 +1925,8 @@ int r3n_resolve_opaque(r3n_ctx *c) {
     if (!c || !c->in_frame) return fail(c, R3N_ERR_STATE, "resolve_opaque: outside a frame");
     HIP_TRY(c, hipSetDevice(c->device));
     const uint32_t r0 = std::min(c->row_begin, c->height), r1 = std::min(c->row_end, c->height);
+    c->sky_window = r1 <= r0;  // an empty row range: nothing to resolve, and nothing for r3n_skybox to do either; else opened below
+    c->resolve_on_shade = false;
     if (r1 <= r0) return R3N_OK;
     CamState &s = c->viewport;
     if (!s.has_hdr && c->capacity) return fail(c, R3N_ERR_STATE, "resolve_opaque: viewport uniforms not baked");
@@ -1933,7 +1946,13 @@ int r3n_resolve_opaque(r3n_ctx *c) {
         TRY(ensure(c, c->tri_rec, (size_t)c->total_tris * sizeof(TriRecord), false, -1));
         TRY(ensure(c, c->tri_seen, (size_t)c->total_tris, false, 0));  // zero: k_vertex_stage returns every flag it consumes to 0
     }
-    if (blend_samples || split) TRY(ensure(c, c->samples16, (size_t)npix_all * 4 * 8, false, -1));
+    // A skybox follows (r3n_skybox): it redoes the box resolve of the pixels it shares with geometry, so their samples must exist.
+    // The split form parks them for every pixel with more than one triangle (its PARK instantiation: also where the edge queue
+    // had no room); the forms that keep no samples at all -- no triangle records: an empty or an oversized world -- write them
+    // out like a frame with a transparent pass does.  The kernels of a frame without a skybox are untouched.
+    const bool sky = c->sky_cube != 0u;
+    const bool sky_samples = sky && c->samples == 4 && !split && !blend_samples;
+    if (blend_samples || split || sky_samples) TRY(ensure(c, c->samples16, (size_t)npix_all * 4 * 8, false, -1));
     if (split) {
         edge_cap = (uint32_t)((uint64_t)(r1 - r0) * c->width * 3u / R3N_EDGEQ) + 4096u;
         if (c->edge_capacity_override) edge_cap = c->edge_capacity_override;  // R3N_EDGE_CAPACITY: exercises the overflow path in tests
@@ -1960,7 +1979,7 @@ int r3n_resolve_opaque(r3n_ctx *c) {
         TRY(join_shade(c));  // an earlier frame's resolve may still be writing the HDR / output targets
     }
     ShadeArgs a = make_shade_args(c, r0, r1);
-    if (blend_samples) a.samples_out = c->samples16.as<ushort4>();
+    if (blend_samples || sky_samples) a.samples_out = c->samples16.as<ushort4>();
     if (use_records && c->samples == 1) a.view_lights = c->view_lights[c->slot].as<ViewLights>();
     if (classes && c->resolve_variants != 0u) {
         a.material_feat = c->material_feat.as<uint32_t>();
@@ -1987,7 +2006,7 @@ int r3n_resolve_opaque(r3n_ctx *c) {
             a.edge_capacity = edge_cap;
             HIP_TRY(c, hipMemsetAsync(a.edge_count, 0, R3N_EDGEQ * 4, stream));
         }
-        HIP_TRY(c, (hipError_t)r3n_internal_resolve(&a, c->samples, tex ? 1 : 0, a.tri_rec != nullptr ? 1 : 0, split ? 1 : 0,
+        HIP_TRY(c, (hipError_t)r3n_internal_resolve(&a, c->samples, tex ? 1 : 0, a.tri_rec != nullptr ? 1 : 0, split ? (sky ? 2 : 1) : 0,
                                                     c->shade_mode == R3N_SHADE_FAST ? 1 : 0, stream));
     }
     TRY(check_launch(c, "k_resolve_opaque"));
@@ -1997,6 +2016,122 @@ int r3n_resolve_opaque(r3n_ctx *c) {
         c->shade_unjoined = true;
         c->shade_last = c->slot;
     }
+    c->sky_window = true;
+    c->resolve_on_shade = on_shade;
+    c->sky_samples_form = split ? R3N_SKY_SAMPLES_EDGES : R3N_SKY_SAMPLES_ALL;
+    return R3N_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ cube textures + skybox node
+namespace {
+// The direction through the point (sc, tc) of face `f`'s plane (|sc|, |tc| may pass 1: a point beyond the face's edge), and back:
+// the face and texel a direction selects.  The Vulkan / WebGPU cube table of skybox.hip, in double: used once per border texel
+// at upload, where the adjacent face's texel across an edge is found by re-projecting the texel centre extended on the face's plane.
+void cube_face_point(uint32_t f, double sc, double tc, double d[3]) {
+    switch (f) {
+        case 0: d[0] = 1.0; d[1] = -tc; d[2] = -sc; break;   // +X: (sc, tc) = (-z, -y)
+        case 1: d[0] = -1.0; d[1] = -tc; d[2] = sc; break;   // -X: (z, -y)
+        case 2: d[0] = sc; d[1] = 1.0; d[2] = tc; break;     // +Y: (x, z)
+        case 3: d[0] = sc; d[1] = -1.0; d[2] = -tc; break;   // -Y: (x, -z)
+        case 4: d[0] = sc; d[1] = -tc; d[2] = 1.0; break;    // +Z: (x, -y)
+        default: d[0] = -sc; d[1] = -tc; d[2] = -1.0; break; // -Z: (-x, -y)
+    }
+}
+void cube_nearest_texel(const double d[3], uint32_t n, uint32_t &f, uint32_t &i, uint32_t &j) {
+    const double ax = std::fabs(d[0]), ay = std::fabs(d[1]), az = std::fabs(d[2]);
+    double sc, tc, ma;
+    if (az >= ax && az >= ay) { f = d[2] < 0.0 ? 5u : 4u; sc = d[2] < 0.0 ? -d[0] : d[0]; tc = -d[1]; ma = az; }
+    else if (ay >= ax) { f = d[1] < 0.0 ? 3u : 2u; sc = d[0]; tc = d[1] < 0.0 ? -d[2] : d[2]; ma = ay; }
+    else { f = d[0] < 0.0 ? 1u : 0u; sc = d[0] < 0.0 ? d[2] : -d[2]; tc = -d[1]; ma = ax; }
+    const double s = 0.5 * (sc / ma) + 0.5, t = 0.5 * (tc / ma) + 0.5;
+    i = (uint32_t)std::min<double>(std::max(std::floor(s * n), 0.0), (double)n - 1.0);
+    j = (uint32_t)std::min<double>(std::max(std::floor(t * n), 0.0), (double)n - 1.0);
+}
+}  // namespace
+
+int r3n_texture_cubes_write(r3n_ctx *c, const r3n_texture_desc32 *descs, uint32_t n, const uint32_t *texels, uint64_t n_texels) {
+    if (!c || (n && (!descs || !texels))) return fail(c, R3N_ERR_INVALID_ARG, "texture cubes write: null");
+    if (c->in_frame) return fail(c, R3N_ERR_STATE, "texture cubes write: inside a frame");
+    size_t words = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        const r3n_texture_desc32 &d = descs[i];
+        if (d.width != d.height) return fail(c, R3N_ERR_INVALID_ARG, "texture cubes write: a cube's faces are square");
+        if (!d.width || d.width > 16384u) return fail(c, R3N_ERR_INVALID_ARG, "texture cubes write: bad extent");
+        if (d.format > R3N_TEXTURE_RGBA8_UNORM_SRGB) return fail(c, R3N_ERR_UNSUPPORTED, "texture cubes write: Rgba8Unorm / Rgba8UnormSrgb cubes only");
+        if (d.mips != 1u) return fail(c, R3N_ERR_UNSUPPORTED, "texture cubes write: single-level cubes only (no level selection from cube-direction derivatives)");
+        if ((uint64_t)d.offset + 6ull * d.width * d.width > n_texels) return fail(c, R3N_ERR_INVALID_ARG, "texture cubes write: faces outside the texel array");
+        words += 6u * (size_t)(d.width + 2u) * (d.width + 2u);
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    TRY(sync_all(c));  // no frame may still sample the old array
+    std::vector<uint32_t> pool(std::max<size_t>(words, 1), 0u);
+    std::vector<r3n_ctx::Cube> cubes(n);
+    size_t at = 0;
+    for (uint32_t ci = 0; ci < n; ++ci) {
+        const uint32_t N = descs[ci].width, P = N + 2u;
+        const uint32_t *src = texels + descs[ci].offset;
+        cubes[ci] = {at, N, descs[ci].format == R3N_TEXTURE_RGBA8_UNORM_SRGB ? 1u : 0u};
+        for (uint32_t f = 0; f < 6u; ++f) {
+            uint32_t *dst = pool.data() + at + (size_t)f * P * P;
+            for (uint32_t j = 0; j < N; ++j) std::memcpy(dst + (size_t)(j + 1u) * P + 1u, src + ((size_t)f * N + j) * N, (size_t)N * 4);
+            // the border: texel centre (i + 0.5, j + 0.5) one step outside the face, extended on the face's plane
+            auto border = [&](int i, int j) {
+                double d[3];
+                cube_face_point(f, (2.0 * (i + 0.5)) / N - 1.0, (2.0 * (j + 0.5)) / N - 1.0, d);
+                uint32_t nf, ni, nj;
+                cube_nearest_texel(d, N, nf, ni, nj);
+                dst[(size_t)(j + 1) * P + (size_t)(i + 1)] = src[((size_t)nf * N + nj) * N + ni];
+            };
+            for (int k = 0; k < (int)N; ++k) { border(-1, k); border((int)N, k); border(k, -1); border(k, (int)N); }
+        }
+        at += 6u * (size_t)P * P;
+    }
+    TRY(ensure(c, c->cube_texels, pool.size() * 4, false, -1));
+    HIP_TRY(c, hipMemcpyAsync(c->cube_texels.p, pool.data(), pool.size() * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_WAIT(c, hipStreamSynchronize(c->stream));  // `pool` is a temporary
+    c->cubes = std::move(cubes);
+    if (c->sky_cube > n) c->sky_cube = 0;
+    return R3N_OK;
+}
+
+int r3n_skybox_set(r3n_ctx *c, uint32_t cube_id) {
+    if (!c) return R3N_ERR_INVALID_ARG;
+    if (c->in_frame) return fail(c, R3N_ERR_STATE, "skybox_set: inside a frame");
+    if (cube_id > c->cubes.size()) return fail(c, R3N_ERR_INVALID_ARG, "skybox_set: no such cube");
+    c->sky_cube = cube_id;
+    return R3N_OK;
+}
+
+int r3n_skybox(r3n_ctx *c) {
+    if (!c || !c->in_frame || !c->sky_window) return fail(c, R3N_ERR_STATE, "skybox: the node follows r3n_resolve_opaque and precedes the transparent pass and r3n_tonemap");
+    if (c->sky_cube == 0u) return R3N_OK;  // `if let Some(bg)`: nothing bound, nothing drawn
+    const uint32_t r0 = std::min(c->row_begin, c->height), r1 = std::min(c->row_end, c->height);
+    if (r1 <= r0) return R3N_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const r3n_ctx::Cube &cube = c->cubes[c->sky_cube - 1u];
+    SkyboxArgs a{};
+    a.vis = c->vis.as<unsigned long long>();
+    a.fu = c->fu.as<r3n_frame_uniforms496>();
+    a.texels = c->cube_texels.as<uint32_t>() + cube.first_word;
+    a.decode = c->srgb8_decode.as<float>();
+    a.n = cube.n; a.srgb = cube.srgb;
+    a.width = c->width; a.height = c->height; a.row_begin = r0; a.row_end = r1;
+    a.hdr_out = c->hdr16.as<ushort4>();
+    a.ldr_out = c->out8.as<uchar4>();
+    a.srgb_lut = c->srgb_lut.as<unsigned char>();
+    a.out_bgr = (c->output_format & 1u) != 0u ? 1u : 0u;
+    a.samples = c->samples == 4 ? c->samples16.as<ushort4>() : nullptr;
+    a.samples_form = c->sky_samples_form;
+    if (c->samples == 4 && !a.samples) return fail(c, R3N_ERR_STATE, "skybox: the resolve kept no samples");
+    // the stream the resolve went to: its own while frames are in flight and no transparent pass follows, else the main stream
+    hipStream_t stream = c->resolve_on_shade ? c->shade : c->stream;
+    {
+        Timed t(c, R3N_STAGE_SKYBOX, stream);
+        HIP_TRY(c, (hipError_t)r3n_internal_skybox(&a, c->samples, stream));
+    }
+    TRY(check_launch(c, "k_skybox"));
+    // whatever waits for the resolve -- the frame that reuses these targets, the read-backs -- waits for the sky as well
+    if (c->resolve_on_shade) HIP_TRY(c, hipEventRecord(c->shade_done[c->slot], c->shade));
     return R3N_OK;
 }
 
@@ -2175,6 +2310,7 @@ int r3n_set_shade_mode(r3n_ctx *c, uint32_t mode) {
 
 int r3n_tonemap(r3n_ctx *c, void *host_rgba8, uint64_t pitch) {
     if (!c || !c->in_frame) return fail(c, R3N_ERR_STATE, "tonemap: outside a frame");
+    c->sky_window = false;
     HIP_TRY(c, hipSetDevice(c->device));
     // the blit is fused into r3n_resolve_opaque (same arithmetic on the Rgba16Float-rounded value); the separate
     // kernel only runs when the HDR buffer was produced some other way
@@ -2537,6 +2673,7 @@ int r3n_render_frame(r3n_ctx *c, const r3n_frame_desc *d) {
     if (d->exchange && d->exchange(d->exchange_user, R3N_EXCHANGE_PASS2) != 0) return fail(c, R3N_ERR_STATE, "render_frame: the pass-2 exchange callback failed");
     if (native && c->comm.by_objects) TRY(comm_reduce_pass2(c));
     TRY(r3n_resolve_opaque(c));               // the opaque passes' fragment stages, deferred
+    TRY(r3n_skybox(c));                       // skybox (base.rs:175)
     // pbr_forward_rendering_transparent (base.rs:181)
     TRY(r3n_forward(c, R3N_CAMERA_VIEWPORT, R3N_PASS_FORWARD, R3N_SOURCE_RESIDUAL, R3N_KEY_BLEND));
     TRY(r3n_tonemap(c, nullptr, 0));          // tonemapping (base.rs:184)

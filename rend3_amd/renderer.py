@@ -194,6 +194,10 @@ class Renderer:
         self.tex_pool = np.zeros(4, dtype=np.uint8)   # every texture's levels in ITS format (bytes)
         self.tex_used = 0
         self._tex_dirty = False
+        self.cubes = []            # (faces uint8[6, N, N, 4], srgb) per add_texture_cube handle
+        self._cubes_dirty = False
+        self._background = None    # SkyboxRoutine.set_background_texture: the cube handle bound as the skybox, or None
+        self._background_sent = None
         self._pose_state = {}      # skeleton handle -> (clip, time): rend3-anim poses re-evaluated in front of every skinning pass
         self._anim_sets = None     # concatenated rend3-anim tables of every AnimationData (animation_add)
         self.output_format = 0
@@ -424,6 +428,46 @@ class Renderer:
                                                             _ffi.ptr(self.tex_pool), self.tex_used), "r3n_textures_write_encoded")
             self._tex_dirty = False
 
+    def add_texture_cube(self, faces, srgb=True):
+        """Renderer::add_texture_cube with Texture{format: Rgba8UnormSrgb | Rgba8Unorm, mip_count: ONE}: faces = uint8[6, N, N, 4]
+        in layer order +X, -X, +Y, -Y, +Z, -Z (scene_viewer's right, left, top, bottom, front, back).  The cube array is re-sent
+        when the next frame is evaluated (r3n_texture_cubes_write).  Returns the cube handle (index)."""
+        faces = np.ascontiguousarray(faces, dtype=np.uint8)
+        if faces.ndim != 4 or faces.shape[0] != 6 or faces.shape[3] != 4:
+            raise ValueError("a cube texture is uint8[6, N, N, 4]")
+        self.cubes.append((faces, bool(srgb)))
+        self._cubes_dirty = True
+        return len(self.cubes) - 1
+
+    def replace_texture_cubes(self, cubes):
+        """Replaces the whole cube array: `cubes` = [(faces, srgb), ...]; handles are indices into it."""
+        self.cubes = []
+        for faces, srgb in cubes:
+            self.add_texture_cube(faces, srgb)
+        self._cubes_dirty = True
+        if self._background is not None and self._background >= len(self.cubes):
+            self._background = None  # (as the library does: a skybox whose cube left the array is unbound)
+
+    def set_background_texture(self, cube):
+        """SkyboxRoutine::set_background_texture(Option<TextureCubeHandle>) (rend3-routine/src/skybox.rs): None = no skybox."""
+        self._background = cube
+
+    def _flush_cubes(self):
+        if self._cubes_dirty:
+            descs = np.zeros((max(len(self.cubes), 1), 8), dtype=np.uint32)
+            at = 0
+            for i, (faces, srgb) in enumerate(self.cubes):
+                descs[i, :5] = (at, faces.shape[2], faces.shape[1], 1, 1 if srgb else 0)
+                at += faces.size // 4
+            texels = (np.concatenate([f.reshape(-1) for f, _ in self.cubes]) if self.cubes else np.zeros(4, dtype=np.uint8)).view(np.uint32)
+            self._check(self.lib.r3n_texture_cubes_write(self.ctx, _ffi.ptr(descs), len(self.cubes), _ffi.ptr(np.ascontiguousarray(texels)), at),
+                        "r3n_texture_cubes_write")
+            self._cubes_dirty = False
+            self._background_sent = None  # (the library unbinds a skybox whose cube left the array)
+        if self._background_sent is None or self._background_sent[0] != self._background:
+            self._check(self.lib.r3n_skybox_set(self.ctx, 0 if self._background is None else int(self._background) + 1), "r3n_skybox_set")
+            self._background_sent = (self._background,)
+
     def add_material(self, record, key=OPAQUE):
         idx = len(self.materials)
         self.materials.append((np.asarray(record, dtype=f32), key))
@@ -636,6 +680,7 @@ class Renderer:
     # ------------------------------------------------------------------ per-frame evaluation
     def evaluate_instructions(self):
         self._flush_textures()
+        self._flush_cubes()
         return self._evaluate_instructions()
 
     def _flush_objects(self):
@@ -730,6 +775,7 @@ class Renderer:
             d.shadow_views = base + _ffi.HostFrame.shadow_views.offset
             d.directional_buffer = base + _ffi.HostFrame.directional_buffer.offset
         self._flush_textures()
+        self._flush_cubes()
         self._flush_objects()
         cam, fr, d = fc["cam"], fc["frame"], fc["desc"]
         view, projection = self._camera_inputs
@@ -1034,6 +1080,23 @@ class TonemappingRoutine:
         graph.add_node("Tonemapping", body)
 
 
+class SkyboxRoutine:
+    """rend3-routine/src/skybox.rs: holds the background cube; its node draws it where nothing nearer was drawn."""
+
+    def __init__(self, renderer):
+        self.renderer = renderer
+
+    def set_background_texture(self, cube):
+        self.renderer.set_background_texture(cube)
+
+    def evaluate(self, renderer=None):
+        """SkyboxRoutine::evaluate: makes the bound cube current (the reference rebuilds its bind group here)."""
+        (renderer or self.renderer)._flush_cubes()
+
+    def add_to_graph(self, graph):
+        graph.add_node("Skybox", lambda r, _ev: r._check(r.lib.r3n_skybox(r.ctx), "r3n_skybox"))
+
+
 class BaseRenderGraphRoutines:
     def __init__(self, pbr, tonemapping, skybox=None):
         self.pbr, self.tonemapping, self.skybox = pbr, tonemapping, skybox
@@ -1050,7 +1113,7 @@ class BaseRenderGraph:
         self.viewport_first = False
 
     def default_routines(self):
-        return BaseRenderGraphRoutines(PbrRoutine(), TonemappingRoutine())
+        return BaseRenderGraphRoutines(PbrRoutine(), TonemappingRoutine(), SkyboxRoutine(self.renderer))
 
     def add_to_graph(self, graph, inputs, settings, exchange=None):
         """Node order == base.rs:135-185.  `exchange` (multi-GPU only, not in the reference) is called with
@@ -1135,7 +1198,10 @@ class BaseRenderGraph:
             graph.add_node("exchange pass-2 keys", lambda r, _ev: exchange("pass2", r, ev=ev, samples=inputs.samples))
         # the deferred evaluation of the opaque passes' fragments (this design's stand-in for their fragment shaders)
         graph.add_node("Resolve Opaque", lambda r, _ev: r._check(r.lib.r3n_resolve_opaque(r.ctx), "r3n_resolve_opaque"))
-        # skybox (base.rs:175): out of scope.  pbr_forward_rendering_transparent (base.rs:181)
+        # skybox (base.rs:175): `if let Some(skybox)`; with no background bound the node enqueues nothing
+        if inputs.routines.skybox is not None:
+            inputs.routines.skybox.add_to_graph(graph)
+        # pbr_forward_rendering_transparent (base.rs:181)
         pbr.blend_routine.add_forward_to_graph(graph, "PBR Forward Transparent", VP, _ffi.SOURCE_RESIDUAL)
         # tonemapping (base.rs:184)
         inputs.routines.tonemapping.add_to_graph(graph)

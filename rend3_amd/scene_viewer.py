@@ -9,6 +9,8 @@ Square: `examples/src/scene_viewer`).  Follows (reference file:line):
                                            :678-681 (ambient = (a, a, a, 1), clear (0, 0, 0, 1))
   App::HANDEDNESS = Right                 :434
   the Bistro test                          :727-751 (flags + camera of BASELINE.json configs[2])
+  load_skybox                              :34-57 (six files right | left | top | bottom | front | back -> add_texture_cube,
+                                           Rgba8UnormSrgb, one level), :675 (`skybox: Some(..)` in the frame's routines)
 
 `build(renderer, host_module, material_record, settings)` works on anything with the Renderer's world-edit API -- the HIP
 renderer and, in the tests / bench.py's cpu_baseline leg, the oracle -- so a real asset runs through exactly the parity and
@@ -67,6 +69,8 @@ def add_arguments(ap):
     ap.add_argument("--gltf-disable-directional-lights", action="store_true", help="ignore KHR_lights_punctual lights of the file")
     ap.add_argument("--camera", type=_camera, default=None, metavar="X,Y,Z,PITCH,YAW",
                     help="camera location and angles (default: the default scene's, mod.rs:320-322)")
+    ap.add_argument("--skybox", default=None, metavar="DIR",
+                    help="directory holding right|left|top|bottom|front|back .jpg or .png: the background cube (default: none)")
     return ap
 
 
@@ -83,7 +87,7 @@ def settings_from(args):
                 directional_light=args.directional_light, directional_light_intensity=args.directional_light_intensity,
                 ambient=args.ambient, scale=args.scale, shadow_distance=args.shadow_distance,
                 shadow_resolution=args.shadow_resolution, enable_directional=not args.gltf_disable_directional_lights,
-                camera=args.camera or DEFAULT_CAMERA)
+                camera=args.camera or DEFAULT_CAMERA, skybox=getattr(args, "skybox", None))
 
 
 def default_settings(**over):
@@ -98,6 +102,24 @@ def camera_view(hm, camera):
     return hm.mat4_mul(hm.from_euler_xyz(-pitch, -yaw, np.float32(0.0)), hm.translation((-x, -y, -z)))
 
 
+SKYBOX_FACES = ("right", "left", "top", "bottom", "front", "back")  # cube layers +X, -X, +Y, -Y, +Z, -Z (mod.rs:38-45)
+
+
+def load_skybox(directory):
+    """The six face images of `directory` as uint8[6, N, N, 4] in layer order; every face square and of one size."""
+    from PIL import Image
+    faces = []
+    for name in SKYBOX_FACES:
+        path = next((os.path.join(directory, name + ext) for ext in (".jpg", ".png") if os.path.exists(os.path.join(directory, name + ext))), None)
+        if path is None:
+            raise FileNotFoundError(f"skybox: no {name}.jpg or {name}.png in {directory}")
+        faces.append(np.ascontiguousarray(np.array(Image.open(path).convert("RGBA"), dtype=np.uint8)))
+    n = faces[0].shape[0]
+    if any(f.shape != (n, n, 4) for f in faces):
+        raise ValueError("skybox: the six faces must be square and of one size")
+    return np.stack(faces)
+
+
 PROJECTION = ("perspective", 60.0, 0.1)  # mod.rs:645
 CLEAR = (0.0, 0.0, 0.0, 1.0)             # mod.rs:681
 
@@ -109,6 +131,8 @@ def build(r, hm, mk, settings):
     objects, triangles)."""
     from . import gltf
     assert r.handedness == RIGHT, "scene_viewer is right-handed (App::HANDEDNESS, mod.rs:434)"
+    if settings.get("skybox"):  # load_skybox (mod.rs:34-57); a renderer without cube textures fails here, it does not skip the sky
+        r.set_background_texture(r.add_texture_cube(load_skybox(settings["skybox"]), srgb=True))
     light = None
     if settings["directional_light"] is not None:  # setup (mod.rs:463-472)
         light = r.add_directional_light(color=(1.0, 1.0, 1.0), intensity=settings["directional_light_intensity"],
