@@ -94,7 +94,8 @@ pub const R3N_STAGE_EXCHANGE_KEYS: i32 = 17;
 pub const R3N_STAGE_RASTER_CUT: i32 = 18;
 pub const R3N_STAGE_RASTER_BIG_CUT: i32 = 19;
 pub const R3N_STAGE_SKYBOX: i32 = 20;
-pub const R3N_STAGE_COUNT: i32 = 21;
+pub const R3N_STAGE_BLEND_SORT: i32 = 21;
+pub const R3N_STAGE_COUNT: i32 = 22;
 
 #[repr(C)]
 pub struct r3n_ctx {
@@ -354,6 +355,8 @@ extern "C" {
     pub fn r3n_texture_cubes_write(ctx: *mut r3n_ctx, descs: *const r3n_texture_desc32, n_cubes: u32, texels: *const u32, n_texels: u64) -> c_int;
     pub fn r3n_skybox_set(ctx: *mut r3n_ctx, cube_id: u32) -> c_int;
     pub fn r3n_blend_order_write(ctx: *mut r3n_ctx, objects_back_to_front: *const u32, n: u32) -> c_int;
+    pub fn r3n_blend_objects_write(ctx: *mut r3n_ctx, slots: *const u32, locations: *const f32, n: u32) -> c_int;
+    pub fn r3n_blend_sort(ctx: *mut r3n_ctx, camera_location: *const f32) -> c_int;
     pub fn r3n_lights_write(ctx: *mut r3n_ctx, directional_buffer: *const c_void, directional_bytes: u64, point_buffer: *const c_void, point_bytes: u64) -> c_int;
     pub fn r3n_set_output_format(ctx: *mut r3n_ctx, format: u32) -> c_int;
     pub fn r3n_set_skinning_mode(ctx: *mut r3n_ctx, mode: u32) -> c_int;
@@ -392,6 +395,7 @@ extern "C" {
     pub fn r3n_readback_triangle_sets(ctx: *mut r3n_ctx, camera: u32, pass: *mut u8, residual: *mut u8, n: u64) -> c_int;
     pub fn r3n_readback_draw_calls(ctx: *mut r3n_ctx, camera: u32, calls: *mut r3n_indirect_call) -> c_int;
     pub fn r3n_readback_raster_stats(ctx: *mut r3n_ctx, big_items: *mut u32) -> c_int;
+    pub fn r3n_readback_blend_order(ctx: *mut r3n_ctx, order: *mut u32, rank_base: *mut u32, capacity: u32) -> c_int;
     pub fn r3n_readback_baked(ctx: *mut r3n_ctx, camera: u32, model_view_and_mvp: *mut f32, capacity: u32) -> c_int;
     pub fn r3n_readback_mesh(ctx: *mut r3n_ctx, byte_offset: u64, dst: *mut c_void, bytes: u64) -> c_int;
     pub fn r3n_readback_joint_matrices(ctx: *mut r3n_ctx, first_matrix: u32, dst: *mut f32, n_matrices: u32) -> c_int;

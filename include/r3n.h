@@ -293,6 +293,24 @@ int r3n_skybox_set(r3n_ctx *ctx, uint32_t cube_id);
  *      sorts them every frame (rend3-routine/src/culling/batching.rs:146-176, Sorting::BLENDING: -distance^2 from the
  *      camera location to the object location).  Call once per frame before r3n_resolve_opaque (n may be 0). */
 int r3n_blend_order_write(r3n_ctx *ctx, const uint32_t *objects_back_to_front, uint32_t n);
+/*      The same order, sorted ON THE DEVICE.  r3n_blend_objects_write uploads the BLEND SET -- the blend-key objects' slots and
+ *      their sorting locations -- when the world changes; r3n_blend_sort orders it for one camera location every frame.  The
+ *      location is host-side state in the reference, like Material::key(): the world bounding-sphere centre at add_object
+ *      (rend3/src/managers/object.rs:273), the transform's translation after set_object_transform (:313); it is not in the
+ *      128-byte record, so the caller supplies it (locations = 3 n floats).  `slots` strictly ascending and < the object
+ *      capacity, else R3N_ERR_INVALID_ARG; 2^29 or more triangles in the set -> R3N_ERR_UNSUPPORTED (the limit of
+ *      r3n_blend_order_write).  The triangle counts are those of the object records at the time of the call: send the set again
+ *      after an r3n_objects_write that touches one of its objects.  n == 0 clears the set.  Uploads through pinned staging without
+ *      waiting for the GPU and sizes the sort's scratch buffers.  Between frames only (R3N_ERR_STATE inside one).
+ *      THE LAST of r3n_blend_order_write and r3n_blend_objects_write decides where the transparent pass takes its order from. */
+int r3n_blend_objects_write(r3n_ctx *ctx, const uint32_t *slots, const float *locations, uint32_t n);
+/*      Sorting::BLENDING on the device: key = -dist, dist = (d.x * d.x + d.y * d.y) + d.z * d.z in f32 with d = camera_location -
+ *      location, ascending; equal keys by ascending slot (the reference's unstable sort leaves ties open).  +inf distances are
+ *      legal and tie with each other; NaN locations are outside the contract (the order is then unspecified, nothing else).
+ *      Call once per frame before r3n_resolve_opaque, where r3n_blend_order_write is called in host order mode.  Enqueues kernels
+ *      on the main stream and nothing else: no host wait, no read-back, no per-object host work.  Without a set (or in host order
+ *      mode) it does nothing and returns R3N_OK. */
+int r3n_blend_sort(r3n_ctx *ctx, const float camera_location[3]);
 /*      DirectionalLightManager / PointLightManager buffers, byte-identical:
  *      u32 count @0, array @16 (stride 128 / 32): rend3/src/managers/directional.rs:31-53,135-153, point.rs:14-74 */
 int r3n_lights_write(r3n_ctx *ctx, const void *directional_buffer, uint64_t directional_bytes,
@@ -363,7 +381,7 @@ int r3n_forward(r3n_ctx *ctx, r3n_camera camera, uint32_t pass, uint32_t source,
  * Must follow the last opaque / cutout FORWARD r3n_forward of the frame (base.rs:172) and precede r3n_tonemap.
  * The transparent pass -- r3n_forward(R3N_CAMERA_VIEWPORT, R3N_PASS_FORWARD, R3N_SOURCE_RESIDUAL, R3N_KEY_BLEND),
  * base.rs:181 -- comes after it: this frame's passing triangles of the blend-key objects, in the order given to
- * r3n_blend_order_write, depth-tested against the opaque depth (no depth write) and alpha-blended into the HDR target
+ * r3n_blend_order_write (or sorted by r3n_blend_sort), depth-tested against the opaque depth (no depth write) and alpha-blended into the HDR target
  * (pbr/routine.rs:113-118). */
 int r3n_resolve_opaque(r3n_ctx *ctx);
 /* SkyboxRoutine::add_to_graph (rend3-routine/src/skybox.rs, skybox.wgsl; base.rs:175): every sample whose depth the sky's 0.0
@@ -523,6 +541,10 @@ int r3n_readback_draw_calls(r3n_ctx *ctx, r3n_camera camera, r3n_indirect_call c
 /* work-queue occupancy of the rasteriser: big_items[i] = number of >8x8 px work items the i-th r3n_forward call of
  * the last frame produced (performance diagnostics only) */
 int r3n_readback_raster_stats(r3n_ctx *ctx, uint32_t big_items[64]);
+/* what the transparent pass reads, whichever of r3n_blend_order_write / r3n_blend_sort wrote it: order[n] = blend objects back to
+ * front, rank_base[n + 1] = exclusive scan of their triangle counts.  `capacity` = entries of `order` (and, plus one, of
+ * `rank_base`); smaller than the set -> R3N_ERR_INVALID_ARG */
+int r3n_readback_blend_order(r3n_ctx *ctx, uint32_t *order, uint32_t *rank_base, uint32_t capacity);
 /* The camera's baked matrices, 32 floats per slot.  After r3n_render_frame only the slots inside the frustum this frame or last
  * frame are defined (see r3n_uniform_bake); after the per-node r3n_uniform_bake every enabled slot is. */
 int r3n_readback_baked(r3n_ctx *ctx, r3n_camera camera, float *model_view_and_mvp, uint32_t capacity);
@@ -561,7 +583,8 @@ int r3n_readback_output(r3n_ctx *ctx, uint8_t *rgba8, float *rgba_f32); /* eithe
 #define R3N_STAGE_RASTER_CUT 18      /* viewport, CUTOUT key: per-triangle pass (alpha test per fragment; the opaque key's launches stay under RASTER) */
 #define R3N_STAGE_RASTER_BIG_CUT 19  /* viewport, CUTOUT key: work-item pass */
 #define R3N_STAGE_SKYBOX 20          /* the skybox node (r3n_skybox) */
-#define R3N_STAGE_COUNT 21
+#define R3N_STAGE_BLEND_SORT 21      /* r3n_blend_sort: the transparent pass's draw order sorted on the device */
+#define R3N_STAGE_COUNT 22
 int r3n_timing_enable(r3n_ctx *ctx, int enable);
 /* What a timed span holds besides its kernels -- two event packets and a launch's dispatch, measured around an empty kernel when
  * timing is first enabled (median of 32) -- and already taken off every span r3n_stage_times reports. */

@@ -19,7 +19,7 @@ SOURCE_PREDICTED, SOURCE_RESIDUAL = 0, 1
 KEY_OPAQUE, KEY_CUTOUT, KEY_BLEND = 0, 1, 2
 STAGES = ["bake", "object_cull", "triangle_cull", "hiz", "raster", "shade", "tonemap", "clear", "raster_big",
           "shadow_raster", "shadow_raster_big", "skinning", "vertex", "pose", "exchange_shadow", "exchange_depth", "exchange_rows", "exchange_keys",
-          "raster_cut", "raster_big_cut", "skybox"]
+          "raster_cut", "raster_big_cut", "skybox", "blend_sort"]
 
 COMM_ID_BYTES, COMM_IDS = 128, 3  # R3N_COMM_ID_BYTES, R3N_COMM_IDS
 
@@ -44,6 +44,8 @@ SIGNATURES = {
     "r3n_set_shade_mode": (cint, [vp, u32]),
     "r3n_set_skinning_mode": (cint, [vp, u32]),
     "r3n_blend_order_write": (cint, [vp, vp, u32]),
+    "r3n_blend_objects_write": (cint, [vp, vp, vp, u32]),
+    "r3n_blend_sort": (cint, [vp, vp]),
     "r3n_lights_write": (cint, [vp, vp, u64, vp, u64]),
     "r3n_frame_begin": (cint, [vp, vp, u32, u32, u32, vp, u32, u32]),
     "r3n_skinning": (cint, [vp, vp, u32, vp, u32]),
@@ -78,6 +80,7 @@ SIGNATURES = {
     "r3n_readback_triangle_sets": (cint, [vp, u32, vp, vp, u64]),
     "r3n_readback_draw_calls": (cint, [vp, u32, vp]),
     "r3n_readback_raster_stats": (cint, [vp, vp]),
+    "r3n_readback_blend_order": (cint, [vp, vp, vp, u32]),
     "r3n_readback_baked": (cint, [vp, u32, vp, u32]),
     "r3n_readback_mesh": (cint, [vp, u64, vp, u64]),
     "r3n_readback_texels": (cint, [vp, u64, vp, u64]),

@@ -20,6 +20,7 @@
 #define R3N_SHADE_DECL_ONLY
 #include "kernels_shade.h"
 #include "skybox.h"
+#include "blend_sort.h"
 
 namespace {
 
@@ -195,6 +196,10 @@ struct r3n_ctx {
     uint32_t *status_host = nullptr, *status_dev = nullptr;  // host-mapped word the kernels raise when a fixed-size buffer ran out
     std::vector<uint32_t> h_blend_order;
     uint32_t n_blend = 0, blend_tris = 0;
+    // sorted mode (blend_sort.h): the blend set of r3n_blend_objects_write and the scratch of r3n_blend_sort, sized at the upload.
+    // The last of r3n_blend_order_write / r3n_blend_objects_write decides where blend_order and blend_rank_base come from.
+    DevBuf blend_set_slots, blend_set_locations, blend_sort_scratch;
+    bool blend_sorted = false;
     uint32_t frag_capacity = 32u << 20;  // fragment nodes (12 B each), allocated on first use
     DevBuf tex_descs, tex_texels, tex_level_off, srgb8_decode;  // bindless texture array (row N2): descriptors, RGBA8 texel pool, decode tables  // bindless texture array (row N2) + sRGB8 -> linear table
     uint32_t n_textures = 0;
@@ -390,7 +395,7 @@ int check_async_status(r3n_ctx *c) {
 
 static const char *const kStageNames[R3N_STAGE_COUNT] = {"bake", "object_cull", "triangle_cull", "hiz", "raster", "shade", "tonemap", "clear",
     "raster_big", "shadow_raster", "shadow_raster_big", "skinning", "vertex", "pose", "exchange_shadow", "exchange_depth",
-    "exchange_rows", "exchange_keys", "raster_cut", "raster_big_cut", "skybox"};
+    "exchange_rows", "exchange_keys", "raster_cut", "raster_big_cut", "skybox", "blend_sort"};
 static void crumb(const r3n_ctx *c, const char *what, long long a, long long b) {
     if (c->crumb_fd < 0) return;
     char line[160];
@@ -941,7 +946,7 @@ void r3n_destroy(r3n_ctx *c) {
                       &c->tri_rec, &c->tri_seen, &c->blend_order, &c->blend_rank_base, &c->frag_keys, &c->frag_vals, &c->frag_head,
                       &c->frag_count, &c->samples16, &c->anim_rigs, &c->anim_joints, &c->anim_clips, &c->anim_tracks,
                       &c->anim_times, &c->anim_values, &c->pose_requests, &c->edge_list, &c->edge_count, &c->material_feat, &c->view_lights[0],
-                      &c->view_lights[1], &c->cube_texels};
+                      &c->view_lights[1], &c->cube_texels, &c->blend_set_slots, &c->blend_set_locations, &c->blend_sort_scratch};
     for (DevBuf *b : bufs)
         if (b->p) (void)hipFree(b->p);
     free_cam(c->canon);
@@ -2148,6 +2153,7 @@ int r3n_blend_order_write(r3n_ctx *c, const uint32_t *objects, uint32_t n) {
     }
     c->n_blend = n;
     c->blend_tris = rank[n];
+    c->blend_sorted = false;  // host order mode
     if (n == 0) return R3N_OK;
     HIP_TRY(c, hipSetDevice(c->device));
     TRY(ensure(c, c->blend_order, (size_t)n * 4, false, -1));
@@ -2156,6 +2162,58 @@ int r3n_blend_order_write(r3n_ctx *c, const uint32_t *objects, uint32_t n) {
     // (the buffers are read by the transparent pass on the main stream: in order with this copy)
     TRY(upload_bulk(c, c->blend_order.p, objects, (size_t)n * 4));  // through pinned staging: no wait for the GPU
     TRY(upload_bulk(c, c->blend_rank_base.p, rank.data(), (size_t)(n + 1) * 4));
+    return R3N_OK;
+}
+
+static_assert(R3N_META_NTRI_MASK == 0x3FFFFFFFu, "blend_sort.hip reads the triangle count out of ObjSoA::meta with this mask");
+
+int r3n_blend_objects_write(r3n_ctx *c, const uint32_t *slots, const float *locations, uint32_t n) {
+    if (!c || (n && (!slots || !locations))) return fail(c, R3N_ERR_INVALID_ARG, "blend objects: null");
+    if (c->in_frame) return fail(c, R3N_ERR_STATE, "blend objects: inside a frame");
+    uint32_t tris = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        if (slots[i] >= c->capacity) return fail(c, R3N_ERR_INVALID_ARG, "blend objects: object slot >= capacity");
+        if (i && slots[i] <= slots[i - 1]) return fail(c, R3N_ERR_INVALID_ARG, "blend objects: slots must be strictly ascending");
+        const uint32_t sum = tris + c->h_ntri[slots[i]];
+        // the same limit as r3n_blend_order_write's, for the same reason; the total does not depend on the order
+        if (sum >= (1u << 29) || sum < tris) return fail(c, R3N_ERR_UNSUPPORTED, "blend objects: more than 2^29 blend triangles in draw order");
+        tris = sum;
+    }
+    c->n_blend = n;
+    c->blend_tris = tris;
+    c->blend_sorted = n != 0u;  // n == 0 clears the set: nothing to sort, nothing to draw
+    if (n == 0) return R3N_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    TRY(ensure(c, c->blend_order, (size_t)n * 4, false, -1));
+    TRY(ensure(c, c->blend_rank_base, (size_t)(n + 1) * 4, false, -1));
+    TRY(ensure(c, c->blend_set_slots, (size_t)n * 4, false, -1));
+    TRY(ensure(c, c->blend_set_locations, (size_t)n * 12, false, -1));
+    const size_t scratch = r3n_internal_blend_sort_scratch_words(n) * 4;
+    if (scratch) TRY(ensure(c, c->blend_sort_scratch, scratch, false, -1));
+    // (read by r3n_blend_sort on the main stream: in order with these copies)
+    TRY(upload_bulk(c, c->blend_set_slots.p, slots, (size_t)n * 4));  // through pinned staging: no wait for the GPU
+    TRY(upload_bulk(c, c->blend_set_locations.p, locations, (size_t)n * 12));
+    return R3N_OK;
+}
+
+int r3n_blend_sort(r3n_ctx *c, const float camera_location[3]) {
+    if (!c || !camera_location) return fail(c, R3N_ERR_INVALID_ARG, "blend sort: null");
+    if (!c->blend_sorted) return R3N_OK;  // no set (or host order mode): nothing to do
+    HIP_TRY(c, hipSetDevice(c->device));
+    BlendSortArgs a{};
+    a.slots = c->blend_set_slots.as<uint32_t>();
+    a.locations = c->blend_set_locations.as<float>();
+    a.n = c->n_blend;
+    for (int k = 0; k < 3; ++k) a.camera[k] = camera_location[k];
+    a.obj_meta = c->obj_meta.as<uint32_t>();
+    a.order = c->blend_order.as<uint32_t>();
+    a.rank_base = c->blend_rank_base.as<uint32_t>();
+    a.scratch = c->blend_sort_scratch.as<uint32_t>();
+    {
+        Timed t(c, R3N_STAGE_BLEND_SORT, c->stream);
+        HIP_TRY(c, (hipError_t)r3n_internal_blend_sort(&a, c->stream));
+    }
+    ++c->main_epoch;
     return R3N_OK;
 }
 
@@ -2879,6 +2937,16 @@ int r3n_readback_triangle_sets(r3n_ctx *c, r3n_camera cam, uint8_t *pass, uint8_
                 }
         }
     }
+    return check_async_status(c);
+}
+
+int r3n_readback_blend_order(r3n_ctx *c, uint32_t *order, uint32_t *rank_base, uint32_t capacity) {
+    if (!c || !order || !rank_base) return fail(c, R3N_ERR_INVALID_ARG, "readback_blend_order: null");
+    if (capacity < c->n_blend) return fail(c, R3N_ERR_INVALID_ARG, "readback_blend_order: buffer too small");
+    rank_base[0] = 0u;
+    if (c->n_blend == 0u) return check_async_status(c);
+    TRY(copy_d2h(c, order, c->blend_order.p, (size_t)c->n_blend * 4));
+    TRY(copy_d2h(c, rank_base, c->blend_rank_base.p, (size_t)(c->n_blend + 1u) * 4));
     return check_async_status(c);
 }
 

@@ -300,3 +300,16 @@ def blend_draw_order(camera_location, object_indices, locations):
         keyed.append((-float(f32(dist)), int(idx)))
     keyed.sort()
     return [i for _k, i in keyed]
+
+
+def blend_sort_key(camera_location, location):
+    """The u32 the device sort (rend3_amd/csrc/blend_sort.hip, r3n_blend_sort) orders by, ascending, ties by ascending object slot:
+    blend_draw_order's key -distance^2, with d = camera - location and dist = (d.x*d.x + d.y*d.y) + d.z*d.z in f32, mapped to an
+    unsigned integer of the same order -- a negative float's bits inverted, a positive one's with the sign bit set.  dist is never
+    negative, so the key is never +0.0, the one float this mapping would separate from its equal (-0.0).  dist = +inf -> 0x007FFFFF."""
+    cam = np.asarray(camera_location, dtype=f32)
+    with np.errstate(over="ignore", under="ignore", invalid="ignore"):
+        d = cam - np.asarray(location, dtype=f32)
+        dist = f32(f32(d[0] * d[0]) + f32(d[1] * d[1])) + f32(d[2] * d[2])
+        bits = np.array([-f32(dist)], dtype=f32).view(np.uint32)[0]
+    return np.uint32(~bits) if bits & np.uint32(0x80000000) else np.uint32(bits | np.uint32(0x80000000))

@@ -175,8 +175,14 @@ class EvalOutput:
 class Renderer:
     """World bookkeeping feeding the object/mesh/material/light buffers of the C ABI."""
 
-    def __init__(self, handedness=host.LEFT, aspect_ratio=None, device=0, max_big_items=None):
+    def __init__(self, handedness=host.LEFT, aspect_ratio=None, device=0, max_big_items=None, blend_sort="host"):
         self.lib = _ffi.lib()
+        if blend_sort not in ("host", "gpu"):
+            raise ValueError("blend_sort: 'host' or 'gpu'")
+        # where the transparent pass's back-to-front order is sorted: "host" = host.blend_draw_order + r3n_blend_order_write every
+        # frame; "gpu" = the blend set goes up when the world changes (r3n_blend_objects_write), r3n_blend_sort orders it per frame
+        self.blend_sort = blend_sort
+        self._blend_sent = None  # "gpu": the (slots, locations) of the last r3n_blend_objects_write
         config = None
         if max_big_items is not None:  # r3n_config.max_big_items: raster work-queue capacity (the library keeps a floor, r3n.h)
             config = _ffi.Config(struct_size=ctypes.sizeof(_ffi.Config), max_big_items=int(max_big_items))
@@ -708,7 +714,37 @@ class Renderer:
         self._write_blend_order(self.camera.location)
         return EvalOutput(shadows, size)
 
+    def _sort_blend_order(self, camera_location):
+        """blend_sort == "gpu": the blend set is sent when it changed -- a blend object came, went or moved --, and the order is
+        sorted on the device for this frame's camera location.  No per-object work in a frame without a world edit."""
+        if self._blend_cache is None or self._blend_sent is None:  # the world was edited / the mode was switched to "gpu"
+            self._blend_cache = [h for h, m in sorted(self.object_meta.items())
+                                 if m["enabled"] and self.materials[m["material"]][1] == BLEND]
+            slots = np.asarray(self._blend_cache, dtype=np.uint32)
+            locs = np.ascontiguousarray([self.object_meta[h]["location"] for h in self._blend_cache], dtype=f32).reshape(-1, 3)
+            sent = self._blend_sent
+            if sent is None or not (np.array_equal(sent[0], slots) and np.array_equal(sent[1].view(np.uint32), locs.view(np.uint32))):
+                if len(slots) or self._had_blend:
+                    self._check(self.lib.r3n_blend_objects_write(self.ctx, _ffi.ptr(slots) if len(slots) else None,
+                                                                 _ffi.ptr(locs) if len(slots) else None, len(slots)),
+                                "r3n_blend_objects_write")
+                self._blend_sent = (slots, locs)
+        if self._blend_cache:
+            cam = np.ascontiguousarray(camera_location, dtype=f32)
+            self._check(self.lib.r3n_blend_sort(self.ctx, _ffi.ptr(cam)), "r3n_blend_sort")
+        self._had_blend = bool(self._blend_cache)
+
+    def readback_blend_order(self):
+        """(order, rank_base): the draw order the transparent pass reads and the scan of its triangle counts (parity tap)."""
+        n = len(self._blend_cache or ())
+        order, rank = np.zeros(max(n, 1), dtype=np.uint32), np.zeros(n + 1, dtype=np.uint32)
+        self._check(self.lib.r3n_readback_blend_order(self.ctx, _ffi.ptr(order), _ffi.ptr(rank), n), "r3n_readback_blend_order")
+        return order[:n], rank
+
     def _write_blend_order(self, camera_location):
+        if self.blend_sort == "gpu":
+            return self._sort_blend_order(camera_location)
+        self._blend_sent = None  # (host order mode replaces whatever set the library holds)
         # the CPU batcher's back-to-front order of the blend-key objects (batching.rs:146-176), every frame
         if self._blend_cache is None:  # rebuilt only after objects / materials changed
             self._blend_cache = [h for h, m in sorted(self.object_meta.items())

@@ -71,6 +71,9 @@ def add_arguments(ap):
                     help="camera location and angles (default: the default scene's, mod.rs:320-322)")
     ap.add_argument("--skybox", default=None, metavar="DIR",
                     help="directory holding right|left|top|bottom|front|back .jpg or .png: the background cube (default: none)")
+    ap.add_argument("--blend-sort", choices=("host", "gpu"), default="host",
+                    help="where the transparent pass's back-to-front order is sorted (not in the reference, whose CPU batcher sorts): "
+                         "host = every frame on the CPU, gpu = r3n_blend_sort")
     return ap
 
 
@@ -87,7 +90,8 @@ def settings_from(args):
                 directional_light=args.directional_light, directional_light_intensity=args.directional_light_intensity,
                 ambient=args.ambient, scale=args.scale, shadow_distance=args.shadow_distance,
                 shadow_resolution=args.shadow_resolution, enable_directional=not args.gltf_disable_directional_lights,
-                camera=args.camera or DEFAULT_CAMERA, skybox=getattr(args, "skybox", None))
+                camera=args.camera or DEFAULT_CAMERA, skybox=getattr(args, "skybox", None),
+                blend_sort=getattr(args, "blend_sort", "host"))
 
 
 def default_settings(**over):
@@ -133,6 +137,10 @@ def build(r, hm, mk, settings):
     assert r.handedness == RIGHT, "scene_viewer is right-handed (App::HANDEDNESS, mod.rs:434)"
     if settings.get("skybox"):  # load_skybox (mod.rs:34-57); a renderer without cube textures fails here, it does not skip the sky
         r.set_background_texture(r.add_texture_cube(load_skybox(settings["skybox"]), srgb=True))
+    if settings.get("blend_sort", "host") != "host":  # (a renderer that cannot sort on the device fails here)
+        if not hasattr(r, "blend_sort"):
+            raise ValueError("--blend-sort gpu: this renderer has no device sort")
+        r.blend_sort = settings["blend_sort"]
     light = None
     if settings["directional_light"] is not None:  # setup (mod.rs:463-472)
         light = r.add_directional_light(color=(1.0, 1.0, 1.0), intensity=settings["directional_light_intensity"],
