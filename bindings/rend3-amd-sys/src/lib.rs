@@ -56,6 +56,7 @@ pub const R3N_TEXTURE_BC5_RG_SNORM: u32 = 31;
 pub const R3N_TEXTURE_BC6H_RGB_UFLOAT: u32 = 32;
 pub const R3N_TEXTURE_BC6H_RGB_FLOAT: u32 = 33;
 pub const R3N_TEXTURE_FORMAT_COUNT: u32 = 34;
+pub const R3N_MAX_MORPH_TARGETS: u32 = 256;
 pub const R3N_SHADE_EXACT: u32 = 0;
 pub const R3N_SHADE_FAST: u32 = 1;
 pub const R3N_OUTPUT_RGBA8_UNORM_SRGB: u32 = 0;
@@ -95,7 +96,8 @@ pub const R3N_STAGE_RASTER_CUT: i32 = 18;
 pub const R3N_STAGE_RASTER_BIG_CUT: i32 = 19;
 pub const R3N_STAGE_SKYBOX: i32 = 20;
 pub const R3N_STAGE_BLEND_SORT: i32 = 21;
-pub const R3N_STAGE_COUNT: i32 = 22;
+pub const R3N_STAGE_MORPH: i32 = 22;
+pub const R3N_STAGE_COUNT: i32 = 23;
 
 #[repr(C)]
 pub struct r3n_ctx {
@@ -200,6 +202,23 @@ pub struct r3n_skinning_input40 {
     pub updated_normal_offset: u32,
     pub updated_tangent_offset: u32,
     pub joint_matrix_base_offset: u32,
+    pub vertex_count: u32,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct r3n_morph_input48 {
+    pub base_position_offset: u32,
+    pub base_normal_offset: u32,
+    pub base_tangent_offset: u32,
+    pub delta_position_offset: u32,
+    pub delta_normal_offset: u32,
+    pub delta_tangent_offset: u32,
+    pub updated_position_offset: u32,
+    pub updated_normal_offset: u32,
+    pub updated_tangent_offset: u32,
+    pub weight_base: u32,
+    pub n_targets: u32,
     pub vertex_count: u32,
 }
 
@@ -365,6 +384,7 @@ extern "C" {
     pub fn r3n_skinning(ctx: *mut r3n_ctx, inputs: *const r3n_skinning_input40, n_skeletons: u32, joint_matrices: *const f32, n_joint_matrices: u32) -> c_int;
     pub fn r3n_animation_write(ctx: *mut r3n_ctx, rigs: *const r3n_anim_rig16, n_rigs: u32, joints: *const r3n_anim_joint80, n_joints: u32, clips: *const r3n_anim_clip16, n_clips: u32, tracks: *const r3n_anim_track80, n_tracks: u32, times: *const f32, n_times: u32, values: *const f32, n_values: u32) -> c_int;
     pub fn r3n_pose_skeletons(ctx: *mut r3n_ctx, requests: *const r3n_pose_request16, n: u32) -> c_int;
+    pub fn r3n_morph(ctx: *mut r3n_ctx, inputs: *const r3n_morph_input48, n_instances: u32, weights: *const f32, n_weights: u32) -> c_int;
     pub fn r3n_uniform_bake(ctx: *mut r3n_ctx, camera: u32, header: *const r3n_camera_header240) -> c_int;
     pub fn r3n_cull(ctx: *mut r3n_ctx, camera: u32) -> c_int;
     pub fn r3n_hi_z(ctx: *mut r3n_ctx) -> c_int;

@@ -192,6 +192,19 @@ typedef struct r3n_skinning_input40 {
     uint32_t joint_matrix_base_offset, vertex_count;
 } r3n_skinning_input40;
 
+/* One morph instance of r3n_morph, 48 B: a mesh's POSITION / NORMAL / TANGENT runs, the deltas of its glTF morph targets and the
+ * instance's private output runs.  Byte offsets into the mesh buffer; 0xFFFFFFFF = absent.  An attribute is morphed when it has
+ * deltas: base, delta and updated offset are then all present, else all three absent.  The deltas of one attribute are
+ * `n_targets` runs of 3 * vertex_count f32 words, target-major, back to back. */
+typedef struct r3n_morph_input48 {
+    uint32_t base_position_offset, base_normal_offset, base_tangent_offset;
+    uint32_t delta_position_offset, delta_normal_offset, delta_tangent_offset; /* target 0's run; target t at + t * 12 * vertex_count */
+    uint32_t updated_position_offset, updated_normal_offset, updated_tangent_offset;
+    uint32_t weight_base; /* first weight of this instance in `weights` */
+    uint32_t n_targets, vertex_count;
+} r3n_morph_input48;
+#define R3N_MAX_MORPH_TARGETS 256u
+
 /* ---- rend3-anim (rend3-anim/src/lib.rs) tables, row N4.  A RIG is one skin: its joints in the skin's order, each with
  * its parent joint and its depth in the joint hierarchy (AnimationData::from_gltf_scene, :77-145, flattened); a CLIP is
  * one animation applied to one rig: a track per joint with the key ranges of its translation / rotation / scale
@@ -361,6 +374,19 @@ int r3n_animation_write(r3n_ctx *ctx, const r3n_anim_rig16 *rigs, uint32_t n_rig
                         uint32_t n_joints, const r3n_anim_clip16 *clips, uint32_t n_clips, const r3n_anim_track80 *tracks,
                         uint32_t n_tracks, const float *times, uint32_t n_times, const float *values, uint32_t n_values);
 int r3n_pose_skeletons(r3n_ctx *ctx, const r3n_pose_request16 *requests, uint32_t n);
+/* glTF 2.0 morph targets (the reference stops at a TODO, rend3-gltf/src/lib.rs:761-763; the arithmetic is defined here and in
+ * DESIGN.md section 2).  For each instance and each attribute that has deltas, every f32 word k of the run becomes
+ *     acc = base[k];  for t = 0 .. n_targets - 1 with weights[weight_base + t] != 0.0f:  acc = fl(acc + fl(w[t] * delta[t][k]));  updated[k] = acc
+ * one rounding per operation, no fused multiply-add.  Skipping the weights that compare equal to zero (+0 and -0; NaN does not) is
+ * part of the definition: all-zero weights reproduce the base run bit for bit (a -0.0 word included).  Nothing is normalised.
+ * ONE launch covers every instance of the call; instances and weights go through pinned staging, the call only enqueues on the
+ * context's stream and does not wait for the GPU.  Callable between frames, or inside one in front of r3n_skinning: morph comes
+ * first, a skeleton that skins a morphed instance takes the updated_* runs as its base_* runs.  It orders itself behind a resolve
+ * still in flight, as r3n_skinning does.  n_instances == 0 returns R3N_OK and launches nothing.
+ * R3N_ERR_INVALID_ARG: a run outside the mesh buffer or not 4-byte aligned; a delta without its base or its output, or a base or
+ * an output without a delta; weight_base + n_targets > n_weights; n_targets outside 1 .. R3N_MAX_MORPH_TARGETS;
+ * an instance that morphs nothing; an output run that overlaps a base or delta run of the same instance. */
+int r3n_morph(r3n_ctx *ctx, const r3n_morph_input48 *inputs, uint32_t n_instances, const float *weights, uint32_t n_weights);
 /* GpuCuller::object_uniform_upload (culler.rs:427-529) + uniform_prep.wgsl.  Called on its own it bakes every enabled slot, like
  * the reference.  Inside r3n_render_frame the bake is fused into the object pass and covers only the slots a kernel reads: those
  * inside the frustum now or (viewport) in the camera's previous frame -- the others keep what they held. */
@@ -584,7 +610,8 @@ int r3n_readback_output(r3n_ctx *ctx, uint8_t *rgba8, float *rgba_f32); /* eithe
 #define R3N_STAGE_RASTER_BIG_CUT 19  /* viewport, CUTOUT key: work-item pass */
 #define R3N_STAGE_SKYBOX 20          /* the skybox node (r3n_skybox) */
 #define R3N_STAGE_BLEND_SORT 21      /* r3n_blend_sort: the transparent pass's draw order sorted on the device */
-#define R3N_STAGE_COUNT 22
+#define R3N_STAGE_MORPH 22           /* r3n_morph: morph targets blended into the instances' private runs */
+#define R3N_STAGE_COUNT 23
 int r3n_timing_enable(r3n_ctx *ctx, int enable);
 /* What a timed span holds besides its kernels -- two event packets and a launch's dispatch, measured around an empty kernel when
  * timing is first enabled (median of 32) -- and already taken off every span r3n_stage_times reports. */

@@ -20,6 +20,9 @@ KEY_OPAQUE, KEY_CUTOUT, KEY_BLEND = 0, 1, 2
 STAGES = ["bake", "object_cull", "triangle_cull", "hiz", "raster", "shade", "tonemap", "clear", "raster_big",
           "shadow_raster", "shadow_raster_big", "skinning", "vertex", "pose", "exchange_shadow", "exchange_depth", "exchange_rows", "exchange_keys",
           "raster_cut", "raster_big_cut", "skybox", "blend_sort"]
+# STAGES stays the 22 names above: tests/test_blend_sort_key.py pins its length.  Stages appended since follow in STAGE_NAMES, the
+# table r3n_stage_times fills (R3N_STAGE_COUNT entries) -- size its arrays by STAGE_NAMES, never by STAGES.
+STAGE_NAMES = STAGES + ["morph"]
 
 COMM_ID_BYTES, COMM_IDS = 128, 3  # R3N_COMM_ID_BYTES, R3N_COMM_IDS
 
@@ -40,6 +43,7 @@ SIGNATURES = {
     "r3n_skybox_set": (cint, [vp, u32]),
     "r3n_animation_write": (cint, [vp, vp, u32, vp, u32, vp, u32, vp, u32, vp, u32, vp, u32]),
     "r3n_pose_skeletons": (cint, [vp, vp, u32]),
+    "r3n_morph": (cint, [vp, vp, u32, vp, u32]),
     "r3n_set_output_format": (cint, [vp, u32]),
     "r3n_set_shade_mode": (cint, [vp, u32]),
     "r3n_set_skinning_mode": (cint, [vp, u32]),
@@ -113,6 +117,7 @@ SIGNATURES = {
 }
 
 MAX_SHADOW_VIEWS = 64
+MAX_MORPH_TARGETS = 256  # R3N_MAX_MORPH_TARGETS
 EXCHANGE_SITES = ("shadow", "pass1", "pass2")  # R3N_EXCHANGE_*
 FRAME_VIEWPORT_FIRST, FRAME_SHADOW_MASK = 1, 2
 EXCHANGE_FN = ctypes.CFUNCTYPE(cint, vp, u32)  # r3n_exchange_fn

@@ -119,6 +119,21 @@ def _sample(channel, t, quat):
     return q
 
 
+def sample_morph_weights(channel, t):
+    """One `weights` channel of gltf.load_animations, (times, values[K, T], interpolation), at time t: the T weights as f32.
+    Keys and x come from _sample_index (previous and next key, x clamped to [0, 1]); LINEAR blends every weight as
+    fl(a + fl(fl(b - a) * x)), like the vec3 channels.  STEP holds the previous key: x = 0 -- except from the LAST key on, where
+    _sample_index still returns the last interval, with x = 1, and the held value is that last key's."""
+    times, values, interpolation = channel
+    p, n, x = _sample_index(np.asarray(times, dtype=f32), t)
+    if interpolation == "STEP":
+        x = ONE if x >= ONE else ZERO
+    elif interpolation != "LINEAR":
+        raise ValueError(f"weights channel: {interpolation} interpolation is not supported")
+    a, b = np.asarray(values[p], dtype=f32), np.asarray(values[n], dtype=f32)
+    return np.array([f32(a[k] + f32(f32(b[k] - a[k]) * x)) for k in range(len(a))], dtype=f32)
+
+
 # ---------------------------------------------------------------------------------------------- rend3-anim API
 class AnimationData:
     """AnimationData::from_gltf_scene (rend3-anim/src/lib.rs:77-145) as flat tables: one rig per skin (joints in the
@@ -196,7 +211,8 @@ class AnimationData:
 def pose_animation_frame(renderer, instance, animation_data, animation_index, time):
     """pose_animation_frame (rend3-anim/src/lib.rs:181-263).  Node half on the host: every animated node's objects get
     the node's LOCAL matrix from the sampled scale / rotation / translation, z scale negated for a left-handed renderer
-    (:191-211).  Skin half on the GPU: one pose request per skeleton of every skin."""
+    (:191-211).  Skin half on the GPU: one pose request per skeleton of every skin.  Every node with a `weights` channel in the
+    animation gets the sampled weights on its morph instances (set_morph_weights; not in the reference)."""
     anim = animation_data.animations[animation_index]
     t = f32(time)
     if t < ZERO:
@@ -216,6 +232,11 @@ def pose_animation_frame(renderer, instance, animation_data, animation_index, ti
         m = mat4_from_srt(sc, ro, tr)
         for h in nodes[node_idx]["objects"]:
             renderer.set_object_transform(h, m)
+    for node_idx, ch in anim.get("morph_channels", {}).items():
+        if nodes[node_idx].get("morphs"):
+            weights = sample_morph_weights(ch, t)
+            for inst in nodes[node_idx]["morphs"]:
+                renderer.set_morph_weights(inst, weights)
     requests = []
     for si in range(animation_data.n_skins):
         clip = animation_data.clip_base + animation_index * animation_data.n_skins + si

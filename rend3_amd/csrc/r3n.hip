@@ -21,6 +21,7 @@
 #include "kernels_shade.h"
 #include "skybox.h"
 #include "blend_sort.h"
+#include "morph.h"
 
 namespace {
 
@@ -179,6 +180,8 @@ struct r3n_ctx {
     uint32_t skinning_mode = R3N_SKIN_EXACT, skin_max_joints = 0;
     std::vector<r3n_skinning_input40> h_skin_inputs;
     uint32_t skin_total_waves = 0;
+    // morph targets (morph.h): the records, wave map and weight terms of ONE r3n_morph call, as one block behind one staged copy
+    DevBuf morph_block;
     uint32_t slot_table_size = 0;
     CamState canon;  // scratch camera used to (re)build the canonical tri_base scan
     // frame targets
@@ -395,7 +398,7 @@ int check_async_status(r3n_ctx *c) {
 
 static const char *const kStageNames[R3N_STAGE_COUNT] = {"bake", "object_cull", "triangle_cull", "hiz", "raster", "shade", "tonemap", "clear",
     "raster_big", "shadow_raster", "shadow_raster_big", "skinning", "vertex", "pose", "exchange_shadow", "exchange_depth",
-    "exchange_rows", "exchange_keys", "raster_cut", "raster_big_cut", "skybox", "blend_sort"};
+    "exchange_rows", "exchange_keys", "raster_cut", "raster_big_cut", "skybox", "blend_sort", "morph"};
 static void crumb(const r3n_ctx *c, const char *what, long long a, long long b) {
     if (c->crumb_fd < 0) return;
     char line[160];
@@ -942,7 +945,7 @@ void r3n_destroy(r3n_ctx *c) {
     }
     DevBuf *bufs[] = {&c->mesh, &c->objects, &c->spheres, &c->obj_meta, &c->materials, &c->material_keys, &c->fb_dev[0], &c->fb_dev[1], &c->big_count_all, &c->owners,
                       &c->tri_base, &c->slot_table, &c->skin_inputs, &c->skin_matrices, &c->skin_wave_skeleton,
-                      &c->skin_wave_first, &c->skin_joint_counts, &c->vis, &c->hdr16, &c->out8, &c->out_f32, &c->atlas, &c->hiz, &c->alt_vis, &c->alt_atlas, &c->alt_vp_baked, &c->srgb_lut, &c->srgb_thr, &c->tex_descs, &c->tex_texels, &c->tex_level_off, &c->srgb8_decode,
+                      &c->skin_wave_first, &c->skin_joint_counts, &c->morph_block, &c->vis, &c->hdr16, &c->out8, &c->out_f32, &c->atlas, &c->hiz, &c->alt_vis, &c->alt_atlas, &c->alt_vp_baked, &c->srgb_lut, &c->srgb_thr, &c->tex_descs, &c->tex_texels, &c->tex_level_off, &c->srgb8_decode,
                       &c->tri_rec, &c->tri_seen, &c->blend_order, &c->blend_rank_base, &c->frag_keys, &c->frag_vals, &c->frag_head,
                       &c->frag_count, &c->samples16, &c->anim_rigs, &c->anim_joints, &c->anim_clips, &c->anim_tracks,
                       &c->anim_times, &c->anim_values, &c->pose_requests, &c->edge_list, &c->edge_count, &c->material_feat, &c->view_lights[0],
@@ -1470,6 +1473,85 @@ int r3n_skinning(r3n_ctx *c, const r3n_skinning_input40 *inputs, uint32_t n, con
                        c->skin_inputs.as<r3n_skinning_input40>(), c->skin_matrices.as<float>(),
                        c->skin_wave_skeleton.as<uint32_t>(), c->skin_wave_first.as<uint32_t>(), c->skin_total_waves);
     return check_launch(c, "k_skinning");
+}
+
+// glTF morph targets (morph.h / morph.hip).  Everything the kernel reads besides the mesh buffer -- instance records, the
+// (target, weight) terms with the zero weights dropped, the wave -> instance map -- is laid out in ONE host block and staged with
+// ONE copy: the instance set differs from call to call, so nothing is cached and nothing waits for the GPU.
+int r3n_morph(r3n_ctx *c, const r3n_morph_input48 *inputs, uint32_t n, const float *weights, uint32_t n_weights) {
+    if (!c) return R3N_ERR_INVALID_ARG;
+    if (n == 0) return R3N_OK;
+    if (!inputs || !weights) return fail(c, R3N_ERR_INVALID_ARG, "morph: null inputs");
+    const uint64_t mesh_words = c->mesh.bytes / 4;
+    uint64_t total_waves = 0, total_terms = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        const r3n_morph_input48 &in = inputs[i];
+        if (in.n_targets < 1u || in.n_targets > R3N_MAX_MORPH_TARGETS)
+            return fail(c, R3N_ERR_INVALID_ARG, "morph: n_targets must be 1 .. R3N_MAX_MORPH_TARGETS");
+        if ((uint64_t)in.weight_base + in.n_targets > n_weights) return fail(c, R3N_ERR_INVALID_ARG, "morph: weight_base + n_targets past the weights");
+        const uint64_t run = (uint64_t)in.vertex_count * 3u;  // words of one run
+        const uint32_t base[3] = {in.base_position_offset, in.base_normal_offset, in.base_tangent_offset};
+        const uint32_t delta[3] = {in.delta_position_offset, in.delta_normal_offset, in.delta_tangent_offset};
+        const uint32_t out[3] = {in.updated_position_offset, in.updated_normal_offset, in.updated_tangent_offset};
+        uint32_t morphed = 0;
+        for (int a = 0; a < 3; ++a) {
+            if (delta[a] == R3N_INVALID) {
+                // an attribute without deltas is not copied: the record names neither a base nor an output run for it
+                if (base[a] != R3N_INVALID || out[a] != R3N_INVALID) return fail(c, R3N_ERR_INVALID_ARG, "morph: a base or output run without deltas");
+                continue;
+            }
+            if (base[a] == R3N_INVALID || out[a] == R3N_INVALID) return fail(c, R3N_ERR_INVALID_ARG, "morph: deltas without their base or output run");
+            // (first word, words) of the three ranges the kernel touches for this attribute
+            const uint64_t rb[2] = {base[a] / 4u, run}, rd[2] = {delta[a] / 4u, run * in.n_targets}, ro[2] = {out[a] / 4u, run};
+            if (((base[a] | delta[a] | out[a]) & 3u) != 0u || rb[0] + rb[1] > mesh_words || rd[0] + rd[1] > mesh_words || ro[0] + ro[1] > mesh_words)
+                return fail(c, R3N_ERR_INVALID_ARG, "morph: attribute range outside the mesh buffer");
+            if (run && ((ro[0] < rb[0] + rb[1] && rb[0] < ro[0] + ro[1]) || (ro[0] < rd[0] + rd[1] && rd[0] < ro[0] + ro[1])))
+                return fail(c, R3N_ERR_INVALID_ARG, "morph: an output run overlaps a base or delta run of its instance");
+            ++morphed;
+        }
+        if (!morphed) return fail(c, R3N_ERR_INVALID_ARG, "morph: an instance without deltas");
+        total_waves += r3n_morph_waves(in.vertex_count);
+        for (uint32_t t = 0; t < in.n_targets; ++t) total_terms += weights[in.weight_base + t] == 0.0f ? 0u : 1u;
+    }
+    if (total_waves > 0x7FFFFFFFull) return fail(c, R3N_ERR_UNSUPPORTED, "morph: more than 2^31 wave slots in one call");
+    HIP_TRY(c, hipSetDevice(c->device));
+    TRY(join_shade(c));  // frames in flight: the previous frame's resolve reads the runs this rewrites
+    if (total_waves == 0) return R3N_OK;  // (instances of zero vertices)
+    // block layout, in words: records | wave_first | wave_instance | terms
+    const size_t o_first = (size_t)n * 16u, o_inst = o_first + n, o_terms = (o_inst + total_waves + 1u) & ~(size_t)1u;
+    std::vector<uint32_t> block(o_terms + 2u * (size_t)total_terms);
+    uint32_t w = 0, term = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        r3n_morph_rec64 rec{};
+        rec.in = inputs[i];
+        rec.pair_first = term;
+        for (uint32_t t = 0; t < rec.in.n_targets; ++t) {
+            const float wt = weights[rec.in.weight_base + t];
+            if (wt == 0.0f) continue;  // part of the contract: +0 and -0 are no terms, NaN is one
+            block[o_terms + 2u * (size_t)term] = t;
+            std::memcpy(&block[o_terms + 2u * (size_t)term + 1u], &wt, 4);
+            ++term;
+        }
+        rec.n_active = term - rec.pair_first;
+        std::memcpy(&block[(size_t)i * 16u], &rec, sizeof rec);
+        block[o_first + i] = w;
+        const uint32_t nw = r3n_morph_waves(rec.in.vertex_count);
+        std::fill(block.begin() + o_inst + w, block.begin() + o_inst + w + nw, i);
+        w += nw;
+    }
+    TRY(ensure(c, c->morph_block, block.size() * 4, false, -1));
+    TRY(upload_bulk(c, c->morph_block.p, block.data(), block.size() * 4));  // pinned staging: no wait for the GPU
+    MorphArgs a{};
+    a.mesh = c->mesh.as<uint32_t>();
+    a.recs = c->morph_block.as<r3n_morph_rec64>();
+    a.wave_first = c->morph_block.as<uint32_t>() + o_first;
+    a.wave_instance = c->morph_block.as<uint32_t>() + o_inst;
+    a.pairs = reinterpret_cast<const r3n_morph_pair *>(c->morph_block.as<uint32_t>() + o_terms);
+    a.total_waves = w;
+    ++c->main_epoch;  // the shadow lanes read the morphed attribute runs
+    Timed t(c, R3N_STAGE_MORPH);
+    HIP_TRY(c, (hipError_t)r3n_internal_morph(&a, c->stream));
+    return R3N_OK;
 }
 
 int r3n_animation_write(r3n_ctx *c, const r3n_anim_rig16 *rigs, uint32_t n_rigs, const r3n_anim_joint80 *joints, uint32_t n_joints,

@@ -3,7 +3,11 @@ into numpy arrays, node hierarchy, skins, materials with their textures (PNG / J
 containers.py), KHR_lights_punctual directional lights and animations, fed into the Renderer-shaped API the way
 rend3-gltf does (rend3-gltf/src/lib.rs: load_meshes :607-678, load_materials_and_textures :806-943, load_image
 :984-1130, load_animations :724-773, instance_loaded_scene :493-562; examples/src/static_gltf/mod.rs:5-41).
-Not read: cameras, morph targets; TEXCOORD_1 is decoded but not uploaded (no shader of the path reads it).
+Morph targets (glTF 2.0 section 3.7.2.2) are read where the reference stops at a TODO (:761-763): a primitive's POSITION /
+NORMAL / TANGENT targets, `weights` of meshes and nodes, and `weights` animation channels (LINEAR and STEP); the blend runs
+on the GPU (Renderer.add_morph_instance, csrc/morph.hip; arithmetic in DESIGN.md section 2).  A mesh without NORMAL keeps the
+normals computed from its base shape under any weights.
+Not read: cameras; TEXCOORD_1 is decoded but not uploaded (no shader of the path reads it).
 """
 import json
 import os
@@ -112,6 +116,18 @@ class Gltf:
         else:
             out["indices"] = np.arange(len(out["positions"]), dtype=np.uint32)
         out["material"] = p.get("material")
+        if p.get("targets"):
+            # morph targets: per attribute f32[T, V, 3] (a target that lacks an attribute another has holds zeros there), or None
+            # when no target has it; TANGENT deltas are vec3 (no handedness component)
+            targets, n_vertices = p["targets"], len(out["positions"])
+            morph = {}
+            for key, name in (("positions", "POSITION"), ("normals", "NORMAL"), ("tangents", "TANGENT")):
+                if any(name in t for t in targets):
+                    morph[key] = np.stack([self.accessor(t[name]).astype(np.float32)[:, :3] if name in t
+                                           else np.zeros((n_vertices, 3), dtype=np.float32) for t in targets])
+                else:
+                    morph[key] = None
+            out["targets"] = morph
         return out
 
     def base_color_factor(self, material):
@@ -258,8 +274,10 @@ def instance_scene(g, r, hm, mk, scale=1.0, enable_directional=True, directional
     under parent_transform = scale(s, s, -s for a left-handed renderer); one object per mesh primitive; a skeleton per
     primitive of a skinned node (joint matrices start as identity, add_mesh_by_index :411-457); winding flipped for
     left-handed renderers (load_meshes :628-634); KHR_lights_punctual directional lights become
-    directional lights (GltfLoadSettings::enable_directional / directional_light_* defaults).  Returns dict(objects=[handles], skeletons=[handles],
-    inverse_bind_matrices=[per skin], node_transforms)."""
+    directional lights (GltfLoadSettings::enable_directional / directional_light_* defaults).  A primitive with morph targets
+    gets one morph instance per (node, primitive), initial weights node.weights, else mesh.weights, else zeros, recorded under
+    nodes[i]["morphs"]; on a skinned node the skeleton skins from the morphed runs.  Returns dict(objects=[handles],
+    skeletons=[handles], inverse_bind_matrices=[per skin], node_transforms)."""
     nodes = g.json.get("nodes", [])
     lh = r.handedness == 0
     parent_of = {}
@@ -278,7 +296,7 @@ def instance_scene(g, r, hm, mk, scale=1.0, enable_directional=True, directional
     image_cache = {}
     xf = [None] * len(nodes)
     out = dict(objects=[], skeletons=[], lights=[], inverse_bind_matrices=[], node_transforms=xf, topological_order=order,
-               nodes=[dict(parent=parent_of.get(i), local_transform=None, objects=[], skin=None, skeletons=[]) for i in range(len(nodes))],
+               nodes=[dict(parent=parent_of.get(i), local_transform=None, objects=[], skin=None, skeletons=[], morphs=[]) for i in range(len(nodes))],
                skins=[dict(joints=list(sk["joints"])) for sk in g.json.get("skins", [])])
     for sk in g.json.get("skins", []):
         nj = len(sk["joints"])
@@ -306,20 +324,30 @@ def instance_scene(g, r, hm, mk, scale=1.0, enable_directional=True, directional
             if (mi, pi) not in meshes:
                 p = g.primitive(mi, pi)
                 idx = p["indices"].reshape(-1, 3)[:, ::-1].reshape(-1) if lh else p["indices"]
+                morph_kw = {}
+                if p.get("targets") is not None:  # (only then: a file without targets makes the calls it always made)
+                    morph_kw = dict(morph_targets=p["targets"], morph_weights=g.json["meshes"][mi].get("weights"))
                 meshes[(mi, pi)] = (r.add_mesh(p["positions"], idx, normals=p.get("normals"), tangents=p.get("tangents"),
                                                joint_indices=p.get("joints"), joint_weights=p.get("weights"),
-                                               uv0=p.get("uv0"), colors=p.get("colors"), mesh_handedness=r.handedness), p["material"])
-            mesh, mat_index = meshes[(mi, pi)]
+                                               uv0=p.get("uv0"), colors=p.get("colors"), mesh_handedness=r.handedness, **morph_kw),
+                                    p["material"], bool(morph_kw))
+            mesh, mat_index, has_targets = meshes[(mi, pi)]
+            morph = None
+            if has_targets:
+                morph = r.add_morph_instance(mesh, node.get("weights", g.json["meshes"][mi].get("weights")))
+                out["nodes"][ni]["morphs"].append(morph)
             if mat_index not in materials:
                 rec, key = material_from_gltf(g, mat_index, mk, r, image_cache, normal_y_down=normal_y_down)
                 materials[mat_index] = r.add_material(rec, key)
             if "skin" in node:
                 nj = len(out["inverse_bind_matrices"][node["skin"]])
-                sk = r.add_skeleton(mesh, np.tile(hm.identity(), (nj, 1)))
+                sk = r.add_skeleton(mesh, np.tile(hm.identity(), (nj, 1)), **({} if morph is None else dict(morph=morph)))
                 out["skeletons"].append(sk)
                 out["nodes"][ni]["skin"] = node["skin"]
                 out["nodes"][ni]["skeletons"].append(sk)
                 out["objects"].append(r.add_object(None, materials[mat_index], xf[ni], skeleton=sk))
+            elif morph is not None:
+                out["objects"].append(r.add_object(None, materials[mat_index], xf[ni], morph=morph))
             else:
                 out["objects"].append(r.add_object(mesh, materials[mat_index], xf[ni]))
             out["nodes"][ni]["objects"].append(out["objects"][-1])
@@ -330,23 +358,34 @@ def instance_scene(g, r, hm, mk, scale=1.0, enable_directional=True, directional
 
 def load_animations(g):
     """load_animations (rend3-gltf/src/lib.rs:724-773): per animation {"channels": {node: {"translation" | "rotation" |
-    "scale": (times, values)}}, "duration"}.  Keyframe values are taken as stored -- the reference ignores the
-    sampler's interpolation mode and always blends linearly (rend3-anim/src/lib.rs:163-175); rotations are read as f32
-    (normalised integer encodings converted like the gltf crate's into_f32).  Morph-target weights are skipped (:765).
-    duration = the latest key time of any channel (compute_animation_duration :706-722)."""
+    "scale": (times, values)}}, "morph_channels": {node: (times, values[K, T], interpolation)}, "duration"}.  Keyframe
+    values are taken as stored -- the reference ignores the sampler's interpolation mode of the transform channels and always
+    blends linearly (rend3-anim/src/lib.rs:163-175); rotations are read as f32 (normalised integer encodings converted like
+    the gltf crate's into_f32).  Morph-target `weights` channels (the reference's TODO, :761-765) keep their sampler's
+    interpolation, "LINEAR" or "STEP"; a CUBICSPLINE one raises ValueError (nothing on this path interprets spline tangents).
+    duration = the latest key time of any channel, weights included (compute_animation_duration :706-722)."""
     out = []
-    for anim in g.json.get("animations", []):
-        channels = {}
+    for ai, anim in enumerate(g.json.get("animations", [])):
+        channels, morph_channels = {}, {}
         duration = 0.0
         for ch in anim["channels"]:
             target = ch["target"]
-            if "node" not in target or target["path"] == "weights":
+            if "node" not in target:
                 continue
             smp = anim["samplers"][ch["sampler"]]
             times = g.accessor(smp["input"]).astype(np.float32).reshape(-1)
-            values = g.accessor(smp["output"]).astype(np.float32)
-            channels.setdefault(target["node"], {})[target["path"]] = (times, values)
+            if target["path"] == "weights":
+                interpolation = smp.get("interpolation", "LINEAR")
+                if interpolation not in ("LINEAR", "STEP"):
+                    raise ValueError(f"animation {anim.get('name', ai)!r}: {interpolation} weights sampler is not supported (LINEAR and STEP are)")
+                values = g.accessor(smp["output"]).astype(np.float32).reshape(-1)
+                if len(times) == 0 or len(values) % len(times):
+                    raise ValueError(f"animation {anim.get('name', ai)!r}: weights output is not a whole number of weights per key")
+                morph_channels[target["node"]] = (times, values.reshape(len(times), -1), interpolation)
+            else:
+                values = g.accessor(smp["output"]).astype(np.float32)
+                channels.setdefault(target["node"], {})[target["path"]] = (times, values)
             if len(times):
                 duration = max(duration, float(times.max()))
-        out.append(dict(channels=channels, duration=np.float32(duration), name=anim.get("name")))
+        out.append(dict(channels=channels, morph_channels=morph_channels, duration=np.float32(duration), name=anim.get("name")))
     return out

@@ -150,6 +150,25 @@ def material_record(albedo=(0, 0, 0, 1), albedo_mode="value", unlit=False, rough
     return rec
 
 
+def morph_reach(position_deltas, n_targets):
+    """reach[t] = max over the vertices of sqrt((dx * dx + dy * dy) + dz * dz), f32 with one rounding per operation: how far
+    target t moves any vertex at weight 1.  Zeros without position deltas."""
+    if position_deltas is None:
+        return np.zeros(n_targets, dtype=f32)
+    d = np.ascontiguousarray(position_deltas, dtype=f32).reshape(n_targets, -1, 3)
+    if d.shape[1] == 0:
+        return np.zeros(n_targets, dtype=f32)
+    return np.sqrt((d[:, :, 0] * d[:, :, 0] + d[:, :, 1] * d[:, :, 1]) + d[:, :, 2] * d[:, :, 2]).max(axis=1).astype(f32)
+
+
+def morph_radius(radius, weights, reach):
+    r = f32(radius)
+    for w, rc in zip(np.asarray(weights, dtype=f32), np.asarray(reach, dtype=f32)):
+        if w != 0.0:
+            r = f32(r + f32(f32(abs(w)) * rc))
+    return r
+
+
 class CameraSpecifier:
     """rend3-routine/src/common/camera.rs:3-35"""
     VIEWPORT = _ffi.CAMERA_VIEWPORT
@@ -161,7 +180,8 @@ class CameraSpecifier:
 
 
 class _Mesh:
-    __slots__ = ("attr_off", "first_index", "index_count", "centre", "radius", "vertex_count", "joint_off", "weight_off")
+    __slots__ = ("attr_off", "first_index", "index_count", "centre", "radius", "vertex_count", "joint_off", "weight_off",
+                 "n_targets", "delta_off", "reach", "morph_weights")
 
 
 class EvalOutput:
@@ -218,6 +238,8 @@ class Renderer:
         self._camera = None
         self.object_range = None
         self.skeletons = []
+        self.morphs = []           # add_morph_instance: dict(mesh, out_off[3], weights, objects)
+        self._morph_dirty = set()  # instances never evaluated, or whose weights changed since: the next frame's one r3n_morph call
         # R3N_FRAME_NODES=1: render() issues the frame node by node through the graph mirror (one C call per reference node, what
         # a Rust integration's node closures do); default: Renderer::evaluate's CPU work and the whole node list behind ONE C call
         # each (r3n_host_evaluate_frame, r3n_render_frame)
@@ -250,7 +272,12 @@ class Renderer:
 
     # ------------------------------------------------------------------ world edits
     def add_mesh(self, positions, indices=None, normals=None, colors=None, mesh_handedness=host.LEFT, tangents=None,
-                 joint_indices=None, joint_weights=None, uv0=None):
+                 joint_indices=None, joint_weights=None, uv0=None, morph_targets=None, morph_weights=None):
+        """morph_targets: glTF morph targets as dict(positions=, normals=, tangents=), each f32[T, V, 3] or None (at least one
+        given; a target that lacks an attribute the others have holds zeros there).  The deltas are written once, here, behind
+        the mesh's own runs: per attribute T target-major runs of 3 V words, the block 16-byte aligned.  morph_weights: the
+        mesh's default weights (T floats, default zeros).  A mesh without NORMAL gets the normals add_mesh computes from the BASE
+        shape; they are not recomputed for a morphed shape (only NORMAL deltas move them)."""
         positions = np.ascontiguousarray(positions, dtype=f32).reshape(-1, 3)
         if indices is None:
             indices = np.arange(len(positions), dtype=np.uint32)
@@ -286,6 +313,28 @@ class Renderer:
             m.weight_off = 4 * push(np.ascontiguousarray(joint_weights, dtype=f32).reshape(-1, 4).view(np.uint32).reshape(-1))
         m.first_index = push(indices)
         m.index_count = len(indices)
+        m.n_targets, m.delta_off, m.reach, m.morph_weights = 0, [INVALID] * 3, None, None
+        if morph_targets is not None:
+            deltas = [morph_targets.get(k) for k in ("positions", "normals", "tangents")]
+            shapes = {np.shape(d) for d in deltas if d is not None}
+            if len(shapes) != 1 or next(iter(shapes))[1:] != (len(positions), 3):
+                raise ValueError("morph_targets: every attribute given is [T, V, 3] with the mesh's V and one T")
+            m.n_targets = int(next(iter(shapes))[0])
+            if not 1 <= m.n_targets <= _ffi.MAX_MORPH_TARGETS:
+                raise ValueError("morph_targets: 1 .. R3N_MAX_MORPH_TARGETS targets")
+            if deltas[2] is not None and tangents is None:
+                raise ValueError("morph_targets: tangent deltas need tangents")
+            for a, d in enumerate(deltas):
+                if d is None:
+                    continue
+                if cursor % 4:  # the delta block starts on a 16-byte boundary
+                    push(np.zeros(4 - cursor % 4, dtype=np.uint32))
+                m.delta_off[a] = 4 * push(np.ascontiguousarray(d, dtype=f32).reshape(-1).view(np.uint32))
+            m.reach = morph_reach(deltas[0], m.n_targets)
+            m.morph_weights = (np.zeros(m.n_targets, dtype=f32) if morph_weights is None
+                               else np.ascontiguousarray(morph_weights, dtype=f32).reshape(-1).copy())
+            if len(m.morph_weights) != m.n_targets:
+                raise ValueError("morph_weights: one weight per target")
         blob = np.concatenate(chunks)
         self._check(self.lib.r3n_mesh_buffer_write(self.ctx, 4 * self.mesh_cursor, _ffi.ptr(blob), blob.nbytes),
                     "r3n_mesh_buffer_write")
@@ -295,10 +344,14 @@ class Renderer:
         return len(self.meshes) - 1
 
     # ---- skeletons (rend3/src/managers/skeleton.rs:67-163)
-    def add_skeleton(self, mesh, joint_matrices):
+    def add_skeleton(self, mesh, joint_matrices, morph=None):
+        """morph: a morph instance of the same mesh -- the skeleton then skins from the instance's morphed runs (glTF: morph
+        first, then skin) and its objects take the instance's widened bounding sphere."""
         m = self.meshes[mesh]
         if m.joint_off == INVALID:
             raise ValueError("Mesh must have joint indices to be used in a skeleton")  # SkeletonCreationError
+        if morph is not None and self.morphs[morph]["mesh"] != mesh:
+            raise ValueError("add_skeleton: the morph instance belongs to another mesh")
         out_off = [INVALID] * 3
         for a in range(3):  # private position / normal / tangent copies (skeleton.rs:110-113)
             if m.attr_off[a] != INVALID:
@@ -306,7 +359,8 @@ class Renderer:
                 zeros = np.zeros(3 * m.vertex_count, dtype=np.uint32)
                 self._check(self.lib.r3n_mesh_buffer_write(self.ctx, out_off[a], _ffi.ptr(zeros), zeros.nbytes), "r3n_mesh_buffer_write")
                 self.mesh_cursor += len(zeros)
-        self.skeletons.append(dict(mesh=mesh, out_off=out_off, matrices=np.ascontiguousarray(joint_matrices, dtype=f32).reshape(-1, 16)))
+        self.skeletons.append(dict(mesh=mesh, out_off=out_off, matrices=np.ascontiguousarray(joint_matrices, dtype=f32).reshape(-1, 16),
+                                   morph=morph))
         self._skin_inputs = None
         return len(self.skeletons) - 1
 
@@ -327,10 +381,86 @@ class Renderer:
                 if m.attr_off[a] != INVALID:
                     out_off[a] = 4 * (base + (i * n_attr + k) * words)
                     k += 1
-            self.skeletons.append(dict(mesh=mesh, out_off=out_off,
+            self.skeletons.append(dict(mesh=mesh, out_off=out_off, morph=None,
                                        matrices=np.ascontiguousarray(joint_matrices_per_skeleton[i], dtype=f32).reshape(-1, 16)))
         self._skin_inputs = None
         return list(range(first, first + n))
+
+    # ---- morph targets (glTF 2.0 section 3.7.2.2; DESIGN.md section 2 "Morph targets")
+    def add_morph_instance(self, mesh, weights=None):
+        """One set of weights over a mesh's morph targets, with private output runs for the attributes that have deltas (an
+        attribute without deltas keeps the mesh's own run).  weights: T floats, default the mesh's.  Bind it with
+        add_object(None, material, transform, morph=handle) or add_skeleton(mesh, matrices, morph=handle)."""
+        return self.add_morph_instances_bulk(mesh, [weights])[0]
+
+    def add_morph_instances_bulk(self, mesh, weights_per_instance):
+        """Many morph instances of one mesh: one zero-fill upload for all private output runs (16-byte aligned each)."""
+        m = self.meshes[mesh]
+        if not m.n_targets:
+            raise ValueError("add_morph_instance: the mesh has no morph targets")
+        n = len(weights_per_instance)
+        attrs = [a for a in range(3) if m.delta_off[a] != INVALID]
+        words = (3 * m.vertex_count + 3) & ~3  # a run, padded to 16 bytes
+        base = (self.mesh_cursor + 3) & ~3
+        zeros = np.zeros(max(n * len(attrs) * words, 4), dtype=np.uint32)
+        self._check(self.lib.r3n_mesh_buffer_write(self.ctx, 4 * base, _ffi.ptr(zeros), zeros.nbytes), "r3n_mesh_buffer_write")
+        self.mesh_cursor = base + len(zeros)
+        first = len(self.morphs)
+        for i, w in enumerate(weights_per_instance):
+            out_off = [INVALID] * 3
+            for k, a in enumerate(attrs):
+                out_off[a] = 4 * (base + (i * len(attrs) + k) * words)
+            self.morphs.append(dict(mesh=mesh, out_off=out_off, weights=self._morph_weights(m, m.morph_weights if w is None else w), objects=[]))
+            self._morph_dirty.add(first + i)
+        return list(range(first, first + n))
+
+    @staticmethod
+    def _morph_weights(m, weights):
+        w = np.ascontiguousarray(weights, dtype=f32).reshape(-1).copy()
+        if len(w) != m.n_targets:
+            raise ValueError(f"morph weights: the mesh has {m.n_targets} targets, got {len(w)} weights")
+        return w
+
+    def set_morph_weights(self, handle, weights):
+        """The instance is evaluated again in front of the next frame; the objects bound to it (directly or through a skeleton)
+        get the bounding sphere of the new weights through the dirty-object path."""
+        inst = self.morphs[handle]
+        inst["weights"] = self._morph_weights(self.meshes[inst["mesh"]], weights)
+        self._morph_dirty.add(handle)
+        self.world_version += 1
+        for h in inst["objects"]:
+            meta = self.object_meta.get(h)
+            if meta is None or meta.get("morph_instance") != handle:
+                continue  # (the handle was freed, perhaps given to another object)
+            rec = self._object_record(h)
+            meta["sphere"] = rec.view(f32)[16:20].copy()
+            self._mark(h, rec)
+
+    def morph_radius(self, handle):
+        """radius' = (((r + |w0| reach0) + |w1| reach1) + ...) over the non-zero weights in target order, f32."""
+        inst = self.morphs[handle]
+        m = self.meshes[inst["mesh"]]
+        return morph_radius(m.radius, inst["weights"], m.reach)
+
+    def _flush_morphs(self):
+        """ONE r3n_morph call for the instances never evaluated or whose weights changed; none when there are none."""
+        if not self._morph_dirty:
+            return
+        handles = sorted(self._morph_dirty)
+        inputs = np.full((len(handles), 12), INVALID, dtype=np.uint32)
+        weights, at = [], 0
+        for i, hd in enumerate(handles):
+            inst = self.morphs[hd]
+            m = self.meshes[inst["mesh"]]
+            for a in range(3):
+                if m.delta_off[a] != INVALID:
+                    inputs[i, a], inputs[i, 3 + a], inputs[i, 6 + a] = m.attr_off[a], m.delta_off[a], inst["out_off"][a]
+            inputs[i, 9:12] = (at, m.n_targets, m.vertex_count)
+            weights.append(inst["weights"])
+            at += m.n_targets
+        weights = np.ascontiguousarray(np.concatenate(weights), dtype=f32)
+        self._check(self.lib.r3n_morph(self.ctx, _ffi.ptr(inputs), len(inputs), _ffi.ptr(weights), len(weights)), "r3n_morph")
+        self._morph_dirty.clear()
 
     def set_skeleton_joint_matrices(self, sk, joint_matrices):
         self.world_version += 1  # skinned vertices may leave the bounds the partition was built from
@@ -383,7 +513,10 @@ class Renderer:
             base = 0
             for i, sk in enumerate(self.skeletons):
                 m = self.meshes[sk["mesh"]]
-                inputs[i] = [m.attr_off[0], m.attr_off[1], m.attr_off[2], m.joint_off, m.weight_off, sk["out_off"][0],
+                src = list(m.attr_off[:3])
+                if sk["morph"] is not None:  # morph, then skin: the base runs are the morph instance's outputs where it has some
+                    src = [o if o != INVALID else b for o, b in zip(self.morphs[sk["morph"]]["out_off"], src)]
+                inputs[i] = [src[0], src[1], src[2], m.joint_off, m.weight_off, sk["out_off"][0],
                              sk["out_off"][1], sk["out_off"][2], base, m.vertex_count]
                 base += len(sk["matrices"])
             self._skin_inputs = inputs
@@ -526,11 +659,16 @@ class Renderer:
         rec = np.zeros(32, dtype=np.uint32)
         rf = rec.view(f32)
         rf[0:16] = meta["transform"]
-        c, r = host.bounding_sphere_apply_transform(mesh.centre, mesh.radius, meta["transform"])
+        radius = mesh.radius if meta.get("morph_instance") is None else self.morph_radius(meta["morph_instance"])
+        c, r = host.bounding_sphere_apply_transform(mesh.centre, radius, meta["transform"])
         rf[16:19] = c
         rf[19] = r
         rec[20], rec[21], rec[22] = mesh.first_index, mesh.index_count, meta["material"]
         rec[23:29] = mesh.attr_off
+        if meta.get("morph") is not None:  # the morph instance's runs override the mesh's, as a skeleton's do
+            for a, off in enumerate(self.morphs[meta["morph"]]["out_off"]):
+                if off != INVALID:
+                    rec[23 + a] = off
         if meta.get("skeleton") is not None:  # object.rs:250-258: skeleton ranges override the mesh's
             for a, off in enumerate(self.skeletons[meta["skeleton"]]["out_off"]):
                 if off != INVALID:
@@ -553,12 +691,22 @@ class Renderer:
                                                _ffi.ptr(recs) if len(slots) else None, len(slots), self.capacity),
                     "r3n_objects_write")
 
-    def add_object(self, mesh, material, transform, skeleton=None):
+    def add_object(self, mesh, material, transform, skeleton=None, morph=None):
+        """morph: a morph instance (add_morph_instance) -- the object draws the instance's runs; with skeleton= the skeleton's
+        own morph instance (add_skeleton(..., morph=)) applies instead."""
+        if skeleton is not None and morph is not None:
+            raise ValueError("add_object: bind the morph instance to the skeleton (add_skeleton(..., morph=))")
         h = self._alloc_handle()
         if skeleton is not None:
             mesh = self.skeletons[skeleton]["mesh"]
+        elif morph is not None:
+            mesh = self.morphs[morph]["mesh"]
+        # morph_instance: the instance whose weights widen this object's bounding sphere
+        morph_instance = morph if skeleton is None else self.skeletons[skeleton]["morph"]
         self.object_meta[h] = dict(mesh=mesh, material=material, transform=np.asarray(transform, dtype=f32).copy(),
-                                   enabled=True, skeleton=skeleton)
+                                   enabled=True, skeleton=skeleton, morph=morph, morph_instance=morph_instance)
+        if morph_instance is not None:
+            self.morphs[morph_instance]["objects"].append(h)
         rec = self._object_record(h)
         self._mark(h, rec)
         # object.rs:273: a new object's sorting location is its transformed bounding-sphere centre
@@ -813,6 +961,7 @@ class Renderer:
         self._flush_textures()
         self._flush_cubes()
         self._flush_objects()
+        self._flush_morphs()  # morph, then skin (the skinning node is inside r3n_render_frame)
         cam, fr, d = fc["cam"], fc["frame"], fc["desc"]
         view, projection = self._camera_inputs
         ct.memmove(cam.view, np.ascontiguousarray(view, dtype=f32).ctypes.data, 64)
@@ -1009,10 +1158,10 @@ class Renderer:
         self._check(self.lib.r3n_set_multi_stream(self.ctx, 1 if on else 0), "r3n_set_multi_stream")
 
     def stage_times(self, reset=True):
-        ms = np.zeros(len(_ffi.STAGES), dtype=np.float64)
-        n = np.zeros(len(_ffi.STAGES), dtype=np.uint64)
+        ms = np.zeros(len(_ffi.STAGE_NAMES), dtype=np.float64)
+        n = np.zeros(len(_ffi.STAGE_NAMES), dtype=np.uint64)
         self._check(self.lib.r3n_stage_times(self.ctx, _ffi.ptr(ms), _ffi.ptr(n), 1 if reset else 0), "r3n_stage_times")
-        return {s: (float(ms[i]), int(n[i])) for i, s in enumerate(_ffi.STAGES)}
+        return {s: (float(ms[i]), int(n[i])) for i, s in enumerate(_ffi.STAGE_NAMES)}
 
     def hbm_copy_rate(self, nbytes=1 << 30, repeats=5):
         """GB/s of a float4 copy of `nbytes` on this device (read + write bytes): the measured HBM roofline denominator."""
@@ -1171,6 +1320,8 @@ class BaseRenderGraph:
                          "r3n_shadow_viewport")
 
         graph.add_node("Frame Uniforms", begin)
+        # morph targets, in front of skinning (glTF: morph first, then skin); not in the reference (rend3-gltf/src/lib.rs:761-763)
+        graph.add_node("Morph", lambda r, _ev: r._flush_morphs())
         # skinning (base.rs:145, skinning.rs:211-226)
         def skin(r, _ev):
             if r.skeletons:

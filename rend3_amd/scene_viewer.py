@@ -15,6 +15,10 @@ Square: `examples/src/scene_viewer`).  Follows (reference file:line):
 `build(renderer, host_module, material_record, settings)` works on anything with the Renderer's world-edit API -- the HIP
 renderer and, in the tests / bench.py's cpu_baseline leg, the oracle -- so a real asset runs through exactly the parity and
 measurement code the synthetic stand-ins do.  This module never imports the oracle.
+
+Morph targets need no switch: a file whose primitives have targets gets a morph instance per (node, primitive) from
+gltf.instance_scene, drawn with the file's default weights, and anim.pose_animation_frame plays its `weights` channels next to
+the node and skin channels (the reference's loader stops at a TODO there; the HIP renderer blends the targets on the GPU).
 """
 import argparse
 import os
