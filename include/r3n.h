@@ -204,6 +204,16 @@ typedef struct r3n_morph_input48 {
     uint32_t n_targets, vertex_count;
 } r3n_morph_input48;
 #define R3N_MAX_MORPH_TARGETS 256u
+/* One instance of r3n_vertex_normals, 32 B: the f32x3 position run to read (a morph instance's updated positions), the f32x3
+ * normal run to write, the mesh's index run and its adjacency words (r3n_host_vertex_adjacency).  Byte offsets into the mesh
+ * buffer, index_count in words. */
+typedef struct r3n_normals_input32 {
+    uint32_t position_offset;   /* f32x3 run to read: a morph instance's updated positions */
+    uint32_t normal_offset;     /* f32x3 run to write */
+    uint32_t index_offset, index_count;
+    uint32_t adjacency_offset;  /* r3n_host_vertex_adjacency's words */
+    uint32_t vertex_count, left_handed, _pad;
+} r3n_normals_input32;
 
 /* ---- rend3-anim (rend3-anim/src/lib.rs) tables, row N4.  A RIG is one skin: its joints in the skin's order, each with
  * its parent joint and its depth in the joint hierarchy (AnimationData::from_gltf_scene, :77-145, flattened); a CLIP is
@@ -387,6 +397,20 @@ int r3n_pose_skeletons(r3n_ctx *ctx, const r3n_pose_request16 *requests, uint32_
  * an output without a delta; weight_base + n_targets > n_weights; n_targets outside 1 .. R3N_MAX_MORPH_TARGETS;
  * an instance that morphs nothing; an output run that overlaps a base or delta run of the same instance. */
 int r3n_morph(r3n_ctx *ctx, const r3n_morph_input48 *inputs, uint32_t n_instances, const float *weights, uint32_t n_weights);
+/* Vertex normals recomputed from an instance's positions, for morphed meshes that ship without NORMAL: what
+ * Mesh::calculate_normals_for_buffers (rend3-types/src/lib.rs:662-704) gives for those positions, bit for bit (DESIGN.md section 2
+ * "Recomputed normals").  With T = floor(index_count / 3) triangles t = (i0, i1, i2) (a remainder is ignored):
+ *     e1 = p[i1] - p[i0];  e2 = p[i2] - p[i0];  n_t = left_handed ? cross(e1, e2) : cross(e2, e1)
+ *     acc = (+0, +0, +0);  for the triangles naming v, in ascending triangle number, once per occurrence: acc = fl(acc + n_t)
+ *     rcp = 1 / sqrt((x * x + y * y) + z * z);  normal[v] = rcp finite and > 0 ? acc * rcp : (+0, +0, +0)
+ * one rounding per operation, no fused multiply-add.  The order of the additions is the serial loop's, so there are no atomics: a
+ * thread per vertex gathers its triangles through the adjacency words.  ONE launch covers every instance of the call; the records
+ * go through pinned staging, the call only enqueues on the context's stream and does not wait for the GPU; it orders itself behind
+ * a resolve still in flight, as r3n_morph does.  Call it after r3n_morph and before r3n_skinning (same stream, no other
+ * synchronisation).  n_instances == 0 returns R3N_OK and launches nothing.
+ * R3N_ERR_INVALID_ARG, nothing launched: a run outside the mesh buffer or not 4-byte aligned; vertex_count == 0; the normal run
+ * overlapping the position, index or adjacency run of its record; left_handed > 1. */
+int r3n_vertex_normals(r3n_ctx *ctx, const r3n_normals_input32 *inputs, uint32_t n_instances);
 /* GpuCuller::object_uniform_upload (culler.rs:427-529) + uniform_prep.wgsl.  Called on its own it bakes every enabled slot, like
  * the reference.  Inside r3n_render_frame the bake is fused into the object pass and covers only the slots a kernel reads: those
  * inside the frustum now or (viewport) in the camera's previous frame -- the others keep what they held. */
@@ -611,7 +635,8 @@ int r3n_readback_output(r3n_ctx *ctx, uint8_t *rgba8, float *rgba_f32); /* eithe
 #define R3N_STAGE_SKYBOX 20          /* the skybox node (r3n_skybox) */
 #define R3N_STAGE_BLEND_SORT 21      /* r3n_blend_sort: the transparent pass's draw order sorted on the device */
 #define R3N_STAGE_MORPH 22           /* r3n_morph: morph targets blended into the instances' private runs */
-#define R3N_STAGE_COUNT 23
+#define R3N_STAGE_NORMALS 23         /* r3n_vertex_normals: normals of morphed meshes without NORMAL, recomputed */
+#define R3N_STAGE_COUNT 24
 int r3n_timing_enable(r3n_ctx *ctx, int enable);
 /* What a timed span holds besides its kernels -- two event packets and a launch's dispatch, measured around an empty kernel when
  * timing is first enabled (median of 32) -- and already taken off every span r3n_stage_times reports. */
@@ -662,6 +687,9 @@ void r3n_host_build_object_records(uint32_t n, const float *transforms /* 16 n *
 /* Mesh::calculate_normals_for_buffers, rend3-types/src/lib.rs:662-704 */
 void r3n_host_calculate_normals(const float *positions, uint64_t vertex_count, const uint32_t *indices,
                                 uint64_t index_count, int left_handed, float *normals);
+/* rows[0..V] then 3*floor(I/3) triangle numbers: row v = the triangles naming v, ascending, one entry per occurrence.
+ * Returns 0, or nonzero if an index is >= vertex_count (nothing usable is written then). */
+int r3n_host_vertex_adjacency(const uint32_t *indices, uint64_t index_count, uint64_t vertex_count, uint32_t *out);
 /* shadow_camera, rend3/src/managers/directional/shadow_camera.rs:6-33: outputs the shadow view matrix and its
  * orthographic projection */
 void r3n_host_shadow_camera(const float direction[3], float distance, uint32_t resolution,

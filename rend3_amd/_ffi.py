@@ -22,7 +22,7 @@ STAGES = ["bake", "object_cull", "triangle_cull", "hiz", "raster", "shade", "ton
           "raster_cut", "raster_big_cut", "skybox", "blend_sort"]
 # STAGES stays the 22 names above: tests/test_blend_sort_key.py pins its length.  Stages appended since follow in STAGE_NAMES, the
 # table r3n_stage_times fills (R3N_STAGE_COUNT entries) -- size its arrays by STAGE_NAMES, never by STAGES.
-STAGE_NAMES = STAGES + ["morph"]
+STAGE_NAMES = STAGES + ["morph", "normals"]
 
 COMM_ID_BYTES, COMM_IDS = 128, 3  # R3N_COMM_ID_BYTES, R3N_COMM_IDS
 
@@ -44,6 +44,7 @@ SIGNATURES = {
     "r3n_animation_write": (cint, [vp, vp, u32, vp, u32, vp, u32, vp, u32, vp, u32, vp, u32]),
     "r3n_pose_skeletons": (cint, [vp, vp, u32]),
     "r3n_morph": (cint, [vp, vp, u32, vp, u32]),
+    "r3n_vertex_normals": (cint, [vp, vp, u32]),
     "r3n_set_output_format": (cint, [vp, u32]),
     "r3n_set_shade_mode": (cint, [vp, u32]),
     "r3n_set_skinning_mode": (cint, [vp, u32]),
@@ -111,6 +112,7 @@ SIGNATURES = {
     "r3n_host_bounding_sphere_apply_transform": (None, [vp, cfloat, vp, vp, vp]),
     "r3n_host_build_object_records": (None, [u32, vp, vp, vp, vp, vp]),
     "r3n_host_calculate_normals": (None, [vp, u64, vp, u64, cint, vp]),
+    "r3n_host_vertex_adjacency": (cint, [vp, u64, u64, vp]),
     "r3n_host_shadow_camera": (None, [vp, cfloat, u32, vp, cint, vp, vp]),
     "r3n_host_allocate_shadow_atlas": (u32, [vp, vp, u32, u32, vp, vp]),
     "r3n_host_evaluate_frame": (cint, [vp, vp, u32, u32, vp, u32, u32, u32, u32, vp]),

@@ -251,6 +251,22 @@ void r3n_host_calculate_normals(const float *positions, uint64_t vertex_count, c
     }
 }
 
+// A stable counting sort of the 3 T (vertex, triangle) occurrences by vertex: pass 1 counts, pass 2 places in triangle order, so
+// every row comes out ascending without a sort.  out: rows[0 .. V] (entry offsets into the list), then the list.
+int r3n_host_vertex_adjacency(const uint32_t *indices, uint64_t index_count, uint64_t vertex_count, uint32_t *out) {
+    const uint64_t n = index_count - index_count % 3;
+    uint32_t *rows = out, *list = out + vertex_count + 1;
+    std::memset(rows, 0, sizeof(uint32_t) * (vertex_count + 1));
+    for (uint64_t k = 0; k < n; ++k) {
+        if (indices[k] >= vertex_count) return 1;
+        ++rows[indices[k] + 1];
+    }
+    for (uint64_t v = 0; v < vertex_count; ++v) rows[v + 1] += rows[v];
+    std::vector<uint32_t> at(rows, rows + vertex_count);
+    for (uint64_t k = 0; k < n; ++k) list[at[indices[k]]++] = (uint32_t)(k / 3);
+    return 0;
+}
+
 void r3n_host_shadow_camera(const float direction[3], float distance, uint32_t resolution,
                             const float camera_location[3], int rh, float *out_view, float *out_proj) {
     const float zero[3] = {0, 0, 0}, up[3] = {0, 1, 0};

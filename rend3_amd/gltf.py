@@ -6,7 +6,8 @@ rend3-gltf does (rend3-gltf/src/lib.rs: load_meshes :607-678, load_materials_and
 Morph targets (glTF 2.0 section 3.7.2.2) are read where the reference stops at a TODO (:761-763): a primitive's POSITION /
 NORMAL / TANGENT targets, `weights` of meshes and nodes, and `weights` animation channels (LINEAR and STEP); the blend runs
 on the GPU (Renderer.add_morph_instance, csrc/morph.hip; arithmetic in DESIGN.md section 2).  A mesh without NORMAL keeps the
-normals computed from its base shape under any weights.
+normals computed from its base shape under any weights, unless instance_scene(..., morph_normals="recompute") asks for them to be
+recomputed from the morphed positions (csrc/normals.hip).
 Not read: cameras; TEXCOORD_1 is decoded but not uploaded (no shader of the path reads it).
 """
 import json
@@ -269,15 +270,19 @@ def material_from_gltf(g, index, mk, r=None, image_cache=None, normal_y_down=Fal
 
 
 def instance_scene(g, r, hm, mk, scale=1.0, enable_directional=True, directional_light_shadow_distance=100.0,
-                   directional_light_resolution=2048, normal_y_down=False):
+                   directional_light_resolution=2048, normal_y_down=False, morph_normals="base"):
     """load_gltf + instance_loaded_scene (rend3-gltf/src/lib.rs:335-379, 493-562): node transforms in topological order
     under parent_transform = scale(s, s, -s for a left-handed renderer); one object per mesh primitive; a skeleton per
     primitive of a skinned node (joint matrices start as identity, add_mesh_by_index :411-457); winding flipped for
     left-handed renderers (load_meshes :628-634); KHR_lights_punctual directional lights become
     directional lights (GltfLoadSettings::enable_directional / directional_light_* defaults).  A primitive with morph targets
     gets one morph instance per (node, primitive), initial weights node.weights, else mesh.weights, else zeros, recorded under
-    nodes[i]["morphs"]; on a skinned node the skeleton skins from the morphed runs.  Returns dict(objects=[handles],
+    nodes[i]["morphs"]; on a skinned node the skeleton skins from the morphed runs.  morph_normals="recompute": a primitive whose
+    targets have POSITION and that has NORMAL neither itself nor in any target is added with add_mesh(morph_normals="recompute")
+    (the keyword is passed for those primitives only).  Returns dict(objects=[handles],
     skeletons=[handles], inverse_bind_matrices=[per skin], node_transforms)."""
+    if morph_normals not in ("base", "recompute"):
+        raise ValueError("morph_normals: 'base' or 'recompute'")
     nodes = g.json.get("nodes", [])
     lh = r.handedness == 0
     parent_of = {}
@@ -327,6 +332,9 @@ def instance_scene(g, r, hm, mk, scale=1.0, enable_directional=True, directional
                 morph_kw = {}
                 if p.get("targets") is not None:  # (only then: a file without targets makes the calls it always made)
                     morph_kw = dict(morph_targets=p["targets"], morph_weights=g.json["meshes"][mi].get("weights"))
+                    if (morph_normals == "recompute" and p.get("normals") is None and p["targets"]["positions"] is not None
+                            and p["targets"]["normals"] is None):
+                        morph_kw["morph_normals"] = "recompute"
                 meshes[(mi, pi)] = (r.add_mesh(p["positions"], idx, normals=p.get("normals"), tangents=p.get("tangents"),
                                                joint_indices=p.get("joints"), joint_weights=p.get("weights"),
                                                uv0=p.get("uv0"), colors=p.get("colors"), mesh_handedness=r.handedness, **morph_kw),

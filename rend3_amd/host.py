@@ -138,6 +138,16 @@ def calculate_normals(positions, indices, left_handed=True):
     return n
 
 
+def vertex_adjacency(indices, vertex_count):
+    """r3n_host_vertex_adjacency: u32[V + 1 + 3 T] = rows[0 .. V], then per vertex the triangles naming it, ascending, one entry per
+    occurrence.  Raises ValueError for an index >= vertex_count."""
+    i = np.ascontiguousarray(indices, dtype=np.uint32).reshape(-1)
+    out = np.zeros(int(vertex_count) + 1 + len(i) - len(i) % 3, dtype=np.uint32)
+    if _ffi.lib().r3n_host_vertex_adjacency(_ffi.ptr(i), len(i), int(vertex_count), _ffi.ptr(out)) != 0:
+        raise ValueError("vertex_adjacency: an index is >= vertex_count")
+    return out
+
+
 class CameraState:
     """rend3/src/managers/camera.rs:11-114."""
 

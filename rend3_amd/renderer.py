@@ -181,7 +181,7 @@ class CameraSpecifier:
 
 class _Mesh:
     __slots__ = ("attr_off", "first_index", "index_count", "centre", "radius", "vertex_count", "joint_off", "weight_off",
-                 "n_targets", "delta_off", "reach", "morph_weights")
+                 "n_targets", "delta_off", "reach", "morph_weights", "adjacency_off", "left_handed")
 
 
 class EvalOutput:
@@ -272,16 +272,30 @@ class Renderer:
 
     # ------------------------------------------------------------------ world edits
     def add_mesh(self, positions, indices=None, normals=None, colors=None, mesh_handedness=host.LEFT, tangents=None,
-                 joint_indices=None, joint_weights=None, uv0=None, morph_targets=None, morph_weights=None):
+                 joint_indices=None, joint_weights=None, uv0=None, morph_targets=None, morph_weights=None, morph_normals="base"):
         """morph_targets: glTF morph targets as dict(positions=, normals=, tangents=), each f32[T, V, 3] or None (at least one
         given; a target that lacks an attribute the others have holds zeros there).  The deltas are written once, here, behind
         the mesh's own runs: per attribute T target-major runs of 3 V words, the block 16-byte aligned.  morph_weights: the
         mesh's default weights (T floats, default zeros).  A mesh without NORMAL gets the normals add_mesh computes from the BASE
-        shape; they are not recomputed for a morphed shape (only NORMAL deltas move them)."""
+        shape.  morph_normals: "base" (default) keeps those for every morphed shape (only NORMAL deltas move normals);
+        "recompute" gives every morph instance of the mesh a private normal run that r3n_vertex_normals rewrites from the
+        instance's morphed positions whenever its weights change -- what calculate_normals gives for those positions, bit for bit
+        (DESIGN.md section 2 "Recomputed normals").  It needs normals=None, position deltas and no normal deltas (ValueError
+        otherwise); the mesh's vertex adjacency (V + 1 + 3 T words) is built once, here, and stored behind the delta block."""
+        if morph_normals not in ("base", "recompute"):
+            raise ValueError("morph_normals: 'base' or 'recompute'")
+        if morph_normals == "recompute":
+            if normals is not None:
+                raise ValueError("morph_normals='recompute': the mesh has normals of its own (normals=None)")
+            if morph_targets is None or morph_targets.get("positions") is None:
+                raise ValueError("morph_normals='recompute': the mesh needs morph targets with position deltas")
+            if morph_targets.get("normals") is not None:
+                raise ValueError("morph_normals='recompute': the targets carry normal deltas")
         positions = np.ascontiguousarray(positions, dtype=f32).reshape(-1, 3)
         if indices is None:
             indices = np.arange(len(positions), dtype=np.uint32)
         indices = np.ascontiguousarray(indices, dtype=np.uint32).reshape(-1)
+        adjacency = host.vertex_adjacency(indices, len(positions)) if morph_normals == "recompute" else None  # (refuses a bad index)
         if normals is None:  # MeshBuilder::build (rend3-types/src/lib.rs:501-504)
             normals = host.calculate_normals(positions, indices, mesh_handedness == host.LEFT)
         normals = np.ascontiguousarray(normals, dtype=f32).reshape(-1, 3)
@@ -314,6 +328,7 @@ class Renderer:
         m.first_index = push(indices)
         m.index_count = len(indices)
         m.n_targets, m.delta_off, m.reach, m.morph_weights = 0, [INVALID] * 3, None, None
+        m.adjacency_off, m.left_handed = INVALID, mesh_handedness == host.LEFT  # morph_normals="recompute"
         if morph_targets is not None:
             deltas = [morph_targets.get(k) for k in ("positions", "normals", "tangents")]
             shapes = {np.shape(d) for d in deltas if d is not None}
@@ -335,6 +350,10 @@ class Renderer:
                                else np.ascontiguousarray(morph_weights, dtype=f32).reshape(-1).copy())
             if len(m.morph_weights) != m.n_targets:
                 raise ValueError("morph_weights: one weight per target")
+            if adjacency is not None:
+                if cursor % 4:
+                    push(np.zeros(4 - cursor % 4, dtype=np.uint32))
+                m.adjacency_off = 4 * push(adjacency)
         blob = np.concatenate(chunks)
         self._check(self.lib.r3n_mesh_buffer_write(self.ctx, 4 * self.mesh_cursor, _ffi.ptr(blob), blob.nbytes),
                     "r3n_mesh_buffer_write")
@@ -399,7 +418,8 @@ class Renderer:
         if not m.n_targets:
             raise ValueError("add_morph_instance: the mesh has no morph targets")
         n = len(weights_per_instance)
-        attrs = [a for a in range(3) if m.delta_off[a] != INVALID]
+        # the attributes with a private run: those with deltas, and the normals of a morph_normals="recompute" mesh
+        attrs = [a for a in range(3) if m.delta_off[a] != INVALID or (a == 1 and m.adjacency_off != INVALID)]
         words = (3 * m.vertex_count + 3) & ~3  # a run, padded to 16 bytes
         base = (self.mesh_cursor + 3) & ~3
         zeros = np.zeros(max(n * len(attrs) * words, 4), dtype=np.uint32)
@@ -443,7 +463,8 @@ class Renderer:
         return morph_radius(m.radius, inst["weights"], m.reach)
 
     def _flush_morphs(self):
-        """ONE r3n_morph call for the instances never evaluated or whose weights changed; none when there are none."""
+        """ONE r3n_morph call for the instances never evaluated or whose weights changed, then ONE r3n_vertex_normals call for those
+        of them whose mesh recomputes its normals; none when there are none."""
         if not self._morph_dirty:
             return
         handles = sorted(self._morph_dirty)
@@ -460,6 +481,16 @@ class Renderer:
             at += m.n_targets
         weights = np.ascontiguousarray(np.concatenate(weights), dtype=f32)
         self._check(self.lib.r3n_morph(self.ctx, _ffi.ptr(inputs), len(inputs), _ffi.ptr(weights), len(weights)), "r3n_morph")
+        recs = []
+        for hd in handles:
+            inst = self.morphs[hd]
+            m = self.meshes[inst["mesh"]]
+            if m.adjacency_off != INVALID:  # r3n_normals_input32
+                recs.append((inst["out_off"][0], inst["out_off"][1], 4 * m.first_index, m.index_count, m.adjacency_off, m.vertex_count,
+                             1 if m.left_handed else 0, 0))
+        if recs:
+            recs = np.array(recs, dtype=np.uint32)
+            self._check(self.lib.r3n_vertex_normals(self.ctx, _ffi.ptr(recs), len(recs)), "r3n_vertex_normals")
         self._morph_dirty.clear()
 
     def set_skeleton_joint_matrices(self, sk, joint_matrices):

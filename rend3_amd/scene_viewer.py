@@ -19,6 +19,8 @@ measurement code the synthetic stand-ins do.  This module never imports the orac
 Morph targets need no switch: a file whose primitives have targets gets a morph instance per (node, primitive) from
 gltf.instance_scene, drawn with the file's default weights, and anim.pose_animation_frame plays its `weights` channels next to
 the node and skin channels (the reference's loader stops at a TODO there; the HIP renderer blends the targets on the GPU).
+--morph-normals recompute: primitives with targets and no NORMAL get their normals recomputed from the morphed positions on the
+GPU (default base: the normals of the bind shape, under any weights).
 """
 import argparse
 import os
@@ -78,6 +80,9 @@ def add_arguments(ap):
     ap.add_argument("--blend-sort", choices=("host", "gpu"), default="host",
                     help="where the transparent pass's back-to-front order is sorted (not in the reference, whose CPU batcher sorts): "
                          "host = every frame on the CPU, gpu = r3n_blend_sort")
+    ap.add_argument("--morph-normals", choices=("base", "recompute"), default="base",
+                    help="normals of morphed primitives without NORMAL: base = those of the bind shape under any weights, "
+                         "recompute = recomputed from the morphed positions on the GPU (r3n_vertex_normals)")
     return ap
 
 
@@ -95,7 +100,7 @@ def settings_from(args):
                 ambient=args.ambient, scale=args.scale, shadow_distance=args.shadow_distance,
                 shadow_resolution=args.shadow_resolution, enable_directional=not args.gltf_disable_directional_lights,
                 camera=args.camera or DEFAULT_CAMERA, skybox=getattr(args, "skybox", None),
-                blend_sort=getattr(args, "blend_sort", "host"))
+                blend_sort=getattr(args, "blend_sort", "host"), morph_normals=getattr(args, "morph_normals", "base"))
 
 
 def default_settings(**over):
@@ -150,9 +155,12 @@ def build(r, hm, mk, settings):
         light = r.add_directional_light(color=(1.0, 1.0, 1.0), intensity=settings["directional_light_intensity"],
                                         direction=settings["directional_light"], distance=settings["shadow_distance"], resolution=2048)
     g = gltf.Gltf(settings["file"])
+    # (passed only when asked for: a renderer whose add_mesh cannot recompute fails there, it does not fall back to base normals)
+    recompute = dict(morph_normals="recompute") if settings.get("morph_normals", "base") == "recompute" else {}
     inst = gltf.instance_scene(g, r, hm, mk, scale=settings["scale"], enable_directional=settings["enable_directional"],
                                directional_light_shadow_distance=settings["shadow_distance"],
-                               directional_light_resolution=settings["shadow_resolution"], normal_y_down=settings["normal_y_down"])
+                               directional_light_resolution=settings["shadow_resolution"], normal_y_down=settings["normal_y_down"],
+                               **recompute)
     view = camera_view(hm, settings["camera"])
     r.set_camera_data(view, PROJECTION)
     a = settings["ambient"]
