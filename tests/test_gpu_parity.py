@@ -575,6 +575,13 @@ def test_abi_error_behaviour(r3):
     slot = np.array([r.capacity], dtype=np.uint32)
     assert lib.r3n_objects_write(ctx, _ffi.ptr(slot), _ffi.ptr(rec), 1, r.capacity) == -1
     assert lib.r3n_objects_write(ctx, None, None, 0, 1) == -1
+    # Material::key() is 0 .. 2.  Beyond it the object pass's three launch plans would part (kernels_cull.h: the fused plan indexes
+    # its three per-key totals by the key, the three-launch plan tests key == 2, the chained plan key >= 2): no such key gets in
+    mrec, mslot = np.zeros((1, 52), dtype=f32), np.zeros(1, dtype=np.uint32)
+    for bad in (3, 255):
+        assert lib.r3n_materials_write(ctx, _ffi.ptr(mslot), _ffi.ptr(mrec), _ffi.ptr(np.array([bad], dtype=np.uint8)), 1) == -1
+        assert b"bad key" in lib.r3n_last_error(ctx)
+    assert lib.r3n_materials_write(ctx, _ffi.ptr(mslot), _ffi.ptr(mrec), _ffi.ptr(np.array([2], dtype=np.uint8)), 1) == 0
     # encoded textures: formats outside the built set, levels outside the payload, misaligned level 0
     payload = np.zeros(256, dtype=np.uint8)
     desc = np.array([[0, 8, 8, 1, 34, 0, 0, 0]], dtype=np.uint32)
