@@ -98,7 +98,8 @@ pub const R3N_STAGE_SKYBOX: i32 = 20;
 pub const R3N_STAGE_BLEND_SORT: i32 = 21;
 pub const R3N_STAGE_MORPH: i32 = 22;
 pub const R3N_STAGE_NORMALS: i32 = 23;
-pub const R3N_STAGE_COUNT: i32 = 24;
+pub const R3N_STAGE_TANGENTS: i32 = 24;
+pub const R3N_STAGE_COUNT: i32 = 25;
 
 #[repr(C)]
 pub struct r3n_ctx {
@@ -234,6 +235,19 @@ pub struct r3n_normals_input32 {
     pub vertex_count: u32,
     pub left_handed: u32,
     pub _pad: u32,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct r3n_tangents_input32 {
+    pub position_offset: u32,
+    pub normal_offset: u32,
+    pub uv_offset: u32,
+    pub tangent_offset: u32,
+    pub index_offset: u32,
+    pub index_count: u32,
+    pub adjacency_offset: u32,
+    pub vertex_count: u32,
 }
 
 #[repr(C)]
@@ -400,6 +414,7 @@ extern "C" {
     pub fn r3n_pose_skeletons(ctx: *mut r3n_ctx, requests: *const r3n_pose_request16, n: u32) -> c_int;
     pub fn r3n_morph(ctx: *mut r3n_ctx, inputs: *const r3n_morph_input48, n_instances: u32, weights: *const f32, n_weights: u32) -> c_int;
     pub fn r3n_vertex_normals(ctx: *mut r3n_ctx, inputs: *const r3n_normals_input32, n_instances: u32) -> c_int;
+    pub fn r3n_vertex_tangents(ctx: *mut r3n_ctx, inputs: *const r3n_tangents_input32, n_instances: u32) -> c_int;
     pub fn r3n_uniform_bake(ctx: *mut r3n_ctx, camera: u32, header: *const r3n_camera_header240) -> c_int;
     pub fn r3n_cull(ctx: *mut r3n_ctx, camera: u32) -> c_int;
     pub fn r3n_hi_z(ctx: *mut r3n_ctx) -> c_int;
@@ -458,6 +473,7 @@ extern "C" {
     pub fn r3n_host_bounding_sphere_apply_transform(center: *const f32, radius: f32, m: *const f32, out_center: *mut f32, out_radius: *mut f32);
     pub fn r3n_host_build_object_records(n: u32, transforms: *const f32, mesh_desc: *const f32, mesh_u32: *const u32, material_index: *const u32, out_records: *mut r3n_object128);
     pub fn r3n_host_calculate_normals(positions: *const f32, vertex_count: u64, indices: *const u32, index_count: u64, left_handed: c_int, normals: *mut f32);
+    pub fn r3n_host_calculate_tangents(positions: *const f32, normals: *const f32, uvs: *const f32, vertex_count: u64, indices: *const u32, index_count: u64, tangents: *mut f32);
     pub fn r3n_host_vertex_adjacency(indices: *const u32, index_count: u64, vertex_count: u64, out: *mut u32) -> c_int;
     pub fn r3n_host_shadow_camera(direction: *const f32, distance: f32, resolution: u32, camera_location: *const f32, rh: c_int, out_view: *mut f32, out_proj: *mut f32);
     pub fn r3n_host_allocate_shadow_atlas(handles: *const u32, resolutions: *const u16, n: u32, max_dimension: u32, out_dimensions: *mut u32, out_maps: *mut u32) -> u32;

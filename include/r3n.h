@@ -214,6 +214,16 @@ typedef struct r3n_normals_input32 {
     uint32_t adjacency_offset;  /* r3n_host_vertex_adjacency's words */
     uint32_t vertex_count, left_handed, _pad;
 } r3n_normals_input32;
+/* One instance of r3n_vertex_tangents, 32 B: the runs to READ -- the instance's current f32x3 positions and normals and the mesh's
+ * f32x2 uv0 -- the f32x3 tangent run to WRITE, the mesh's index run and its adjacency words (r3n_host_vertex_adjacency).  Byte
+ * offsets into the mesh buffer, index_count in words. */
+typedef struct r3n_tangents_input32 {
+    uint32_t position_offset, normal_offset, uv_offset; /* runs to read */
+    uint32_t tangent_offset;                            /* f32x3 run to write */
+    uint32_t index_offset, index_count;
+    uint32_t adjacency_offset;                          /* r3n_host_vertex_adjacency's words */
+    uint32_t vertex_count;
+} r3n_tangents_input32;
 
 /* ---- rend3-anim (rend3-anim/src/lib.rs) tables, row N4.  A RIG is one skin: its joints in the skin's order, each with
  * its parent joint and its depth in the joint hierarchy (AnimationData::from_gltf_scene, :77-145, flattened); a CLIP is
@@ -411,6 +421,25 @@ int r3n_morph(r3n_ctx *ctx, const r3n_morph_input48 *inputs, uint32_t n_instance
  * R3N_ERR_INVALID_ARG, nothing launched: a run outside the mesh buffer or not 4-byte aligned; vertex_count == 0; the normal run
  * overlapping the position, index or adjacency run of its record; left_handed > 1. */
 int r3n_vertex_normals(r3n_ctx *ctx, const r3n_normals_input32 *inputs, uint32_t n_instances);
+/* Vertex tangents generated from an instance's positions, normals and the mesh's uv0, for morphed meshes that ship without TANGENT:
+ * what Mesh::calculate_tangents_for_buffers (rend3-types/src/lib.rs:784-837, zeroed = true, glam's scalar Vec3) gives for those
+ * runs, bit for bit (DESIGN.md section 2 "Generated tangents").  With T = floor(index_count / 3) triangles t = (i0, i1, i2) (a
+ * remainder is ignored):
+ *     e1 = p[i1] - p[i0];  e2 = p[i2] - p[i0];  a = uv[i1] - uv[i0];  b = uv[i2] - uv[i0]
+ *     r = 1 / (a.x * b.y - a.y * b.x);  g_t = e1 * b.y - (e2 * a.y) * r          per component; r multiplies the second product only
+ *     acc = (+0, +0, +0);  for the triangles naming v, in ascending triangle number, once per occurrence: acc = fl(acc + g_t)
+ *     d = (n.x * acc.x + n.y * acc.y) + n.z * acc.z;  q = acc - n * d            n = normal[v] as stored, not re-normalised
+ *     rcp = 1 / sqrt((q.x * q.x + q.y * q.y) + q.z * q.z);  tangent[v] = rcp finite and > 0 ? q * rcp : (+0, +0, +0)
+ * one rounding per operation, no fused multiply-add.  A triangle with a degenerate uv footprint (every triangle that names a vertex
+ * twice is one) has r = +-inf; its term is inf or NaN and every vertex it names ends as (+0, +0, +0).  No output word is NaN or inf;
+ * handedness plays no part.  The order of the additions is the serial loop's, so there are no atomics: a thread per vertex gathers
+ * its triangles through the adjacency words.  ONE launch covers every instance of the call; the records go through pinned staging,
+ * the call only enqueues on the context's stream and does not wait for the GPU; it orders itself behind a resolve still in flight.
+ * Call order inside a frame: r3n_morph -> r3n_vertex_normals -> r3n_vertex_tangents -> r3n_skinning (same stream, no other
+ * synchronisation).  n_instances == 0 returns R3N_OK and launches nothing.
+ * R3N_ERR_INVALID_ARG, nothing launched: a run outside the mesh buffer or not 4-byte aligned; vertex_count == 0; the tangent run
+ * overlapping the position, normal, uv, index or adjacency run of its record. */
+int r3n_vertex_tangents(r3n_ctx *ctx, const r3n_tangents_input32 *inputs, uint32_t n_instances);
 /* GpuCuller::object_uniform_upload (culler.rs:427-529) + uniform_prep.wgsl.  Called on its own it bakes every enabled slot, like
  * the reference.  Inside r3n_render_frame the bake is fused into the object pass and covers only the slots a kernel reads: those
  * inside the frustum now or (viewport) in the camera's previous frame -- the others keep what they held. */
@@ -636,7 +665,8 @@ int r3n_readback_output(r3n_ctx *ctx, uint8_t *rgba8, float *rgba_f32); /* eithe
 #define R3N_STAGE_BLEND_SORT 21      /* r3n_blend_sort: the transparent pass's draw order sorted on the device */
 #define R3N_STAGE_MORPH 22           /* r3n_morph: morph targets blended into the instances' private runs */
 #define R3N_STAGE_NORMALS 23         /* r3n_vertex_normals: normals of morphed meshes without NORMAL, recomputed */
-#define R3N_STAGE_COUNT 24
+#define R3N_STAGE_TANGENTS 24        /* r3n_vertex_tangents: tangents of morphed meshes without TANGENT, generated */
+#define R3N_STAGE_COUNT 25
 int r3n_timing_enable(r3n_ctx *ctx, int enable);
 /* What a timed span holds besides its kernels -- two event packets and a launch's dispatch, measured around an empty kernel when
  * timing is first enabled (median of 32) -- and already taken off every span r3n_stage_times reports. */
@@ -687,6 +717,10 @@ void r3n_host_build_object_records(uint32_t n, const float *transforms /* 16 n *
 /* Mesh::calculate_normals_for_buffers, rend3-types/src/lib.rs:662-704 */
 void r3n_host_calculate_normals(const float *positions, uint64_t vertex_count, const uint32_t *indices,
                                 uint64_t index_count, int left_handed, float *normals);
+/* Mesh::calculate_tangents_for_buffers, rend3-types/src/lib.rs:784-837 (zeroed = true): the serial loop whose words
+ * r3n_vertex_tangents reproduces (contract there).  uvs: vertex_count f32x2; tangents: vertex_count f32x3, written. */
+void r3n_host_calculate_tangents(const float *positions, const float *normals, const float *uvs, uint64_t vertex_count,
+                                 const uint32_t *indices, uint64_t index_count, float *tangents);
 /* rows[0..V] then 3*floor(I/3) triangle numbers: row v = the triangles naming v, ascending, one entry per occurrence.
  * Returns 0, or nonzero if an index is >= vertex_count (nothing usable is written then). */
 int r3n_host_vertex_adjacency(const uint32_t *indices, uint64_t index_count, uint64_t vertex_count, uint32_t *out);

@@ -20,9 +20,12 @@ KEY_OPAQUE, KEY_CUTOUT, KEY_BLEND = 0, 1, 2
 STAGES = ["bake", "object_cull", "triangle_cull", "hiz", "raster", "shade", "tonemap", "clear", "raster_big",
           "shadow_raster", "shadow_raster_big", "skinning", "vertex", "pose", "exchange_shadow", "exchange_depth", "exchange_rows", "exchange_keys",
           "raster_cut", "raster_big_cut", "skybox", "blend_sort"]
-# STAGES stays the 22 names above: tests/test_blend_sort_key.py pins its length.  Stages appended since follow in STAGE_NAMES, the
-# table r3n_stage_times fills (R3N_STAGE_COUNT entries) -- size its arrays by STAGE_NAMES, never by STAGES.
+# STAGES stays the 22 names above: tests/test_blend_sort_key.py pins its length.  Stages appended since follow in STAGE_NAMES
+# and STAGE_TABLE.
 STAGE_NAMES = STAGES + ["morph", "normals"]
+# STAGE_NAMES stays the 24 names above in its turn: tests/test_normals.py pins its tail.  STAGE_TABLE is the whole table
+# (R3N_STAGE_COUNT entries): size the arrays handed to r3n_stage_times by it.
+STAGE_TABLE = STAGE_NAMES + ["tangents"]
 
 COMM_ID_BYTES, COMM_IDS = 128, 3  # R3N_COMM_ID_BYTES, R3N_COMM_IDS
 
@@ -45,6 +48,7 @@ SIGNATURES = {
     "r3n_pose_skeletons": (cint, [vp, vp, u32]),
     "r3n_morph": (cint, [vp, vp, u32, vp, u32]),
     "r3n_vertex_normals": (cint, [vp, vp, u32]),
+    "r3n_vertex_tangents": (cint, [vp, vp, u32]),
     "r3n_set_output_format": (cint, [vp, u32]),
     "r3n_set_shade_mode": (cint, [vp, u32]),
     "r3n_set_skinning_mode": (cint, [vp, u32]),
@@ -112,6 +116,7 @@ SIGNATURES = {
     "r3n_host_bounding_sphere_apply_transform": (None, [vp, cfloat, vp, vp, vp]),
     "r3n_host_build_object_records": (None, [u32, vp, vp, vp, vp, vp]),
     "r3n_host_calculate_normals": (None, [vp, u64, vp, u64, cint, vp]),
+    "r3n_host_calculate_tangents": (None, [vp, vp, vp, u64, vp, u64, vp]),
     "r3n_host_vertex_adjacency": (cint, [vp, u64, u64, vp]),
     "r3n_host_shadow_camera": (None, [vp, cfloat, u32, vp, cint, vp, vp]),
     "r3n_host_allocate_shadow_atlas": (u32, [vp, vp, u32, u32, vp, vp]),

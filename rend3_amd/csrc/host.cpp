@@ -251,6 +251,36 @@ void r3n_host_calculate_normals(const float *positions, uint64_t vertex_count, c
     }
 }
 
+// Mesh::calculate_tangents_for_buffers, rend3-types/src/lib.rs:784-837 (zeroed = true): glam's scalar Vec3, every operation rounded
+// once (this file is built with -ffp-contract=off).  `r` multiplies the second product only, as Rust's precedence has it on :825.
+void r3n_host_calculate_tangents(const float *positions, const float *normals, const float *uvs, uint64_t vertex_count,
+                                 const uint32_t *indices, uint64_t index_count, float *tangents) {
+    std::memset(tangents, 0, sizeof(float) * 3 * vertex_count);
+    for (uint64_t t = 0; t + 2 < index_count; t += 3) {
+        const uint64_t i0 = indices[t], i1 = indices[t + 1], i2 = indices[t + 2];
+        const float *p1 = positions + 3 * i0, *p2 = positions + 3 * i1, *p3 = positions + 3 * i2;
+        const float *t1 = uvs + 2 * i0, *t2 = uvs + 2 * i1, *t3 = uvs + 2 * i2;
+        const float uv1[2] = {t2[0] - t1[0], t2[1] - t1[1]}, uv2[2] = {t3[0] - t1[0], t3[1] - t1[1]};
+        const float r = 1.0f / (uv1[0] * uv2[1] - uv1[1] * uv2[0]);
+        float g[3];
+        for (int c = 0; c < 3; ++c) {
+            const float e1 = p2[c] - p1[c], e2 = p3[c] - p1[c];
+            g[c] = e1 * uv2[1] - (e2 * uv1[1]) * r;
+        }
+        for (int k = 0; k < 3; ++k)
+            for (int c = 0; c < 3; ++c) tangents[3 * (uint64_t)indices[t + k] + c] += g[c];
+    }
+    for (uint64_t i = 0; i < vertex_count; ++i) {
+        float *a = tangents + 3 * i;
+        const float *n = normals + 3 * i;
+        const float d = dot3(n, a);
+        const float q[3] = {a[0] - n[0] * d, a[1] - n[1] * d, a[2] - n[2] * d};
+        const float rcp = 1.0f / std::sqrt(dot3(q, q));  // glam normalize_or_zero
+        if (std::isfinite(rcp) && rcp > 0.0f) { a[0] = q[0] * rcp; a[1] = q[1] * rcp; a[2] = q[2] * rcp; }
+        else { a[0] = a[1] = a[2] = 0.0f; }
+    }
+}
+
 // A stable counting sort of the 3 T (vertex, triangle) occurrences by vertex: pass 1 counts, pass 2 places in triangle order, so
 // every row comes out ascending without a sort.  out: rows[0 .. V] (entry offsets into the list), then the list.
 int r3n_host_vertex_adjacency(const uint32_t *indices, uint64_t index_count, uint64_t vertex_count, uint32_t *out) {

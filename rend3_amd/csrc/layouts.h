@@ -24,6 +24,7 @@ static_assert(sizeof(r3n_frame_uniforms496) == 496, "FrameUniforms must be 496 B
 static_assert(sizeof(r3n_indirect_call) == 20, "IndirectCall must be 20 B");
 static_assert(sizeof(r3n_morph_input48) == 48 && offsetof(r3n_morph_input48, weight_base) == 36, "morph instance record must be 48 B");
 static_assert(sizeof(r3n_normals_input32) == 32 && offsetof(r3n_normals_input32, adjacency_offset) == 16, "normals instance record must be 32 B");
+static_assert(sizeof(r3n_tangents_input32) == 32 && offsetof(r3n_tangents_input32, index_offset) == 16, "tangents instance record must be 32 B");
 // the one-call frame boundary (r3n_render_frame / r3n_host_evaluate_frame): sizes the ctypes / Rust mirrors repeat
 static_assert(sizeof(r3n_shadow_view272) == 272, "shadow view = 240-byte header + viewport");
 static_assert(sizeof(r3n_frame_desc) == 152 && offsetof(r3n_frame_desc, uniforms) == 48 && offsetof(r3n_frame_desc, exchange) == 136, "r3n_frame_desc layout");

@@ -23,6 +23,7 @@
 #include "blend_sort.h"
 #include "morph.h"
 #include "normals.h"
+#include "tangents.h"
 
 namespace {
 
@@ -185,6 +186,8 @@ struct r3n_ctx {
     DevBuf morph_block;
     // recomputed normals (normals.h): the records and wave map of ONE r3n_vertex_normals call, one block behind one staged copy
     DevBuf normals_block;
+    // generated tangents (tangents.h): the same, of ONE r3n_vertex_tangents call
+    DevBuf tangents_block;
     uint32_t slot_table_size = 0;
     CamState canon;  // scratch camera used to (re)build the canonical tri_base scan
     // frame targets
@@ -401,7 +404,7 @@ int check_async_status(r3n_ctx *c) {
 
 static const char *const kStageNames[R3N_STAGE_COUNT] = {"bake", "object_cull", "triangle_cull", "hiz", "raster", "shade", "tonemap", "clear",
     "raster_big", "shadow_raster", "shadow_raster_big", "skinning", "vertex", "pose", "exchange_shadow", "exchange_depth",
-    "exchange_rows", "exchange_keys", "raster_cut", "raster_big_cut", "skybox", "blend_sort", "morph", "normals"};
+    "exchange_rows", "exchange_keys", "raster_cut", "raster_big_cut", "skybox", "blend_sort", "morph", "normals", "tangents"};
 static void crumb(const r3n_ctx *c, const char *what, long long a, long long b) {
     if (c->crumb_fd < 0) return;
     char line[160];
@@ -948,7 +951,7 @@ void r3n_destroy(r3n_ctx *c) {
     }
     DevBuf *bufs[] = {&c->mesh, &c->objects, &c->spheres, &c->obj_meta, &c->materials, &c->material_keys, &c->fb_dev[0], &c->fb_dev[1], &c->big_count_all, &c->owners,
                       &c->tri_base, &c->slot_table, &c->skin_inputs, &c->skin_matrices, &c->skin_wave_skeleton,
-                      &c->skin_wave_first, &c->skin_joint_counts, &c->morph_block, &c->normals_block, &c->vis, &c->hdr16, &c->out8, &c->out_f32, &c->atlas, &c->hiz, &c->alt_vis, &c->alt_atlas, &c->alt_vp_baked, &c->srgb_lut, &c->srgb_thr, &c->tex_descs, &c->tex_texels, &c->tex_level_off, &c->srgb8_decode,
+                      &c->skin_wave_first, &c->skin_joint_counts, &c->morph_block, &c->normals_block, &c->tangents_block, &c->vis, &c->hdr16, &c->out8, &c->out_f32, &c->atlas, &c->hiz, &c->alt_vis, &c->alt_atlas, &c->alt_vp_baked, &c->srgb_lut, &c->srgb_thr, &c->tex_descs, &c->tex_texels, &c->tex_level_off, &c->srgb8_decode,
                       &c->tri_rec, &c->tri_seen, &c->blend_order, &c->blend_rank_base, &c->frag_keys, &c->frag_vals, &c->frag_head,
                       &c->frag_count, &c->samples16, &c->anim_rigs, &c->anim_joints, &c->anim_clips, &c->anim_tracks,
                       &c->anim_times, &c->anim_values, &c->pose_requests, &c->edge_list, &c->edge_count, &c->material_feat, &c->view_lights[0],
@@ -1608,6 +1611,59 @@ int r3n_vertex_normals(r3n_ctx *c, const r3n_normals_input32 *inputs, uint32_t n
     ++c->main_epoch;  // the shadow lanes read the mesh buffer
     Timed t(c, R3N_STAGE_NORMALS);
     HIP_TRY(c, (hipError_t)r3n_internal_vertex_normals(&a, c->stream));
+    return R3N_OK;
+}
+
+// Tangents of morphed meshes without TANGENT (tangents.h / tangents.hip): r3n_vertex_normals' shape, with two more runs to read.
+int r3n_vertex_tangents(r3n_ctx *c, const r3n_tangents_input32 *inputs, uint32_t n) {
+    if (!c) return R3N_ERR_INVALID_ARG;
+    if (n == 0) return R3N_OK;
+    if (!inputs) return fail(c, R3N_ERR_INVALID_ARG, "tangents: null inputs");
+    const uint64_t mesh_words = c->mesh.bytes / 4;
+    uint64_t total_waves = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        const r3n_tangents_input32 &in = inputs[i];
+        if (in.vertex_count == 0u) return fail(c, R3N_ERR_INVALID_ARG, "tangents: an instance without vertices");
+        const uint64_t run = (uint64_t)in.vertex_count * 3u, tri_words = in.index_count - in.index_count % 3u;
+        // (first word, words) of the six ranges the kernel touches: positions, normals, uvs, indices, adjacency; tangents
+        const uint64_t read[5][2] = {{in.position_offset / 4u, run}, {in.normal_offset / 4u, run}, {in.uv_offset / 4u, (uint64_t)in.vertex_count * 2u},
+                                     {in.index_offset / 4u, in.index_count}, {in.adjacency_offset / 4u, (uint64_t)in.vertex_count + 1u + tri_words}};
+        const uint64_t out[2] = {in.tangent_offset / 4u, run};
+        if (((in.position_offset | in.normal_offset | in.uv_offset | in.tangent_offset | in.index_offset | in.adjacency_offset) & 3u) != 0u ||
+            out[0] + out[1] > mesh_words)
+            return fail(c, R3N_ERR_INVALID_ARG, "tangents: run outside the mesh buffer or not 4-byte aligned");
+        for (const auto &r : read) {
+            if (r[0] + r[1] > mesh_words) return fail(c, R3N_ERR_INVALID_ARG, "tangents: run outside the mesh buffer or not 4-byte aligned");
+            if (r[1] && out[0] < r[0] + r[1] && r[0] < out[0] + out[1])
+                return fail(c, R3N_ERR_INVALID_ARG, "tangents: the tangent run overlaps a run its instance reads");
+        }
+        total_waves += r3n_tangents_waves(in.vertex_count);
+    }
+    if (total_waves > 0x7FFFFFFFull) return fail(c, R3N_ERR_UNSUPPORTED, "tangents: more than 2^31 wave slots in one call");
+    HIP_TRY(c, hipSetDevice(c->device));
+    TRY(join_shade(c));  // frames in flight: the previous frame's resolve reads the runs this rewrites
+    // block layout, in words: records | wave_first | wave_instance
+    const size_t o_first = (size_t)n * 8u, o_inst = o_first + n;
+    std::vector<uint32_t> block(o_inst + total_waves);
+    std::memcpy(block.data(), inputs, (size_t)n * sizeof *inputs);
+    uint32_t w = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        block[o_first + i] = w;
+        const uint32_t nw = r3n_tangents_waves(inputs[i].vertex_count);
+        std::fill(block.begin() + o_inst + w, block.begin() + o_inst + w + nw, i);
+        w += nw;
+    }
+    TRY(ensure(c, c->tangents_block, block.size() * 4, false, -1));
+    TRY(upload_bulk(c, c->tangents_block.p, block.data(), block.size() * 4));  // pinned staging: no wait for the GPU
+    TangentsArgs a{};
+    a.mesh = c->mesh.as<uint32_t>();
+    a.recs = c->tangents_block.as<r3n_tangents_input32>();
+    a.wave_first = c->tangents_block.as<uint32_t>() + o_first;
+    a.wave_instance = c->tangents_block.as<uint32_t>() + o_inst;
+    a.total_waves = w;
+    ++c->main_epoch;  // the shadow lanes read the mesh buffer
+    Timed t(c, R3N_STAGE_TANGENTS);
+    HIP_TRY(c, (hipError_t)r3n_internal_vertex_tangents(&a, c->stream));
     return R3N_OK;
 }
 

@@ -270,7 +270,8 @@ def material_from_gltf(g, index, mk, r=None, image_cache=None, normal_y_down=Fal
 
 
 def instance_scene(g, r, hm, mk, scale=1.0, enable_directional=True, directional_light_shadow_distance=100.0,
-                   directional_light_resolution=2048, normal_y_down=False, morph_normals="base"):
+                   directional_light_resolution=2048, normal_y_down=False, morph_normals="base",
+                   build_tangents=False, morph_tangents="base"):
     """load_gltf + instance_loaded_scene (rend3-gltf/src/lib.rs:335-379, 493-562): node transforms in topological order
     under parent_transform = scale(s, s, -s for a left-handed renderer); one object per mesh primitive; a skeleton per
     primitive of a skinned node (joint matrices start as identity, add_mesh_by_index :411-457); winding flipped for
@@ -279,10 +280,15 @@ def instance_scene(g, r, hm, mk, scale=1.0, enable_directional=True, directional
     gets one morph instance per (node, primitive), initial weights node.weights, else mesh.weights, else zeros, recorded under
     nodes[i]["morphs"]; on a skinned node the skeleton skins from the morphed runs.  morph_normals="recompute": a primitive whose
     targets have POSITION and that has NORMAL neither itself nor in any target is added with add_mesh(morph_normals="recompute")
-    (the keyword is passed for those primitives only).  Returns dict(objects=[handles],
+    (the keyword is passed for those primitives only).  build_tangents=True: a primitive with TEXCOORD_0 and without TANGENT is
+    added with add_mesh(build_tangents=True), which is what rend3-gltf's MeshBuilder does for every primitive (the default, False,
+    keeps such a primitive without tangents until the oracle follows); morph_tangents="recompute" is passed on, with it, for those of
+    them whose targets have POSITION and no TANGENT.  Returns dict(objects=[handles],
     skeletons=[handles], inverse_bind_matrices=[per skin], node_transforms)."""
     if morph_normals not in ("base", "recompute"):
         raise ValueError("morph_normals: 'base' or 'recompute'")
+    if morph_tangents not in ("base", "recompute"):
+        raise ValueError("morph_tangents: 'base' or 'recompute'")
     nodes = g.json.get("nodes", [])
     lh = r.handedness == 0
     parent_of = {}
@@ -335,9 +341,15 @@ def instance_scene(g, r, hm, mk, scale=1.0, enable_directional=True, directional
                     if (morph_normals == "recompute" and p.get("normals") is None and p["targets"]["positions"] is not None
                             and p["targets"]["normals"] is None):
                         morph_kw["morph_normals"] = "recompute"
+                tangent_kw = {}
+                if build_tangents and p.get("uv0") is not None and p.get("tangents") is None:
+                    tangent_kw["build_tangents"] = True
+                    if (morph_tangents == "recompute" and morph_kw and p["targets"]["positions"] is not None
+                            and p["targets"]["tangents"] is None):
+                        tangent_kw["morph_tangents"] = "recompute"
                 meshes[(mi, pi)] = (r.add_mesh(p["positions"], idx, normals=p.get("normals"), tangents=p.get("tangents"),
                                                joint_indices=p.get("joints"), joint_weights=p.get("weights"),
-                                               uv0=p.get("uv0"), colors=p.get("colors"), mesh_handedness=r.handedness, **morph_kw),
+                                               uv0=p.get("uv0"), colors=p.get("colors"), mesh_handedness=r.handedness, **morph_kw, **tangent_kw),
                                     p["material"], bool(morph_kw))
             mesh, mat_index, has_targets = meshes[(mi, pi)]
             morph = None

@@ -138,6 +138,20 @@ def calculate_normals(positions, indices, left_handed=True):
     return n
 
 
+def calculate_tangents(positions, normals, uv0, indices):
+    """Mesh::calculate_tangents_for_buffers (rend3-types/src/lib.rs:784-837): f32[V, 3], the tangents MeshBuilder::build generates
+    for a mesh with NORMAL and TEXCOORD_0 and without TANGENT (DESIGN.md section 2 "Generated tangents")."""
+    p = np.ascontiguousarray(positions, dtype=np.float32).reshape(-1, 3)
+    n = np.ascontiguousarray(normals, dtype=np.float32).reshape(-1, 3)
+    uv = np.ascontiguousarray(uv0, dtype=np.float32).reshape(-1, 2)
+    i = np.ascontiguousarray(indices, dtype=np.uint32).reshape(-1)
+    if len(n) != len(p) or len(uv) != len(p):
+        raise ValueError("calculate_tangents: one normal and one uv per position")
+    out = np.zeros_like(p)
+    _ffi.lib().r3n_host_calculate_tangents(_ffi.ptr(p), _ffi.ptr(n), _ffi.ptr(uv), len(p), _ffi.ptr(i), len(i), _ffi.ptr(out))
+    return out
+
+
 def vertex_adjacency(indices, vertex_count):
     """r3n_host_vertex_adjacency: u32[V + 1 + 3 T] = rows[0 .. V], then per vertex the triangles naming it, ascending, one entry per
     occurrence.  Raises ValueError for an index >= vertex_count."""

@@ -181,7 +181,7 @@ class CameraSpecifier:
 
 class _Mesh:
     __slots__ = ("attr_off", "first_index", "index_count", "centre", "radius", "vertex_count", "joint_off", "weight_off",
-                 "n_targets", "delta_off", "reach", "morph_weights", "adjacency_off", "left_handed")
+                 "n_targets", "delta_off", "reach", "morph_weights", "adjacency_off", "left_handed", "morph_normals", "morph_tangents")
 
 
 class EvalOutput:
@@ -272,7 +272,8 @@ class Renderer:
 
     # ------------------------------------------------------------------ world edits
     def add_mesh(self, positions, indices=None, normals=None, colors=None, mesh_handedness=host.LEFT, tangents=None,
-                 joint_indices=None, joint_weights=None, uv0=None, morph_targets=None, morph_weights=None, morph_normals="base"):
+                 joint_indices=None, joint_weights=None, uv0=None, morph_targets=None, morph_weights=None, morph_normals="base",
+                 build_tangents=False, morph_tangents="base"):
         """morph_targets: glTF morph targets as dict(positions=, normals=, tangents=), each f32[T, V, 3] or None (at least one
         given; a target that lacks an attribute the others have holds zeros there).  The deltas are written once, here, behind
         the mesh's own runs: per attribute T target-major runs of 3 V words, the block 16-byte aligned.  morph_weights: the
@@ -281,7 +282,16 @@ class Renderer:
         "recompute" gives every morph instance of the mesh a private normal run that r3n_vertex_normals rewrites from the
         instance's morphed positions whenever its weights change -- what calculate_normals gives for those positions, bit for bit
         (DESIGN.md section 2 "Recomputed normals").  It needs normals=None, position deltas and no normal deltas (ValueError
-        otherwise); the mesh's vertex adjacency (V + 1 + 3 T words) is built once, here, and stored behind the delta block."""
+        otherwise); the mesh's vertex adjacency (V + 1 + 3 T words) is built once, here, and stored behind the delta block.
+        build_tangents: True is MeshBuilder::build's second half (rend3-types/src/lib.rs:505-509): a mesh with uv0 and without
+        tangents gets the tangents calculate_tangents generates from its positions, normals (given or just computed) and uv0,
+        over the same index run, as attribute 2 (DESIGN.md section 2 "Generated tangents").  With tangents given or without uv0
+        it does nothing, as in the reference.  False (default) leaves such a mesh without a tangent run, as before; True is the
+        reference's behaviour and becomes the default together with the oracle.  morph_tangents: "base" (default) lets the
+        tangents of the bind shape serve every weight; "recompute" gives every morph instance a private tangent run that
+        r3n_vertex_tangents rewrites from the instance's current positions and normals whenever its weights change.  It needs
+        build_tangents=True, tangents=None, uv0, position deltas and no tangent deltas (ValueError otherwise) and shares the
+        adjacency with morph_normals="recompute"."""
         if morph_normals not in ("base", "recompute"):
             raise ValueError("morph_normals: 'base' or 'recompute'")
         if morph_normals == "recompute":
@@ -291,14 +301,30 @@ class Renderer:
                 raise ValueError("morph_normals='recompute': the mesh needs morph targets with position deltas")
             if morph_targets.get("normals") is not None:
                 raise ValueError("morph_normals='recompute': the targets carry normal deltas")
+        if morph_tangents not in ("base", "recompute"):
+            raise ValueError("morph_tangents: 'base' or 'recompute'")
+        if morph_tangents == "recompute":
+            if not build_tangents:
+                raise ValueError("morph_tangents='recompute': the mesh's tangents are not generated (build_tangents=True)")
+            if tangents is not None:
+                raise ValueError("morph_tangents='recompute': the mesh has tangents of its own (tangents=None)")
+            if uv0 is None:
+                raise ValueError("morph_tangents='recompute': the mesh needs uv0")
+            if morph_targets is None or morph_targets.get("positions") is None:
+                raise ValueError("morph_tangents='recompute': the mesh needs morph targets with position deltas")
+            if morph_targets.get("tangents") is not None:
+                raise ValueError("morph_tangents='recompute': the targets carry tangent deltas")
         positions = np.ascontiguousarray(positions, dtype=f32).reshape(-1, 3)
         if indices is None:
             indices = np.arange(len(positions), dtype=np.uint32)
         indices = np.ascontiguousarray(indices, dtype=np.uint32).reshape(-1)
-        adjacency = host.vertex_adjacency(indices, len(positions)) if morph_normals == "recompute" else None  # (refuses a bad index)
+        # (refuses a bad index; built once, shared by the two recomputing kernels)
+        adjacency = host.vertex_adjacency(indices, len(positions)) if "recompute" in (morph_normals, morph_tangents) else None
         if normals is None:  # MeshBuilder::build (rend3-types/src/lib.rs:501-504)
             normals = host.calculate_normals(positions, indices, mesh_handedness == host.LEFT)
         normals = np.ascontiguousarray(normals, dtype=f32).reshape(-1, 3)
+        if build_tangents and tangents is None and uv0 is not None:  # MeshBuilder::build (rend3-types/src/lib.rs:505-509)
+            tangents = host.calculate_tangents(positions, normals, uv0, indices)
         m = _Mesh()
         m.attr_off = [INVALID] * 6
         chunks = []
@@ -328,7 +354,8 @@ class Renderer:
         m.first_index = push(indices)
         m.index_count = len(indices)
         m.n_targets, m.delta_off, m.reach, m.morph_weights = 0, [INVALID] * 3, None, None
-        m.adjacency_off, m.left_handed = INVALID, mesh_handedness == host.LEFT  # morph_normals="recompute"
+        m.adjacency_off, m.left_handed = INVALID, mesh_handedness == host.LEFT  # morph_normals / morph_tangents = "recompute"
+        m.morph_normals, m.morph_tangents = morph_normals == "recompute", morph_tangents == "recompute"
         if morph_targets is not None:
             deltas = [morph_targets.get(k) for k in ("positions", "normals", "tangents")]
             shapes = {np.shape(d) for d in deltas if d is not None}
@@ -418,8 +445,9 @@ class Renderer:
         if not m.n_targets:
             raise ValueError("add_morph_instance: the mesh has no morph targets")
         n = len(weights_per_instance)
-        # the attributes with a private run: those with deltas, and the normals of a morph_normals="recompute" mesh
-        attrs = [a for a in range(3) if m.delta_off[a] != INVALID or (a == 1 and m.adjacency_off != INVALID)]
+        # the attributes with a private run: those with deltas, the normals of a morph_normals="recompute" mesh and the tangents of a
+        # morph_tangents="recompute" one
+        attrs = [a for a in range(3) if m.delta_off[a] != INVALID or (a == 1 and m.morph_normals) or (a == 2 and m.morph_tangents)]
         words = (3 * m.vertex_count + 3) & ~3  # a run, padded to 16 bytes
         base = (self.mesh_cursor + 3) & ~3
         zeros = np.zeros(max(n * len(attrs) * words, 4), dtype=np.uint32)
@@ -464,7 +492,8 @@ class Renderer:
 
     def _flush_morphs(self):
         """ONE r3n_morph call for the instances never evaluated or whose weights changed, then ONE r3n_vertex_normals call for those
-        of them whose mesh recomputes its normals; none when there are none."""
+        of them whose mesh recomputes its normals, then ONE r3n_vertex_tangents call for those whose mesh recomputes its tangents;
+        none when there are none."""
         if not self._morph_dirty:
             return
         handles = sorted(self._morph_dirty)
@@ -485,12 +514,23 @@ class Renderer:
         for hd in handles:
             inst = self.morphs[hd]
             m = self.meshes[inst["mesh"]]
-            if m.adjacency_off != INVALID:  # r3n_normals_input32
+            if m.morph_normals:  # r3n_normals_input32
                 recs.append((inst["out_off"][0], inst["out_off"][1], 4 * m.first_index, m.index_count, m.adjacency_off, m.vertex_count,
                              1 if m.left_handed else 0, 0))
         if recs:
             recs = np.array(recs, dtype=np.uint32)
             self._check(self.lib.r3n_vertex_normals(self.ctx, _ffi.ptr(recs), len(recs)), "r3n_vertex_normals")
+        recs = []
+        for hd in handles:
+            inst = self.morphs[hd]
+            m = self.meshes[inst["mesh"]]
+            if m.morph_tangents:  # r3n_tangents_input32: the instance's current positions and normals, the mesh's uv0
+                out = inst["out_off"]
+                recs.append((out[0], out[1] if out[1] != INVALID else m.attr_off[1], m.attr_off[3], out[2], 4 * m.first_index,
+                             m.index_count, m.adjacency_off, m.vertex_count))
+        if recs:
+            recs = np.array(recs, dtype=np.uint32)
+            self._check(self.lib.r3n_vertex_tangents(self.ctx, _ffi.ptr(recs), len(recs)), "r3n_vertex_tangents")
         self._morph_dirty.clear()
 
     def set_skeleton_joint_matrices(self, sk, joint_matrices):
@@ -1189,10 +1229,10 @@ class Renderer:
         self._check(self.lib.r3n_set_multi_stream(self.ctx, 1 if on else 0), "r3n_set_multi_stream")
 
     def stage_times(self, reset=True):
-        ms = np.zeros(len(_ffi.STAGE_NAMES), dtype=np.float64)
-        n = np.zeros(len(_ffi.STAGE_NAMES), dtype=np.uint64)
+        ms = np.zeros(len(_ffi.STAGE_TABLE), dtype=np.float64)
+        n = np.zeros(len(_ffi.STAGE_TABLE), dtype=np.uint64)
         self._check(self.lib.r3n_stage_times(self.ctx, _ffi.ptr(ms), _ffi.ptr(n), 1 if reset else 0), "r3n_stage_times")
-        return {s: (float(ms[i]), int(n[i])) for i, s in enumerate(_ffi.STAGE_NAMES)}
+        return {s: (float(ms[i]), int(n[i])) for i, s in enumerate(_ffi.STAGE_TABLE)}
 
     def hbm_copy_rate(self, nbytes=1 << 30, repeats=5):
         """GB/s of a float4 copy of `nbytes` on this device (read + write bytes): the measured HBM roofline denominator."""

@@ -21,6 +21,9 @@ gltf.instance_scene, drawn with the file's default weights, and anim.pose_animat
 the node and skin channels (the reference's loader stops at a TODO there; the HIP renderer blends the targets on the GPU).
 --morph-normals recompute: primitives with targets and no NORMAL get their normals recomputed from the morphed positions on the
 GPU (default base: the normals of the bind shape, under any weights).
+--build-tangents: primitives with TEXCOORD_0 and no TANGENT get the tangents rend3's MeshBuilder generates (the reference always
+does; here it is opt-in until the oracle follows).  --morph-tangents recompute: with it, morphed primitives get those tangents
+regenerated from the morphed positions and normals on the GPU (default base: the tangents of the bind shape).
 """
 import argparse
 import os
@@ -83,6 +86,11 @@ def add_arguments(ap):
     ap.add_argument("--morph-normals", choices=("base", "recompute"), default="base",
                     help="normals of morphed primitives without NORMAL: base = those of the bind shape under any weights, "
                          "recompute = recomputed from the morphed positions on the GPU (r3n_vertex_normals)")
+    ap.add_argument("--build-tangents", action="store_true",
+                    help="generate the tangents of primitives with TEXCOORD_0 and no TANGENT, as the reference's MeshBuilder does")
+    ap.add_argument("--morph-tangents", choices=("base", "recompute"), default="base",
+                    help="generated tangents of morphed primitives: base = those of the bind shape under any weights, "
+                         "recompute = regenerated from the morphed positions and normals on the GPU (r3n_vertex_tangents)")
     return ap
 
 
@@ -100,7 +108,8 @@ def settings_from(args):
                 ambient=args.ambient, scale=args.scale, shadow_distance=args.shadow_distance,
                 shadow_resolution=args.shadow_resolution, enable_directional=not args.gltf_disable_directional_lights,
                 camera=args.camera or DEFAULT_CAMERA, skybox=getattr(args, "skybox", None),
-                blend_sort=getattr(args, "blend_sort", "host"), morph_normals=getattr(args, "morph_normals", "base"))
+                blend_sort=getattr(args, "blend_sort", "host"), morph_normals=getattr(args, "morph_normals", "base"),
+                build_tangents=getattr(args, "build_tangents", False), morph_tangents=getattr(args, "morph_tangents", "base"))
 
 
 def default_settings(**over):
@@ -157,6 +166,10 @@ def build(r, hm, mk, settings):
     g = gltf.Gltf(settings["file"])
     # (passed only when asked for: a renderer whose add_mesh cannot recompute fails there, it does not fall back to base normals)
     recompute = dict(morph_normals="recompute") if settings.get("morph_normals", "base") == "recompute" else {}
+    if settings.get("build_tangents", False):
+        recompute["build_tangents"] = True
+    if settings.get("morph_tangents", "base") == "recompute":
+        recompute["morph_tangents"] = "recompute"
     inst = gltf.instance_scene(g, r, hm, mk, scale=settings["scale"], enable_directional=settings["enable_directional"],
                                directional_light_shadow_distance=settings["shadow_distance"],
                                directional_light_resolution=settings["shadow_resolution"], normal_y_down=settings["normal_y_down"],

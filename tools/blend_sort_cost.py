@@ -60,7 +60,7 @@ def measure(lib, n, repeats, warmup, lines):
     ok(lib.r3n_blend_objects_write(ctx, _ffi.ptr(slots), _ffi.ptr(loc), n), "r3n_blend_objects_write")
     upload_us = 1e6 * (time.perf_counter() - t0)
     ok(lib.r3n_sync(ctx), "r3n_sync")
-    ms, launches = np.zeros(len(_ffi.STAGE_NAMES)), np.zeros(len(_ffi.STAGE_NAMES), dtype=np.uint64)
+    ms, launches = np.zeros(len(_ffi.STAGE_TABLE)), np.zeros(len(_ffi.STAGE_TABLE), dtype=np.uint64)
     stage = _ffi.STAGES.index("blend_sort")
     # (c) the call on the host, taps off
     call_us = []
