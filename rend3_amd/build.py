@@ -21,16 +21,17 @@ SO = os.path.join(HERE, "librend3_amd.so")
 COMMON = ["layouts.h", "device_math.h", "../../include/r3n.h"]
 # translation unit -> the headers it includes (besides COMMON)
 UNITS = {
-    "r3n.hip": ["texture.h", "kernels_cull.h", "kernels_raster.h", "kernels_shade.h", "comm.h", "skybox.h", "blend_sort.h", "morph.h", "normals.h", "tangents.h"],
+    "r3n.hip": ["texture.h", "kernels_cull.h", "kernels_raster.h", "kernels_shade.h", "comm.h", "skybox.h", "blend_sort.h", "morph.h", "normals.h", "tangents.h",
+                "vertex_block.h", "vertex_gather.h", "exact_math.h"],
     "shade.hip": ["texture.h", "kernels_shade.h"],
     "shade_cls.hip": ["texture.h", "kernels_shade.h"],
     "shade_ms.hip": ["texture.h", "kernels_shade.h"],
     "shade_blend.hip": ["texture.h", "kernels_shade.h"],
     "skybox.hip": ["texture.h", "kernels_shade.h", "skybox.h"],
     "blend_sort.hip": ["blend_sort.h"],
-    "morph.hip": ["morph.h"],
-    "normals.hip": ["normals.h", "exact_math.h"],
-    "tangents.hip": ["tangents.h", "exact_math.h"],
+    "morph.hip": ["morph.h", "vertex_gather.h", "exact_math.h"],
+    "normals.hip": ["normals.h", "vertex_gather.h", "exact_math.h"],
+    "tangents.hip": ["tangents.h", "vertex_gather.h", "exact_math.h"],
     "texture_decode.hip": ["bc7_tables.h", "bc6h_tables.h"],
     "anim.hip": [],
     "selftest.hip": ["exact_math.h"],

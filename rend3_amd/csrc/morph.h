@@ -7,10 +7,8 @@
 // (+0 and -0; NaN is one): r3n_morph compacts the (target, weight) pairs that are terms on the host, so all-zero weights copy the
 // base run bit for bit and a skipped target costs no bytes.  There is no per-vertex structure: a run is 3 * vertex_count words.
 #pragma once
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
 #include "../../include/r3n.h"
+#include "vertex_gather.h"
 
 #define R3N_MORPH_WAVE_WORDS 256u  // words of every morphed run one wave covers: 64 lanes x 4 words (one dwordx4 each)
 
@@ -28,19 +26,9 @@ struct r3n_morph_pair {
     float weight;
 };
 
-struct MorphArgs {
-    uint32_t *mesh;
-    const r3n_morph_rec64 *recs;
+struct MorphArgs : vertex_gather::Args<r3n_morph_rec64> {
     const r3n_morph_pair *pairs;
-    const uint32_t *wave_instance;  // total_waves: the instance of every wave slot
-    const uint32_t *wave_first;     // per instance: its first wave slot
-    uint32_t total_waves;
 };
-
-// waves an instance of `vertex_count` vertices takes
-static inline uint32_t r3n_morph_waves(uint32_t vertex_count) {
-    return (uint32_t)(((uint64_t)vertex_count * 3u + R3N_MORPH_WAVE_WORDS - 1u) / R3N_MORPH_WAVE_WORDS);
-}
 
 // enqueues the ONE launch on `stream`; returns the hipError_t of the launch
 extern "C" int r3n_internal_morph(const MorphArgs *a, hipStream_t stream);

@@ -1,10 +1,10 @@
 // morph.hip -- glTF morph targets: out = base + sum of weight * delta over the instance's non-zero weights, for the private
 // POSITION / NORMAL / TANGENT runs of every instance of one r3n_morph call, in ONE launch.  Contract and terms: morph.h.
 //
-// The operation is element-wise per f32 word, so a run is a flat array of 3 * vertex_count words.  Wave slot w belongs to instance
-// wave_instance[w] (the map k_skinning uses) and covers words [256 * (w - wave_first[instance]), +256) of each of the instance's
-// morphed runs: lane l holds words 4 l .. 4 l + 3.  The 64-byte record and the (target, weight) terms are wave-uniform and come
-// through scalar registers; the loop over the terms has the same trip count in every lane.
+// The operation is element-wise per f32 word, so a run is a flat array of 3 * vertex_count words.  A wave slot (wave map:
+// vertex_gather.h) covers 256 words of each of its instance's morphed runs: lane l holds words 4 l .. 4 l + 3.  The 64-byte record
+// and the (target, weight) terms are wave-uniform and come through scalar registers; the loop over the terms has the same trip
+// count in every lane.
 //
 // Access width: a lane's four words are moved as one dwordx4 where the run's byte offset is a multiple of 16 (the delta and output
 // runs the renderer allocates; a target's run inside the delta block only when 12 * vertex_count is one too), as four dword
@@ -86,13 +86,11 @@ MORPH_DEV void blend_run(uint32_t *__restrict__ mesh, uint32_t base_off, uint32_
 __global__ __launch_bounds__(256) void k_morph(uint32_t *__restrict__ mesh, const r3n_morph_rec64 *__restrict__ recs,
                                                const r3n_morph_pair *__restrict__ pairs, const uint32_t *__restrict__ wave_instance,
                                                const uint32_t *__restrict__ wave_first, uint32_t total_waves) {
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t w = __builtin_amdgcn_readfirstlane(blockIdx.x * 4u + (threadIdx.x >> 6));
+    const uint32_t w = vertex_gather::wave_index();
     if (w >= total_waves) return;
-    const uint32_t inst = __builtin_amdgcn_readfirstlane(wave_instance[w]);
-    const r3n_morph_rec64 rec = recs[inst];
+    uint32_t i;
+    const r3n_morph_rec64 rec = vertex_gather::wave_record(w, recs, wave_instance, wave_first, R3N_MORPH_WAVE_WORDS, i);
     const uint32_t n_words = rec.in.vertex_count * 3u;
-    const uint32_t i = (w - __builtin_amdgcn_readfirstlane(wave_first[inst])) * R3N_MORPH_WAVE_WORDS + lane * 4u;
     if (i >= n_words) return;
     const r3n_morph_pair *terms = pairs + rec.pair_first;
     if (rec.in.delta_position_offset != 0xFFFFFFFFu)

@@ -12,25 +12,12 @@
 // Adjacency (r3n_host_vertex_adjacency, host.cpp), vertex_count + 1 + 3 T words: rows[0 .. V], then the triangle numbers; row v =
 // entries [rows[v], rows[v + 1]) of the list, the triangles naming v, ascending, one entry per occurrence.
 #pragma once
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
 #include "../../include/r3n.h"
+#include "vertex_gather.h"
 
 #define R3N_NORMALS_WAVE_VERTICES 64u  // one thread per vertex
 
-struct NormalsArgs {
-    uint32_t *mesh;
-    const r3n_normals_input32 *recs;  // 8 words each: one s_load_dwordx8
-    const uint32_t *wave_instance;    // total_waves: the instance of every wave slot
-    const uint32_t *wave_first;       // per instance: its first wave slot
-    uint32_t total_waves;
-};
-
-// waves an instance of `vertex_count` vertices takes
-static inline uint32_t r3n_normals_waves(uint32_t vertex_count) {
-    return (uint32_t)(((uint64_t)vertex_count + R3N_NORMALS_WAVE_VERTICES - 1u) / R3N_NORMALS_WAVE_VERTICES);
-}
+using NormalsArgs = vertex_gather::Args<r3n_normals_input32>;  // 8 words each: one s_load_dwordx8
 
 // enqueues the ONE launch on `stream`; returns the hipError_t of the launch
 extern "C" int r3n_internal_vertex_normals(const NormalsArgs *a, hipStream_t stream);

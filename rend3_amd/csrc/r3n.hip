@@ -24,6 +24,7 @@
 #include "morph.h"
 #include "normals.h"
 #include "tangents.h"
+#include "vertex_block.h"
 
 namespace {
 
@@ -401,6 +402,21 @@ int check_async_status(r3n_ctx *c) {
         int _r = (expr);               \
         if (_r != R3N_OK) return _r;   \
     } while (0)
+
+// A vertex stage's host block (vertex_block.h) into the stage's own buffer -- ONE copy through pinned staging, no wait for the GPU --
+// and the device pointers into it.
+template <class Rec>
+int stage_wave_block(r3n_ctx *c, DevBuf &buf, const std::vector<uint32_t> &block, const vertex_block::layout &l, uint64_t total_waves,
+                     vertex_gather::Args<Rec> &a) {
+    TRY(ensure(c, buf, block.size() * 4, false, -1));
+    TRY(upload_bulk(c, buf.p, block.data(), block.size() * 4));
+    a.mesh = c->mesh.as<uint32_t>();
+    a.recs = buf.as<Rec>();
+    a.wave_first = buf.as<uint32_t>() + l.o_first;
+    a.wave_instance = buf.as<uint32_t>() + l.o_inst;
+    a.total_waves = (uint32_t)total_waves;
+    return R3N_OK;
+}
 
 static const char *const kStageNames[R3N_STAGE_COUNT] = {"bake", "object_cull", "triangle_cull", "hiz", "raster", "shade", "tonemap", "clear",
     "raster_big", "shadow_raster", "shadow_raster_big", "skinning", "vertex", "pose", "exchange_shadow", "exchange_depth",
@@ -1415,7 +1431,7 @@ int r3n_skinning(r3n_ctx *c, const r3n_skinning_input40 *inputs, uint32_t n, con
                                      {in.updated_normal_offset, 3}, {in.updated_tangent_offset, 3}, {R3N_INVALID, 0}};
         for (const auto &run : runs) {
             if (run[0] == R3N_INVALID) continue;
-            if ((run[0] & 3u) != 0u || (uint64_t)run[0] / 4 + (uint64_t)in.vertex_count * run[1] > mesh_words)
+            if (!vertex_block::aligned4(run[0]) || !vertex_block::inside(vertex_block::words_at(run[0], (uint64_t)in.vertex_count * run[1]), mesh_words))
                 return fail(c, R3N_ERR_INVALID_ARG, "skinning: attribute range outside the mesh buffer");
         }
         if (in.joint_matrix_base_offset >= n_joints) return fail(c, R3N_ERR_INVALID_ARG, "skinning: joint matrix base out of range");
@@ -1428,7 +1444,7 @@ int r3n_skinning(r3n_ctx *c, const r3n_skinning_input40 *inputs, uint32_t n, con
         uint32_t w = 0;
         for (uint32_t i = 0; i < n; ++i) {
             wave_first[i] = w;
-            const uint32_t nw = (inputs[i].vertex_count + 63u) / 64u;
+            const uint32_t nw = (uint32_t)vertex_block::waves(inputs[i].vertex_count, 64u);
             wave_skel.insert(wave_skel.end(), nw, i);
             w += nw;
         }
@@ -1481,10 +1497,11 @@ int r3n_skinning(r3n_ctx *c, const r3n_skinning_input40 *inputs, uint32_t n, con
     return check_launch(c, "k_skinning");
 }
 
-// glTF morph targets (morph.h / morph.hip).  Everything the kernel reads besides the mesh buffer -- instance records, the
-// (target, weight) terms with the zero weights dropped, the wave -> instance map -- is laid out in ONE host block and staged with
-// ONE copy: the instance set differs from call to call, so nothing is cached and nothing waits for the GPU.
+// glTF morph targets (morph.h / morph.hip).  Everything the kernel reads besides the mesh buffer -- instance records, the wave ->
+// instance map, the (target, weight) terms with the zero weights dropped -- is laid out in ONE host block (vertex_block.h) and
+// staged with ONE copy: the instance set differs from call to call, so nothing is cached and nothing waits for the GPU.
 int r3n_morph(r3n_ctx *c, const r3n_morph_input48 *inputs, uint32_t n, const float *weights, uint32_t n_weights) {
+    using namespace vertex_block;
     if (!c) return R3N_ERR_INVALID_ARG;
     if (n == 0) return R3N_OK;
     if (!inputs || !weights) return fail(c, R3N_ERR_INVALID_ARG, "morph: null inputs");
@@ -1507,26 +1524,26 @@ int r3n_morph(r3n_ctx *c, const r3n_morph_input48 *inputs, uint32_t n, const flo
                 continue;
             }
             if (base[a] == R3N_INVALID || out[a] == R3N_INVALID) return fail(c, R3N_ERR_INVALID_ARG, "morph: deltas without their base or output run");
-            // (first word, words) of the three ranges the kernel touches for this attribute
-            const uint64_t rb[2] = {base[a] / 4u, run}, rd[2] = {delta[a] / 4u, run * in.n_targets}, ro[2] = {out[a] / 4u, run};
-            if (((base[a] | delta[a] | out[a]) & 3u) != 0u || rb[0] + rb[1] > mesh_words || rd[0] + rd[1] > mesh_words || ro[0] + ro[1] > mesh_words)
+            // the three ranges the kernel touches for this attribute
+            const range rb = words_at(base[a], run), rd = words_at(delta[a], run * in.n_targets), ro = words_at(out[a], run);
+            if (!aligned4(base[a] | delta[a] | out[a]) || !inside(rb, mesh_words) || !inside(rd, mesh_words) || !inside(ro, mesh_words))
                 return fail(c, R3N_ERR_INVALID_ARG, "morph: attribute range outside the mesh buffer");
-            if (run && ((ro[0] < rb[0] + rb[1] && rb[0] < ro[0] + ro[1]) || (ro[0] < rd[0] + rd[1] && rd[0] < ro[0] + ro[1])))
+            if (overlaps(ro, rb) || overlaps(ro, rd))
                 return fail(c, R3N_ERR_INVALID_ARG, "morph: an output run overlaps a base or delta run of its instance");
             ++morphed;
         }
         if (!morphed) return fail(c, R3N_ERR_INVALID_ARG, "morph: an instance without deltas");
-        total_waves += r3n_morph_waves(in.vertex_count);
+        total_waves += waves(run, R3N_MORPH_WAVE_WORDS);
         for (uint32_t t = 0; t < in.n_targets; ++t) total_terms += weights[in.weight_base + t] == 0.0f ? 0u : 1u;
     }
-    if (total_waves > 0x7FFFFFFFull) return fail(c, R3N_ERR_UNSUPPORTED, "morph: more than 2^31 wave slots in one call");
+    if (total_waves > MAX_WAVES) return fail(c, R3N_ERR_UNSUPPORTED, "morph: more than 2^31 wave slots in one call");
     HIP_TRY(c, hipSetDevice(c->device));
     TRY(join_shade(c));  // frames in flight: the previous frame's resolve reads the runs this rewrites
     if (total_waves == 0) return R3N_OK;  // (instances of zero vertices)
-    // block layout, in words: records | wave_first | wave_instance | terms
-    const size_t o_first = (size_t)n * 16u, o_inst = o_first + n, o_terms = (o_inst + total_waves + 1u) & ~(size_t)1u;
-    std::vector<uint32_t> block(o_terms + 2u * (size_t)total_terms);
-    uint32_t w = 0, term = 0;
+    std::vector<uint32_t> block;
+    const layout l = lay_out(block, n, sizeof(r3n_morph_rec64) / 4, total_waves,
+                             [&](uint32_t i) { return waves((uint64_t)inputs[i].vertex_count * 3u, R3N_MORPH_WAVE_WORDS); }, 2u * (size_t)total_terms);
+    uint32_t term = 0;
     for (uint32_t i = 0; i < n; ++i) {
         r3n_morph_rec64 rec{};
         rec.in = inputs[i];
@@ -1534,26 +1551,16 @@ int r3n_morph(r3n_ctx *c, const r3n_morph_input48 *inputs, uint32_t n, const flo
         for (uint32_t t = 0; t < rec.in.n_targets; ++t) {
             const float wt = weights[rec.in.weight_base + t];
             if (wt == 0.0f) continue;  // part of the contract: +0 and -0 are no terms, NaN is one
-            block[o_terms + 2u * (size_t)term] = t;
-            std::memcpy(&block[o_terms + 2u * (size_t)term + 1u], &wt, 4);
+            block[l.o_tail + 2u * (size_t)term] = t;
+            std::memcpy(&block[l.o_tail + 2u * (size_t)term + 1u], &wt, 4);
             ++term;
         }
         rec.n_active = term - rec.pair_first;
         std::memcpy(&block[(size_t)i * 16u], &rec, sizeof rec);
-        block[o_first + i] = w;
-        const uint32_t nw = r3n_morph_waves(rec.in.vertex_count);
-        std::fill(block.begin() + o_inst + w, block.begin() + o_inst + w + nw, i);
-        w += nw;
     }
-    TRY(ensure(c, c->morph_block, block.size() * 4, false, -1));
-    TRY(upload_bulk(c, c->morph_block.p, block.data(), block.size() * 4));  // pinned staging: no wait for the GPU
     MorphArgs a{};
-    a.mesh = c->mesh.as<uint32_t>();
-    a.recs = c->morph_block.as<r3n_morph_rec64>();
-    a.wave_first = c->morph_block.as<uint32_t>() + o_first;
-    a.wave_instance = c->morph_block.as<uint32_t>() + o_inst;
-    a.pairs = reinterpret_cast<const r3n_morph_pair *>(c->morph_block.as<uint32_t>() + o_terms);
-    a.total_waves = w;
+    TRY(stage_wave_block(c, c->morph_block, block, l, total_waves, a));
+    a.pairs = reinterpret_cast<const r3n_morph_pair *>(c->morph_block.as<uint32_t>() + l.o_tail);
     ++c->main_epoch;  // the shadow lanes read the morphed attribute runs
     Timed t(c, R3N_STAGE_MORPH);
     HIP_TRY(c, (hipError_t)r3n_internal_morph(&a, c->stream));
@@ -1563,6 +1570,7 @@ int r3n_morph(r3n_ctx *c, const r3n_morph_input48 *inputs, uint32_t n, const flo
 // Normals of morphed meshes without NORMAL (normals.h / normals.hip).  As in r3n_morph, everything the kernel reads besides the mesh
 // buffer -- the records and the wave -> instance map -- is ONE host block behind ONE staged copy; nothing waits for the GPU.
 int r3n_vertex_normals(r3n_ctx *c, const r3n_normals_input32 *inputs, uint32_t n) {
+    using namespace vertex_block;
     if (!c) return R3N_ERR_INVALID_ARG;
     if (n == 0) return R3N_OK;
     if (!inputs) return fail(c, R3N_ERR_INVALID_ARG, "normals: null inputs");
@@ -1573,49 +1581,36 @@ int r3n_vertex_normals(r3n_ctx *c, const r3n_normals_input32 *inputs, uint32_t n
         if (in.vertex_count == 0u) return fail(c, R3N_ERR_INVALID_ARG, "normals: an instance without vertices");
         if (in.left_handed > 1u) return fail(c, R3N_ERR_INVALID_ARG, "normals: left_handed is 0 or 1");
         const uint64_t run = (uint64_t)in.vertex_count * 3u, tri_words = in.index_count - in.index_count % 3u;
-        // (first word, words) of the four ranges the kernel touches: positions, indices, adjacency; normals
-        const uint64_t read[3][2] = {{in.position_offset / 4u, run}, {in.index_offset / 4u, in.index_count},
-                                     {in.adjacency_offset / 4u, (uint64_t)in.vertex_count + 1u + tri_words}};
-        const uint64_t out[2] = {in.normal_offset / 4u, run};
-        if (((in.position_offset | in.normal_offset | in.index_offset | in.adjacency_offset) & 3u) != 0u || out[0] + out[1] > mesh_words)
+        // the four ranges the kernel touches: positions, indices, adjacency; normals
+        const range read[3] = {words_at(in.position_offset, run), words_at(in.index_offset, in.index_count),
+                               words_at(in.adjacency_offset, (uint64_t)in.vertex_count + 1u + tri_words)};
+        const range out = words_at(in.normal_offset, run);
+        if (!aligned4(in.position_offset | in.normal_offset | in.index_offset | in.adjacency_offset) || !inside(out, mesh_words))
             return fail(c, R3N_ERR_INVALID_ARG, "normals: run outside the mesh buffer or not 4-byte aligned");
-        for (const auto &r : read) {
-            if (r[0] + r[1] > mesh_words) return fail(c, R3N_ERR_INVALID_ARG, "normals: run outside the mesh buffer or not 4-byte aligned");
-            if (r[1] && out[0] < r[0] + r[1] && r[0] < out[0] + out[1])
+        for (const range &r : read) {
+            if (!inside(r, mesh_words)) return fail(c, R3N_ERR_INVALID_ARG, "normals: run outside the mesh buffer or not 4-byte aligned");
+            if (overlaps(out, r))
                 return fail(c, R3N_ERR_INVALID_ARG, "normals: the normal run overlaps the position, index or adjacency run of its instance");
         }
-        total_waves += r3n_normals_waves(in.vertex_count);
+        total_waves += waves(in.vertex_count, R3N_NORMALS_WAVE_VERTICES);
     }
-    if (total_waves > 0x7FFFFFFFull) return fail(c, R3N_ERR_UNSUPPORTED, "normals: more than 2^31 wave slots in one call");
+    if (total_waves > MAX_WAVES) return fail(c, R3N_ERR_UNSUPPORTED, "normals: more than 2^31 wave slots in one call");
     HIP_TRY(c, hipSetDevice(c->device));
     TRY(join_shade(c));  // frames in flight: the previous frame's resolve reads the runs this rewrites
-    // block layout, in words: records | wave_first | wave_instance
-    const size_t o_first = (size_t)n * 8u, o_inst = o_first + n;
-    std::vector<uint32_t> block(o_inst + total_waves);
+    std::vector<uint32_t> block;
+    const layout l = lay_out(block, n, sizeof *inputs / 4, total_waves, [&](uint32_t i) { return waves(inputs[i].vertex_count, R3N_NORMALS_WAVE_VERTICES); });
     std::memcpy(block.data(), inputs, (size_t)n * sizeof *inputs);
-    uint32_t w = 0;
-    for (uint32_t i = 0; i < n; ++i) {
-        block[o_first + i] = w;
-        const uint32_t nw = r3n_normals_waves(inputs[i].vertex_count);
-        std::fill(block.begin() + o_inst + w, block.begin() + o_inst + w + nw, i);
-        w += nw;
-    }
-    TRY(ensure(c, c->normals_block, block.size() * 4, false, -1));
-    TRY(upload_bulk(c, c->normals_block.p, block.data(), block.size() * 4));  // pinned staging: no wait for the GPU
     NormalsArgs a{};
-    a.mesh = c->mesh.as<uint32_t>();
-    a.recs = c->normals_block.as<r3n_normals_input32>();
-    a.wave_first = c->normals_block.as<uint32_t>() + o_first;
-    a.wave_instance = c->normals_block.as<uint32_t>() + o_inst;
-    a.total_waves = w;
+    TRY(stage_wave_block(c, c->normals_block, block, l, total_waves, a));
     ++c->main_epoch;  // the shadow lanes read the mesh buffer
     Timed t(c, R3N_STAGE_NORMALS);
     HIP_TRY(c, (hipError_t)r3n_internal_vertex_normals(&a, c->stream));
     return R3N_OK;
 }
 
-// Tangents of morphed meshes without TANGENT (tangents.h / tangents.hip): r3n_vertex_normals' shape, with two more runs to read.
+// Tangents of morphed meshes without TANGENT (tangents.h / tangents.hip): r3n_vertex_normals' steps, with two more runs to read.
 int r3n_vertex_tangents(r3n_ctx *c, const r3n_tangents_input32 *inputs, uint32_t n) {
+    using namespace vertex_block;
     if (!c) return R3N_ERR_INVALID_ARG;
     if (n == 0) return R3N_OK;
     if (!inputs) return fail(c, R3N_ERR_INVALID_ARG, "tangents: null inputs");
@@ -1625,42 +1620,27 @@ int r3n_vertex_tangents(r3n_ctx *c, const r3n_tangents_input32 *inputs, uint32_t
         const r3n_tangents_input32 &in = inputs[i];
         if (in.vertex_count == 0u) return fail(c, R3N_ERR_INVALID_ARG, "tangents: an instance without vertices");
         const uint64_t run = (uint64_t)in.vertex_count * 3u, tri_words = in.index_count - in.index_count % 3u;
-        // (first word, words) of the six ranges the kernel touches: positions, normals, uvs, indices, adjacency; tangents
-        const uint64_t read[5][2] = {{in.position_offset / 4u, run}, {in.normal_offset / 4u, run}, {in.uv_offset / 4u, (uint64_t)in.vertex_count * 2u},
-                                     {in.index_offset / 4u, in.index_count}, {in.adjacency_offset / 4u, (uint64_t)in.vertex_count + 1u + tri_words}};
-        const uint64_t out[2] = {in.tangent_offset / 4u, run};
-        if (((in.position_offset | in.normal_offset | in.uv_offset | in.tangent_offset | in.index_offset | in.adjacency_offset) & 3u) != 0u ||
-            out[0] + out[1] > mesh_words)
+        // the six ranges the kernel touches: positions, normals, uvs, indices, adjacency; tangents
+        const range read[5] = {words_at(in.position_offset, run), words_at(in.normal_offset, run), words_at(in.uv_offset, (uint64_t)in.vertex_count * 2u),
+                               words_at(in.index_offset, in.index_count), words_at(in.adjacency_offset, (uint64_t)in.vertex_count + 1u + tri_words)};
+        const range out = words_at(in.tangent_offset, run);
+        if (!aligned4(in.position_offset | in.normal_offset | in.uv_offset | in.tangent_offset | in.index_offset | in.adjacency_offset) ||
+            !inside(out, mesh_words))
             return fail(c, R3N_ERR_INVALID_ARG, "tangents: run outside the mesh buffer or not 4-byte aligned");
-        for (const auto &r : read) {
-            if (r[0] + r[1] > mesh_words) return fail(c, R3N_ERR_INVALID_ARG, "tangents: run outside the mesh buffer or not 4-byte aligned");
-            if (r[1] && out[0] < r[0] + r[1] && r[0] < out[0] + out[1])
-                return fail(c, R3N_ERR_INVALID_ARG, "tangents: the tangent run overlaps a run its instance reads");
+        for (const range &r : read) {
+            if (!inside(r, mesh_words)) return fail(c, R3N_ERR_INVALID_ARG, "tangents: run outside the mesh buffer or not 4-byte aligned");
+            if (overlaps(out, r)) return fail(c, R3N_ERR_INVALID_ARG, "tangents: the tangent run overlaps a run its instance reads");
         }
-        total_waves += r3n_tangents_waves(in.vertex_count);
+        total_waves += waves(in.vertex_count, R3N_TANGENTS_WAVE_VERTICES);
     }
-    if (total_waves > 0x7FFFFFFFull) return fail(c, R3N_ERR_UNSUPPORTED, "tangents: more than 2^31 wave slots in one call");
+    if (total_waves > MAX_WAVES) return fail(c, R3N_ERR_UNSUPPORTED, "tangents: more than 2^31 wave slots in one call");
     HIP_TRY(c, hipSetDevice(c->device));
     TRY(join_shade(c));  // frames in flight: the previous frame's resolve reads the runs this rewrites
-    // block layout, in words: records | wave_first | wave_instance
-    const size_t o_first = (size_t)n * 8u, o_inst = o_first + n;
-    std::vector<uint32_t> block(o_inst + total_waves);
+    std::vector<uint32_t> block;
+    const layout l = lay_out(block, n, sizeof *inputs / 4, total_waves, [&](uint32_t i) { return waves(inputs[i].vertex_count, R3N_TANGENTS_WAVE_VERTICES); });
     std::memcpy(block.data(), inputs, (size_t)n * sizeof *inputs);
-    uint32_t w = 0;
-    for (uint32_t i = 0; i < n; ++i) {
-        block[o_first + i] = w;
-        const uint32_t nw = r3n_tangents_waves(inputs[i].vertex_count);
-        std::fill(block.begin() + o_inst + w, block.begin() + o_inst + w + nw, i);
-        w += nw;
-    }
-    TRY(ensure(c, c->tangents_block, block.size() * 4, false, -1));
-    TRY(upload_bulk(c, c->tangents_block.p, block.data(), block.size() * 4));  // pinned staging: no wait for the GPU
     TangentsArgs a{};
-    a.mesh = c->mesh.as<uint32_t>();
-    a.recs = c->tangents_block.as<r3n_tangents_input32>();
-    a.wave_first = c->tangents_block.as<uint32_t>() + o_first;
-    a.wave_instance = c->tangents_block.as<uint32_t>() + o_inst;
-    a.total_waves = w;
+    TRY(stage_wave_block(c, c->tangents_block, block, l, total_waves, a));
     ++c->main_epoch;  // the shadow lanes read the mesh buffer
     Timed t(c, R3N_STAGE_TANGENTS);
     HIP_TRY(c, (hipError_t)r3n_internal_vertex_tangents(&a, c->stream));

@@ -14,25 +14,12 @@
 //
 // Adjacency: r3n_host_vertex_adjacency's words, as normals.h describes them.
 #pragma once
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
 #include "../../include/r3n.h"
+#include "vertex_gather.h"
 
 #define R3N_TANGENTS_WAVE_VERTICES 64u  // one thread per vertex
 
-struct TangentsArgs {
-    uint32_t *mesh;
-    const r3n_tangents_input32 *recs;  // 8 words each: one s_load_dwordx8
-    const uint32_t *wave_instance;     // total_waves: the instance of every wave slot
-    const uint32_t *wave_first;        // per instance: its first wave slot
-    uint32_t total_waves;
-};
-
-// waves an instance of `vertex_count` vertices takes
-static inline uint32_t r3n_tangents_waves(uint32_t vertex_count) {
-    return (uint32_t)(((uint64_t)vertex_count + R3N_TANGENTS_WAVE_VERTICES - 1u) / R3N_TANGENTS_WAVE_VERTICES);
-}
+using TangentsArgs = vertex_gather::Args<r3n_tangents_input32>;  // 8 words each: one s_load_dwordx8
 
 // enqueues the ONE launch on `stream`; returns the hipError_t of the launch
 extern "C" int r3n_internal_vertex_tangents(const TangentsArgs *a, hipStream_t stream);
