@@ -310,6 +310,19 @@ pub struct r3n_config {
 
 #[repr(C)]
 #[derive(Clone, Copy)]
+pub struct r3n_texture_counters {
+    pub update_calls: u64,
+    pub kernel_launches: u64,
+    pub bytes_staged: u64,
+    pub full_syncs: u64,
+    pub pool_grows: u64,
+    pub pool_words: u64,
+    pub live_words: u64,
+    pub free_ranges: u64,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
 pub struct r3n_shadow_view272 {
     pub header: r3n_camera_header240,
     pub x: u32,
@@ -399,6 +412,9 @@ extern "C" {
     pub fn r3n_materials_write(ctx: *mut r3n_ctx, slots: *const u32, records: *const r3n_material208, keys: *const u8, n: u32) -> c_int;
     pub fn r3n_textures_write(ctx: *mut r3n_ctx, descs: *const r3n_texture_desc32, n_textures: u32, texels: *const u32, n_texels: u64) -> c_int;
     pub fn r3n_textures_write_encoded(ctx: *mut r3n_ctx, descs: *const r3n_texture_desc32, n_textures: u32, payload: *const c_void, payload_bytes: u64) -> c_int;
+    pub fn r3n_textures_update(ctx: *mut r3n_ctx, slots: *const u32, descs: *const r3n_texture_desc32, n: u32, payload: *const c_void, payload_bytes: u64) -> c_int;
+    pub fn r3n_textures_remove(ctx: *mut r3n_ctx, slots: *const u32, n: u32) -> c_int;
+    pub fn r3n_texture_stats(ctx: *mut r3n_ctx, out: *mut r3n_texture_counters, reset: c_int) -> c_int;
     pub fn r3n_texture_cubes_write(ctx: *mut r3n_ctx, descs: *const r3n_texture_desc32, n_cubes: u32, texels: *const u32, n_texels: u64) -> c_int;
     pub fn r3n_skybox_set(ctx: *mut r3n_ctx, cube_id: u32) -> c_int;
     pub fn r3n_blend_order_write(ctx: *mut r3n_ctx, objects_back_to_front: *const u32, n: u32) -> c_int;
@@ -449,6 +465,7 @@ extern "C" {
     pub fn r3n_readback_baked(ctx: *mut r3n_ctx, camera: u32, model_view_and_mvp: *mut f32, capacity: u32) -> c_int;
     pub fn r3n_readback_mesh(ctx: *mut r3n_ctx, byte_offset: u64, dst: *mut c_void, bytes: u64) -> c_int;
     pub fn r3n_readback_joint_matrices(ctx: *mut r3n_ctx, first_matrix: u32, dst: *mut f32, n_matrices: u32) -> c_int;
+    pub fn r3n_readback_texture_descs(ctx: *mut r3n_ctx, descs: *mut r3n_texture_desc32, capacity: u32, n_slots: *mut u32) -> c_int;
     pub fn r3n_readback_texels(ctx: *mut r3n_ctx, first_texel: u64, rgba8: *mut u32, n_texels: u64) -> c_int;
     pub fn r3n_readback_visibility(ctx: *mut r3n_ctx, keys: *mut u64) -> c_int;
     pub fn r3n_readback_depth(ctx: *mut r3n_ctx, depth: *mut f32) -> c_int;

@@ -310,6 +310,39 @@ int r3n_textures_write(r3n_ctx *ctx, const r3n_texture_desc32 *descs, uint32_t n
  *      150).  Snorm / float / 16-bit / ETC2 / ASTC / BC6H formats -> R3N_ERR_UNSUPPORTED. */
 int r3n_textures_write_encoded(r3n_ctx *ctx, const r3n_texture_desc32 *descs, uint32_t n_textures, const void *payload,
                                uint64_t payload_bytes);
+/*      TextureManager::add (rend3/src/managers/texture.rs: one texture per handle, handed over while frames are being drawn), for n
+ *      entries at once: texture descs[i] goes into slot slots[i] of the bindless array (material texture id = slot + 1).  descs /
+ *      payload exactly as r3n_textures_write_encoded takes them (offset = byte offset of level 0 in `payload`, 4-byte aligned;
+ *      stored_mips as there; every format that call accepts).  A slot that holds a texture is replaced.  Only the call's own data
+ *      is copied and decoded -- every stored level of every texture of the call in at most four launches -- into a texel pool that
+ *      stays resident: a texture is one contiguous range of pool words on a 4-word boundary, first fit at the lowest address,
+ *      appended behind the last one when no hole takes it (slots k, k + 1, ... updated in ascending order from an empty context or
+ *      after a whole-array write get the offsets the whole-array write of the concatenated list gives).  The whole-array writes
+ *      above reset the pool to their own layout; the two kinds of call can be mixed.
+ *      Duplicate slots, a slot >= table length + n (the host allocates the lowest free index: it never needs more) and everything
+ *      r3n_textures_write_encoded rejects are rejected before anything changes; a pool beyond 2^32 words -> R3N_ERR_CAPACITY.
+ *      Frames in flight are waited for only when a buffer has to grow (geometric), when a written slot held a texture at any time
+ *      since the last such wait, or when the data goes into words freed since then (ranges not recently freed are preferred);
+ *      otherwise the call waits for its own copy and decode work alone, which runs on a stream of its own beside the frames (the
+ *      caller owns `payload` for the duration of the call; what is enqueued after the call sees the new textures). */
+int r3n_textures_update(r3n_ctx *ctx, const uint32_t *slots, const r3n_texture_desc32 *descs, uint32_t n, const void *payload,
+                        uint64_t payload_bytes);
+/*      TextureManager::remove (rend3/src/managers/texture.rs; the reference drops the texture with its handle): the slots' pool words
+ *      become reusable; the slots stay in the table as removed entries -- on the device a 1 x 1, one-level RGBA8 entry at pool word
+ *      0, so that a stale material id reads in bounds, with an unspecified value.  Removing a removed or never-written slot, or one
+ *      slot twice -> R3N_ERR_INVALID_ARG, nothing changed.  Never waits for the GPU.  (After a raw r3n_textures_write whose ranges
+ *      are not ascending, disjoint and 4-word aligned the slots own no words: removing them frees none.) */
+int r3n_textures_remove(r3n_ctx *ctx, const uint32_t *slots, uint32_t n);
+/*      Counters of the streamed texture path since creation or the last reset, and the pool's state now.  update_calls: successful
+ *      r3n_textures_update calls; kernel_launches: every kernel they enqueued; bytes_staged: payload bytes they copied; full_syncs:
+ *      waits for every frame in flight they made; pool_grows: calls in which the pool, the descriptor table or the level-offset
+ *      table grew.  pool_words: the pool's high-water mark; live_words: words owned by live textures; free_ranges: holes below the
+ *      mark.  `out` may be NULL with reset != 0.  (The staging and job-table blocks grow geometrically without a wait: an outgrown
+ *      block is kept until the next full wait and freed there.) */
+typedef struct r3n_texture_counters {
+    uint64_t update_calls, kernel_launches, bytes_staged, full_syncs, pool_grows, pool_words, live_words, free_ranges;
+} r3n_texture_counters;
+int r3n_texture_stats(r3n_ctx *ctx, r3n_texture_counters *out, int reset);
 /*      The cube textures (the reference's d2c_texture_manager, rend3/src/managers/texture.rs; Renderer::add_texture_cube): replaces
  *      the context's whole cube array, which is separate from the bindless 2D array.  A cube is six square faces of width x width
  *      RGBA8 texels, contiguous from desc.offset (in texels) in `texels`, in layer order +X, -X, +Y, -Y, +Z, -Z (what scene_viewer
@@ -629,6 +662,11 @@ int r3n_readback_blend_order(r3n_ctx *ctx, uint32_t *order, uint32_t *rank_base,
 int r3n_readback_baked(r3n_ctx *ctx, r3n_camera camera, float *model_view_and_mvp, uint32_t capacity);
 int r3n_readback_mesh(r3n_ctx *ctx, uint64_t byte_offset, void *dst, uint64_t bytes); /* e.g. skinned attribute runs */
 int r3n_readback_joint_matrices(r3n_ctx *ctx, uint32_t first_matrix, float *dst, uint32_t n_matrices); /* what the last r3n_skinning read */
+/* The texture table as the device holds it (rend3/src/managers/texture.rs keeps one entry per handle): offset in pool words, width,
+ * height, mips, format = the pool class (R3N_TEXTURE_RGBA8_UNORM / _SRGB, or 2 = four f32 per texel); removed slots have width =
+ * height = 0 in THIS read-back.  *n_slots = table length; descs == NULL asks for the length alone (R3N_OK); a `capacity` below it
+ * -> R3N_ERR_INVALID_ARG. */
+int r3n_readback_texture_descs(r3n_ctx *ctx, r3n_texture_desc32 *descs, uint32_t capacity, uint32_t *n_slots);
 int r3n_readback_texels(r3n_ctx *ctx, uint64_t first_texel, uint32_t *rgba8, uint64_t n_texels); /* the decoded RGBA8 texel pool (after
                                                                                          r3n_textures_write_encoded: texture i's levels back to back, textures
                                                                                          in array order, each starting on a 4-texel boundary) */

@@ -42,6 +42,9 @@ SIGNATURES = {
     "r3n_materials_write": (cint, [vp, vp, vp, vp, u32]),
     "r3n_textures_write": (cint, [vp, vp, u32, vp, u64]),
     "r3n_textures_write_encoded": (cint, [vp, vp, u32, vp, u64]),
+    "r3n_textures_update": (cint, [vp, vp, vp, u32, vp, u64]),
+    "r3n_textures_remove": (cint, [vp, vp, u32]),
+    "r3n_texture_stats": (cint, [vp, vp, cint]),
     "r3n_texture_cubes_write": (cint, [vp, vp, u32, vp, u64]),
     "r3n_skybox_set": (cint, [vp, u32]),
     "r3n_animation_write": (cint, [vp, vp, u32, vp, u32, vp, u32, vp, u32, vp, u32, vp, u32]),
@@ -92,6 +95,7 @@ SIGNATURES = {
     "r3n_readback_blend_order": (cint, [vp, vp, vp, u32]),
     "r3n_readback_baked": (cint, [vp, u32, vp, u32]),
     "r3n_readback_mesh": (cint, [vp, u64, vp, u64]),
+    "r3n_readback_texture_descs": (cint, [vp, vp, u32, vp]),
     "r3n_readback_texels": (cint, [vp, u64, vp, u64]),
     "r3n_readback_joint_matrices": (cint, [vp, u32, vp, u32]),
     "r3n_readback_visibility": (cint, [vp, vp]),
@@ -158,6 +162,12 @@ class FrameDesc(ctypes.Structure):
                 ("directional_buffer", vp), ("directional_bytes", u64), ("point_buffer", vp), ("point_bytes", u64),
                 ("skin_inputs", vp), ("n_skeletons", u32), ("n_joint_matrices", u32), ("joint_matrices", vp),
                 ("exchange", EXCHANGE_FN), ("exchange_user", vp)]
+
+
+class TextureCounters(ctypes.Structure):
+    """r3n_texture_counters"""
+    _fields_ = [(name, u64) for name in ("update_calls", "kernel_launches", "bytes_staged", "full_syncs", "pool_grows", "pool_words",
+                                         "live_words", "free_ranges")]
 
 
 class Config(ctypes.Structure):

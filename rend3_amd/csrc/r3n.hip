@@ -24,6 +24,8 @@
 #include "morph.h"
 #include "normals.h"
 #include "tangents.h"
+#include "texel_alloc.h"
+#include "texture_jobs.h"
 #include "vertex_block.h"
 
 namespace {
@@ -212,8 +214,23 @@ struct r3n_ctx {
     bool blend_sorted = false;
     uint32_t frag_capacity = 32u << 20;  // fragment nodes (12 B each), allocated on first use
     DevBuf tex_descs, tex_texels, tex_level_off, srgb8_decode;  // bindless texture array (row N2): descriptors, RGBA8 texel pool, decode tables  // bindless texture array (row N2) + sRGB8 -> linear table
-    uint32_t n_textures = 0;
-    uint64_t n_texels = 0;
+    uint32_t n_textures = 0;  // table length (streamed path: removed slots included)
+    uint64_t n_texels = 0;    // pool words in use: the allocator's high-water mark
+    // Streamed texture path (r3n_textures_update / r3n_textures_remove; texel_alloc.h): the host's mirror of the table and who owns
+    // which pool words.  A whole-array write resets all of it to "one live prefix".
+    texel_alloc::Pool tex_alloc;
+    std::vector<r3n_texture_desc32> h_tex_descs;  // per slot, as the device holds it; a removed slot: width = height = 0
+    std::vector<uint64_t> h_tex_words;            // per slot: pool words its range owns (0: none -- removed, or a raw write with overlapping ranges)
+    std::vector<uint8_t> h_tex_live;              // per slot: holds a texture
+    std::vector<uint8_t> h_tex_hot;               // per slot: held a texture at some time since the last full wait (a frame in flight may read it)
+    uint64_t sync_serial = 0, tex_sync_seen = 0;  // sync_all counts its calls; the texture path compares
+    DevBuf tex_stage, tex_jobs;                   // grow-only, owned by the texture path alone: the call's payload, its job tables
+    std::vector<void *> tex_retired;              // outgrown blocks of those two: freed behind the next full wait (hipFree waits for the device)
+    // The streamed path's own stream (created by the first r3n_textures_update): the payload copy, the table rows, the decode and
+    // the generated levels run on it, and the call waits for IT alone -- the frames in flight on the main stream, the lanes and the
+    // shade stream keep running.  Everything enqueued after the call comes after its work, because the call has waited for it.
+    hipStream_t tex_stream = nullptr;
+    r3n_texture_counters tex_stats{};
     // cube textures + the skybox node (skybox.h): the bordered faces of every cube, where each cube starts, which one is bound
     struct Cube { size_t first_word; uint32_t n, srgb; };
     DevBuf cube_texels;
@@ -507,6 +524,7 @@ int sync_all(r3n_ctx *c) {
     if (r != R3N_OK) return r;
     HIP_WAIT(c, hipStreamSynchronize(c->stream));
     if (c->shade) HIP_WAIT(c, hipStreamSynchronize(c->shade));
+    ++c->sync_serial;  // every frame enqueued so far has finished: the texture path's quarantine is over
     crumb(c, "sync_all done");
     return R3N_OK;
 }
@@ -967,7 +985,7 @@ void r3n_destroy(r3n_ctx *c) {
     }
     DevBuf *bufs[] = {&c->mesh, &c->objects, &c->spheres, &c->obj_meta, &c->materials, &c->material_keys, &c->fb_dev[0], &c->fb_dev[1], &c->big_count_all, &c->owners,
                       &c->tri_base, &c->slot_table, &c->skin_inputs, &c->skin_matrices, &c->skin_wave_skeleton,
-                      &c->skin_wave_first, &c->skin_joint_counts, &c->morph_block, &c->normals_block, &c->tangents_block, &c->vis, &c->hdr16, &c->out8, &c->out_f32, &c->atlas, &c->hiz, &c->alt_vis, &c->alt_atlas, &c->alt_vp_baked, &c->srgb_lut, &c->srgb_thr, &c->tex_descs, &c->tex_texels, &c->tex_level_off, &c->srgb8_decode,
+                      &c->skin_wave_first, &c->skin_joint_counts, &c->morph_block, &c->normals_block, &c->tangents_block, &c->vis, &c->hdr16, &c->out8, &c->out_f32, &c->atlas, &c->hiz, &c->alt_vis, &c->alt_atlas, &c->alt_vp_baked, &c->srgb_lut, &c->srgb_thr, &c->tex_descs, &c->tex_texels, &c->tex_level_off, &c->srgb8_decode, &c->tex_stage, &c->tex_jobs,
                       &c->tri_rec, &c->tri_seen, &c->blend_order, &c->blend_rank_base, &c->frag_keys, &c->frag_vals, &c->frag_head,
                       &c->frag_count, &c->samples16, &c->anim_rigs, &c->anim_joints, &c->anim_clips, &c->anim_tracks,
                       &c->anim_times, &c->anim_values, &c->pose_requests, &c->edge_list, &c->edge_count, &c->material_feat, &c->view_lights[0],
@@ -996,6 +1014,8 @@ void r3n_destroy(r3n_ctx *c) {
     }
     for (auto e : c->stage_half_done)
         if (e) (void)hipEventDestroy(e);
+    if (c->tex_stream) (void)hipStreamDestroy(c->tex_stream);
+    for (void *p : c->tex_retired) (void)hipFree(p);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
@@ -1143,23 +1163,47 @@ static TextureArgs texture_args(r3n_ctx *c) {
 // First word (pool index) of every level of every texture: R3N_TEX_LEVELS entries per texture, so that the sampler does not
 // walk the chain.  `descs` = the descriptors as the device holds them (offsets in pool words; a texel is one word, or four
 // for R3N_POOL_FLOAT textures).
+static void level_row(const r3n_texture_desc32 &d, uint32_t *row) {
+    uint64_t at = d.offset;
+    for (uint32_t k = 0; k < R3N_TEX_LEVELS; ++k) {
+        row[k] = (uint32_t)at;
+        if (k < d.mips) at += (uint64_t)std::max(1u, d.width >> k) * std::max(1u, d.height >> k) * (d.format == R3N_POOL_FLOAT ? 4u : 1u);
+    }
+}
+// which textures the sampler's short path covers (texture.h tex_sample_grad): power-of-two extents, RGBA8 pool texels
+static uint8_t texture_is_short(const r3n_texture_desc32 &d) {
+    const uint32_t w = d.width, h = d.height;
+    // (w * h <= 2^29: tex_level_start_pow2 forms 1 << (log2 w + log2 h + 2) in 32 bits -- a single-level 32768^2 texture would
+    // shift by 32; it goes to the general sampler instead)
+    return (w && h && ((w & (w - 1u)) | (h & (h - 1u))) == 0u && (uint64_t)w * h <= (1ull << 29) && d.format < R3N_POOL_FLOAT) ? 1 : 0;
+}
+static uint64_t texture_pool_words(const r3n_texture_desc32 &d) {
+    uint64_t words = 0;
+    for (uint32_t k = 0; k < d.mips; ++k) words += (uint64_t)std::max(1u, d.width >> k) * std::max(1u, d.height >> k) * (d.format == R3N_POOL_FLOAT ? 4u : 1u);
+    return words;
+}
+
 static int upload_level_offsets(r3n_ctx *c, const r3n_texture_desc32 *descs, uint32_t n, uint64_t n_texels) {
     std::vector<uint32_t> off((size_t)std::max(n, 1u) * R3N_TEX_LEVELS, 0u);
-    for (uint32_t i = 0; i < n; ++i) {
-        uint64_t at = descs[i].offset;
-        for (uint32_t k = 0; k < R3N_TEX_LEVELS; ++k) {
-            off[(size_t)i * R3N_TEX_LEVELS + k] = (uint32_t)at;
-            if (k < descs[i].mips) at += (uint64_t)std::max(1u, descs[i].width >> k) * std::max(1u, descs[i].height >> k) * (descs[i].format == R3N_POOL_FLOAT ? 4u : 1u);
-        }
-    }
-    // which textures the sampler's short path covers (texture.h tex_sample_grad): power-of-two extents, RGBA8 pool texels
+    for (uint32_t i = 0; i < n; ++i) level_row(descs[i], off.data() + (size_t)i * R3N_TEX_LEVELS);
     c->h_tex_short.assign(n, 0);
-    for (uint32_t i = 0; i < n; ++i) {
-        const uint32_t w = descs[i].width, h = descs[i].height;
-        // (w * h <= 2^29: tex_level_start_pow2 forms 1 << (log2 w + log2 h + 2) in 32 bits -- a single-level 32768^2 texture would
-        // shift by 32; it goes to the general sampler instead)
-        c->h_tex_short[i] = (w && h && ((w & (w - 1u)) | (h & (h - 1u))) == 0u && (uint64_t)w * h <= (1ull << 29) && descs[i].format < R3N_POOL_FLOAT) ? 1 : 0;
+    for (uint32_t i = 0; i < n; ++i) c->h_tex_short[i] = texture_is_short(descs[i]);
+    // the streamed path's mirror: one live prefix [0, n_texels), table length n.  A slot owns its words (r3n_textures_remove gives
+    // them back) when the ranges are the disjoint, ascending, 4-word-aligned ones r3n_textures_write_encoded lays out; a raw
+    // r3n_textures_write whose ranges are not owns none.
+    c->h_tex_descs.assign(descs, descs + n);
+    c->h_tex_live.assign(n, 1);
+    c->h_tex_hot.assign(n, 1);
+    c->h_tex_words.assign(n, 0);
+    bool canonical = true;
+    uint64_t prev_end = 0;
+    for (uint32_t i = 0; i < n && canonical; ++i) {
+        canonical = (descs[i].offset & 3u) == 0u && descs[i].offset >= prev_end;
+        prev_end = descs[i].offset + texture_pool_words(descs[i]);
     }
+    if (canonical)
+        for (uint32_t i = 0; i < n; ++i) c->h_tex_words[i] = texture_pool_words(descs[i]);
+    c->tex_alloc.reset(n_texels);
     c->classes_dirty = true; c->cutout_short_dirty = true;
     TRY(ensure(c, c->tex_level_off, off.size() * 4, false, -1));
     HIP_TRY(c, hipMemcpyAsync(c->tex_level_off.p, off.data(), off.size() * 4, hipMemcpyHostToDevice, c->stream));
@@ -1210,41 +1254,52 @@ extern "C" uint32_t r3n_internal_format_align(uint32_t format);
 extern "C" int r3n_internal_format_generates_mips_f32(uint32_t format);
 extern "C" int r3n_internal_generate_mip_f32(uint32_t format, uint32_t sw, uint32_t sh, uint32_t dw, uint32_t dh, const float *src, float *dst,
                                              hipStream_t stream);
+extern "C" int r3n_internal_decode_jobs(uint32_t family, const uint32_t *block, uint64_t o_first, uint64_t o_inst, uint32_t total_waves,
+                                        const void *staged, uint32_t *pool, hipStream_t stream);
+
+// One descriptor of r3n_textures_write_encoded / r3n_textures_update (`what` names the call in the message): validates it against
+// the payload and gives the descriptor the device holds (pool format class, offset still to be placed) and its pool words.
+static int check_encoded_desc(r3n_ctx *c, const std::string &what, const r3n_texture_desc32 &d, uint64_t payload_bytes, r3n_texture_desc32 &internal,
+                              uint64_t &words) {
+    if (d.format >= R3N_TEXTURE_FORMAT_COUNT) return fail(c, R3N_ERR_UNSUPPORTED, what + ": unknown format id");
+    const bool is_float = r3n_internal_format_is_float(d.format) != 0;
+    if (!d.width || !d.height || !d.mips || d.width > 65535u || d.height > 65535u) return fail(c, R3N_ERR_INVALID_ARG, what + ": bad extent");
+    uint32_t max_mips = 0;
+    for (uint32_t m = std::max(d.width, d.height); m; m >>= 1) ++max_mips;
+    if (d.mips > max_mips) return fail(c, R3N_ERR_INVALID_ARG, what + ": more mips than the extent has");
+    if (d.stored_mips > d.mips) return fail(c, R3N_ERR_INVALID_ARG, what + ": more stored levels than mips");
+    const uint32_t stored = d.stored_mips ? d.stored_mips : d.mips;
+    if (stored < d.mips && d.format >= R3N_TEXTURE_BC1_RGBA_UNORM && !r3n_internal_format_generates_mips_f32(d.format))
+        return fail(c, R3N_ERR_UNSUPPORTED, what + (is_float ? ": among the float-decoded formats mips are generated for R16Float / Rg16Float / Rgba16Float / Rgb10a2Unorm only (filterable render targets); the others must carry their levels"
+                                                             : ": mips are generated for uncompressed formats only (block formats are not render targets)"));
+    uint64_t end = d.offset;
+    words = 0;
+    for (uint32_t k = 0; k < d.mips; ++k) {
+        const uint32_t w = std::max(1u, d.width >> k), h = std::max(1u, d.height >> k);
+        if (k < stored) end += r3n_internal_level_bytes(d.format, w, h);
+        words += (uint64_t)w * h * (is_float ? 4u : 1u);  // pool words
+    }
+    if (end > payload_bytes) return fail(c, R3N_ERR_INVALID_ARG, what + ": levels outside the payload");
+    if ((d.offset & 3u) != 0u) return fail(c, R3N_ERR_INVALID_ARG, what + ": level 0 must start on a 4-byte boundary");
+    const bool srgb = d.format == R3N_TEXTURE_RGBA8_UNORM_SRGB || d.format == R3N_TEXTURE_BGRA8_UNORM_SRGB ||
+                      d.format == R3N_TEXTURE_BC1_RGBA_UNORM_SRGB || d.format == R3N_TEXTURE_BC2_RGBA_UNORM_SRGB ||
+                      d.format == R3N_TEXTURE_BC3_RGBA_UNORM_SRGB || d.format == R3N_TEXTURE_BC7_RGBA_UNORM_SRGB;
+    internal = d;
+    internal.stored_mips = 0;
+    internal.format = is_float ? R3N_POOL_FLOAT : (srgb ? R3N_TEXTURE_RGBA8_UNORM_SRGB : R3N_TEXTURE_RGBA8_UNORM);
+    return R3N_OK;
+}
 
 int r3n_textures_write_encoded(r3n_ctx *c, const r3n_texture_desc32 *descs, uint32_t n, const void *payload, uint64_t payload_bytes) {
     if (!c || (n && (!descs || !payload))) return fail(c, R3N_ERR_INVALID_ARG, "textures write (encoded): null");
     std::vector<r3n_texture_desc32> internal(n);
     uint64_t n_texels = 0;
     for (uint32_t i = 0; i < n; ++i) {
-        const r3n_texture_desc32 &d = descs[i];
-        if (d.format >= R3N_TEXTURE_FORMAT_COUNT) return fail(c, R3N_ERR_UNSUPPORTED, "textures write (encoded): unknown format id");
-        const bool is_float = r3n_internal_format_is_float(d.format) != 0;
-        if (!d.width || !d.height || !d.mips || d.width > 65535u || d.height > 65535u) return fail(c, R3N_ERR_INVALID_ARG, "textures write (encoded): bad extent");
-        uint32_t max_mips = 0;
-        for (uint32_t m = std::max(d.width, d.height); m; m >>= 1) ++max_mips;
-        if (d.mips > max_mips) return fail(c, R3N_ERR_INVALID_ARG, "textures write (encoded): more mips than the extent has");
-        if (d.stored_mips > d.mips) return fail(c, R3N_ERR_INVALID_ARG, "textures write (encoded): more stored levels than mips");
-        const uint32_t stored = d.stored_mips ? d.stored_mips : d.mips;
-        if (stored < d.mips && d.format >= R3N_TEXTURE_BC1_RGBA_UNORM && !r3n_internal_format_generates_mips_f32(d.format))
-            return fail(c, R3N_ERR_UNSUPPORTED, is_float ? "textures write (encoded): among the float-decoded formats mips are generated for R16Float / Rg16Float / Rgba16Float / Rgb10a2Unorm only (filterable render targets); the others must carry their levels"
-                                                         : "textures write (encoded): mips are generated for uncompressed formats only (block formats are not render targets)");
-        uint64_t end = d.offset, texels = 0;
-        for (uint32_t k = 0; k < d.mips; ++k) {
-            const uint32_t w = std::max(1u, d.width >> k), h = std::max(1u, d.height >> k);
-            if (k < stored) end += r3n_internal_level_bytes(d.format, w, h);
-            texels += (uint64_t)w * h * (is_float ? 4u : 1u);  // pool words
-        }
-        if (end > payload_bytes) return fail(c, R3N_ERR_INVALID_ARG, "textures write (encoded): levels outside the payload");
-        if ((d.offset & 3u) != 0u) return fail(c, R3N_ERR_INVALID_ARG, "textures write (encoded): level 0 must start on a 4-byte boundary");
+        uint64_t texels = 0;
+        TRY(check_encoded_desc(c, "textures write (encoded)", descs[i], payload_bytes, internal[i], texels));
         if (n_texels + texels > 0xFFFFFFFFull) return fail(c, R3N_ERR_CAPACITY, "textures write (encoded): texel pool exceeds 2^32 texels");
-        const bool srgb = d.format == R3N_TEXTURE_RGBA8_UNORM_SRGB || d.format == R3N_TEXTURE_BGRA8_UNORM_SRGB ||
-                          d.format == R3N_TEXTURE_BC1_RGBA_UNORM_SRGB || d.format == R3N_TEXTURE_BC2_RGBA_UNORM_SRGB ||
-                          d.format == R3N_TEXTURE_BC3_RGBA_UNORM_SRGB || d.format == R3N_TEXTURE_BC7_RGBA_UNORM_SRGB;
         n_texels = (n_texels + 3u) & ~3ull;  // 16-byte-aligned texture starts: the block decoder stores whole rows
-        internal[i] = d;
-        internal[i].stored_mips = 0;
         internal[i].offset = (uint32_t)n_texels;
-        internal[i].format = is_float ? R3N_POOL_FLOAT : (srgb ? R3N_TEXTURE_RGBA8_UNORM_SRGB : R3N_TEXTURE_RGBA8_UNORM);
         n_texels += texels;
     }
     HIP_TRY(c, hipSetDevice(c->device));
@@ -1294,6 +1349,290 @@ int r3n_textures_write_encoded(r3n_ctx *c, const r3n_texture_desc32 *descs, uint
     }
     TRY(upload_level_offsets(c, internal.data(), n, n_texels));
     c->n_textures = n;
+    return R3N_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ streamed textures
+// r3n_textures_update / r3n_textures_remove: the texel pool, the descriptor table and the level-offset table stay resident and
+// single entries change.  What a frame in flight may read is never rewritten without waiting for it: a NEW slot and FRESH pool
+// words (behind the high-water mark, or a hole nobody has read since the last full wait) cannot be named by a frame already
+// enqueued, so writing them needs no wait; everything else goes behind sync_all.  The update's work runs on a stream of its
+// own (r3n_ctx::tex_stream), so waiting for it waits for no frame.
+
+// a sync_all since the texture path last looked: ranges parked by r3n_textures_remove are clean, only live slots can be read
+static void texture_note_syncs(r3n_ctx *c) {
+    if (c->tex_sync_seen == c->sync_serial) return;
+    c->tex_sync_seen = c->sync_serial;
+    c->tex_alloc.release();
+    c->n_texels = c->tex_alloc.end();
+    c->h_tex_hot = c->h_tex_live;
+    for (void *p : c->tex_retired) (void)hipFree(p);  // the device is idle: the free stalls nothing
+    c->tex_retired.clear();
+}
+
+// what the device holds for a slot: a removed (or never written) slot is a 1 x 1, one-level RGBA8 entry at pool word 0
+static r3n_texture_desc32 device_desc(const r3n_ctx *c, uint32_t slot) {
+    if (c->h_tex_live[slot]) return c->h_tex_descs[slot];
+    r3n_texture_desc32 d{};
+    d.width = d.height = d.mips = 1u;
+    d.format = R3N_TEXTURE_RGBA8_UNORM;
+    return d;
+}
+
+// descriptors and level-offset rows of `slots` (ascending) from the host mirror: one copy pair per run of consecutive slots.
+// own_stream: on the texture stream (r3n_textures_update; the caller waits for that stream before it returns); otherwise on the
+// main stream through pinned staging -- no wait for the GPU (r3n_textures_remove).
+static int upload_texture_slots(r3n_ctx *c, const std::vector<uint32_t> &slots, bool own_stream) {
+    std::vector<r3n_texture_desc32> d;
+    std::vector<uint32_t> rows;
+    for (size_t i = 0; i < slots.size();) {
+        size_t run = 1;
+        while (i + run < slots.size() && slots[i + run] == slots[i] + run) ++run;
+        d.resize(run);
+        rows.resize(run * R3N_TEX_LEVELS);
+        for (size_t k = 0; k < run; ++k) {
+            d[k] = device_desc(c, slots[i + k]);
+            level_row(d[k], rows.data() + k * R3N_TEX_LEVELS);
+        }
+        r3n_texture_desc32 *d_dst = c->tex_descs.as<r3n_texture_desc32>() + slots[i];
+        uint32_t *r_dst = c->tex_level_off.as<uint32_t>() + (size_t)slots[i] * R3N_TEX_LEVELS;
+        if (own_stream) {  // (pageable sources: the copy has left `d` / `rows` when the call returns)
+            HIP_TRY(c, hipMemcpyAsync(d_dst, d.data(), run * sizeof(r3n_texture_desc32), hipMemcpyHostToDevice, c->tex_stream));
+            HIP_TRY(c, hipMemcpyAsync(r_dst, rows.data(), rows.size() * 4, hipMemcpyHostToDevice, c->tex_stream));
+        } else {
+            TRY(upload_bulk(c, d_dst, d.data(), run * sizeof(r3n_texture_desc32)));
+            TRY(upload_bulk(c, r_dst, rows.data(), rows.size() * 4));
+        }
+        i += run;
+    }
+    return R3N_OK;
+}
+
+// Grow-only block the texture path alone uses (payload staging, job tables); contents are not kept.  Every call that used it
+// waited for its own work, so nothing reads the old block; it is freed behind the next full wait (texture_note_syncs), because
+// hipFree waits for the whole device.
+static int grow_texture_scratch(r3n_ctx *c, DevBuf &b, size_t bytes) {
+    if (b.p && bytes <= b.bytes) return R3N_OK;
+    const size_t want = std::max<size_t>(std::max<size_t>(bytes, 2 * b.bytes), 4096);
+    if (b.p) {
+        c->tex_retired.push_back(b.p);
+        b.p = nullptr; b.bytes = 0;
+    }
+    HIP_TRY(c, hipMalloc(&b.p, want));
+    b.bytes = want;
+    return R3N_OK;
+}
+
+// Geometric growth of a resident buffer, contents kept: one device-to-device copy.  The caller has waited for every frame.
+static int grow_texture_resident(r3n_ctx *c, DevBuf &b, size_t bytes, size_t most) {
+    if (b.p && bytes <= b.bytes) return R3N_OK;
+    const size_t want = std::max(bytes, std::min<size_t>(2 * b.bytes, most));
+    void *np = nullptr;
+    HIP_TRY(c, hipMalloc(&np, want));
+    hipError_t e = hipSuccess;
+    if (b.p && b.bytes) e = hipMemcpyAsync(np, b.p, b.bytes, hipMemcpyDeviceToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(static_cast<char *>(np) + b.bytes, 0, want - b.bytes, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) {
+        (void)hipFree(np);
+        return fail(c, R3N_ERR_HIP, std::string("textures update: growing a buffer: ") + hipGetErrorString(e));
+    }
+    if (b.p) HIP_TRY(c, hipFree(b.p));
+    b.p = np;
+    b.bytes = want;
+    ++c->main_epoch;
+    return R3N_OK;
+}
+
+int r3n_textures_update(r3n_ctx *c, const uint32_t *slots, const r3n_texture_desc32 *descs, uint32_t n, const void *payload,
+                        uint64_t payload_bytes) {
+    if (!c || (n && (!slots || !descs || !payload))) return fail(c, R3N_ERR_INVALID_ARG, "textures update: null");
+    if (!n) return R3N_OK;
+    // ---- validation and planning: nothing of the context changes before both are through
+    const uint32_t table = c->n_textures;
+    std::vector<r3n_texture_desc32> internal(n);
+    std::vector<uint64_t> words(n);
+    for (uint32_t i = 0; i < n; ++i) {
+        TRY(check_encoded_desc(c, "textures update", descs[i], payload_bytes, internal[i], words[i]));
+        if ((uint64_t)slots[i] >= (uint64_t)table + n)
+            return fail(c, R3N_ERR_INVALID_ARG, "textures update: slot past table length + n (the lowest free index never is)");
+    }
+    std::vector<uint32_t> touched(slots, slots + n);
+    std::sort(touched.begin(), touched.end());
+    if (std::adjacent_find(touched.begin(), touched.end()) != touched.end()) return fail(c, R3N_ERR_INVALID_ARG, "textures update: one slot named twice");
+    const uint32_t new_table = std::max(table, touched.back() + 1u);
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (!c->tex_stream) HIP_TRY(c, hipStreamCreateWithFlags(&c->tex_stream, hipStreamNonBlocking));
+    texture_note_syncs(c);
+    const uint64_t syncs_before = c->sync_serial;
+
+    texel_alloc::Pool plan = c->tex_alloc;
+    bool wait = false;  // for every frame in flight
+    for (uint32_t i = 0; i < n; ++i) wait = wait || (slots[i] < table && c->h_tex_hot[slots[i]] != 0);
+    const size_t descs_bytes = (size_t)new_table * sizeof(r3n_texture_desc32), rows_bytes = (size_t)new_table * R3N_TEX_LEVELS * 4u;
+    const bool grow_tables = descs_bytes > c->tex_descs.bytes || rows_bytes > c->tex_level_off.bytes;
+    wait = wait || grow_tables;
+    if (wait) plan.release();
+    for (uint32_t i = 0; i < n; ++i)  // replaced textures give their words back first (a live slot is hot: the wait is certain)
+        if (slots[i] < table && c->h_tex_live[slots[i]]) plan.free(c->h_tex_descs[slots[i]].offset, c->h_tex_words[slots[i]], false);
+    for (uint32_t i = 0; i < n; ++i) {
+        bool merged = false;
+        const uint64_t at = plan.alloc(words[i], &merged);
+        if (at == texel_alloc::NONE) return fail(c, R3N_ERR_CAPACITY, "textures update: texel pool exceeds 2^32 texels");
+        wait = wait || merged;  // the range was freed since the last full wait
+        internal[i].offset = (uint32_t)at;
+    }
+    const size_t pool_bytes = (size_t)std::max<uint64_t>(plan.end(), 1) * 4u + 16u;  // (+16: see r3n_textures_write)
+    const bool grow_pool = pool_bytes > c->tex_texels.bytes;
+    wait = wait || grow_pool;
+
+    // the job tables: one record per stored level, per kernel family (texture_jobs.h); generated levels follow per level
+    texture_jobs::Table tables[texture_jobs::FAMILIES];
+    uint64_t generated = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        const r3n_texture_desc32 &d = descs[i];
+        const uint32_t stored = d.stored_mips ? d.stored_mips : d.mips, per = internal[i].format == R3N_POOL_FLOAT ? 4u : 1u;
+        uint64_t src = d.offset, dst = internal[i].offset;
+        for (uint32_t k = 0; k < d.mips; ++k) {
+            const uint32_t w = std::max(1u, d.width >> k), h = std::max(1u, d.height >> k);
+            if (k < stored) {
+                texture_jobs::add_level(tables, d.format, w, h, src, (uint32_t)dst);
+                src += r3n_internal_level_bytes(d.format, w, h);
+            } else {
+                ++generated;
+            }
+            dst += (uint64_t)w * h * per;
+        }
+    }
+    if (!texture_jobs::finish(tables)) return fail(c, R3N_ERR_CAPACITY, "textures update: more than 2^31 wave slots of decode work in one call");
+    size_t job_words = 0, job_at[texture_jobs::FAMILIES];
+    for (int f = 0; f < texture_jobs::FAMILIES; ++f) {
+        job_at[f] = job_words;
+        job_words += (tables[f].block.size() + 7u) & ~(size_t)7u;
+    }
+
+    // ---- device side: wait if a frame may read what changes, grow, stage
+    if (wait) {
+        TRY(sync_all(c));
+        texture_note_syncs(c);
+        plan.release();
+    }
+    if (grow_tables || grow_pool) {
+        TRY(grow_texture_resident(c, c->tex_descs, descs_bytes, ~(size_t)0));
+        TRY(grow_texture_resident(c, c->tex_level_off, rows_bytes, ~(size_t)0));
+        TRY(grow_texture_resident(c, c->tex_texels, pool_bytes, (size_t)(texel_alloc::LIMIT + 1u) * 4u + 16u));
+        ++c->tex_stats.pool_grows;
+    }
+    TRY(grow_texture_scratch(c, c->tex_stage, (size_t)std::max<uint64_t>(payload_bytes, 4)));
+    TRY(grow_texture_scratch(c, c->tex_jobs, std::max<size_t>(job_words, 1) * 4u));
+
+    // ---- the host mirror follows
+    c->h_tex_descs.resize(new_table, r3n_texture_desc32{});
+    c->h_tex_words.resize(new_table, 0);
+    c->h_tex_live.resize(new_table, 0);
+    c->h_tex_hot.resize(new_table, 0);
+    c->h_tex_short.resize(new_table, 0);
+    for (uint32_t slot = table; slot < new_table; ++slot) {  // slots the call opens: its own, and any it leaves out (removed entries)
+        if (!std::binary_search(touched.begin(), touched.end(), slot)) touched.push_back(slot);
+        c->h_tex_descs[slot] = device_desc(c, slot);
+        c->h_tex_descs[slot].width = c->h_tex_descs[slot].height = 0;
+    }
+    std::sort(touched.begin(), touched.end());
+    for (uint32_t i = 0; i < n; ++i) {
+        c->h_tex_descs[slots[i]] = internal[i];
+        c->h_tex_words[slots[i]] = words[i];
+        c->h_tex_live[slots[i]] = c->h_tex_hot[slots[i]] = 1;
+        c->h_tex_short[slots[i]] = texture_is_short(internal[i]);
+    }
+    c->tex_alloc = plan;
+    c->n_textures = new_table;
+    c->n_texels = plan.end();
+    c->classes_dirty = true; c->cutout_short_dirty = true;
+    ++c->main_epoch;  // the shadow lanes' cutout rasterisers sample the array
+
+    // ---- copy, decode: the payload once, the tables, at most four launches for every stored level of the call
+    uint64_t launches = 0;
+    std::vector<uint32_t> job_block(std::max<size_t>(job_words, 1), 0u);
+    for (int f = 0; f < texture_jobs::FAMILIES; ++f) std::copy(tables[f].block.begin(), tables[f].block.end(), job_block.begin() + job_at[f]);
+    // (the main stream is idle or busy with frames that cannot name what is written here: nothing on it has to come first -- a
+    // growth, a whole-array write and an earlier update all ended in a wait, a removal's table rows belong to hot slots)
+    HIP_TRY(c, hipMemcpyAsync(c->tex_stage.p, payload, payload_bytes, hipMemcpyHostToDevice, c->tex_stream));
+    HIP_TRY(c, hipMemcpyAsync(c->tex_jobs.p, job_block.data(), job_block.size() * 4u, hipMemcpyHostToDevice, c->tex_stream));
+    TRY(upload_texture_slots(c, touched, true));
+    uint32_t *pool = c->tex_texels.as<uint32_t>();
+    hipError_t e = hipSuccess;
+    for (int f = 0; f < texture_jobs::FAMILIES && e == hipSuccess; ++f) {
+        if (!tables[f].total_waves) continue;
+        e = (hipError_t)r3n_internal_decode_jobs((uint32_t)f, c->tex_jobs.as<uint32_t>() + job_at[f], tables[f].layout.o_first, tables[f].layout.o_inst,
+                                                 (uint32_t)tables[f].total_waves, c->tex_stage.p, pool, c->tex_stream);
+        ++launches;
+    }
+    for (uint32_t i = 0; i < n && generated && e == hipSuccess; ++i) {  // MipmapSource::Generated: level by level, behind the decode
+        const r3n_texture_desc32 &d = descs[i];
+        const uint32_t stored = d.stored_mips ? d.stored_mips : d.mips;
+        const bool is_float = internal[i].format == R3N_POOL_FLOAT;
+        uint64_t dst = internal[i].offset;
+        for (uint32_t k = 0; k < d.mips && e == hipSuccess; ++k) {
+            const uint32_t w = std::max(1u, d.width >> k), h = std::max(1u, d.height >> k);
+            if (k >= stored) {
+                const uint32_t sw = std::max(1u, d.width >> (k - 1u)), sh = std::max(1u, d.height >> (k - 1u));
+                if (is_float) {
+                    float *level = reinterpret_cast<float *>(pool + dst);
+                    e = (hipError_t)r3n_internal_generate_mip_f32(d.format, sw, sh, w, h, level - (uint64_t)sw * sh * 4u, level, c->tex_stream);
+                } else {
+                    e = (hipError_t)r3n_internal_generate_mip(internal[i].format == R3N_TEXTURE_RGBA8_UNORM_SRGB, sw, sh, w, h, pool + dst - (uint64_t)sw * sh,
+                                                              pool + dst, c->srgb8_decode.as<float>(), c->srgb_thr.as<float>(), c->tex_stream);
+                }
+                ++launches;
+            }
+            dst += (uint64_t)w * h * (is_float ? 4u : 1u);
+        }
+    }
+    const hipError_t e2 = hipStreamSynchronize(c->tex_stream);  // its own work alone; the caller owns the payload only for the duration of the call
+    if (e != hipSuccess) return fail(c, R3N_ERR_HIP, std::string("textures update: ") + hipGetErrorString(e));
+    if (e2 != hipSuccess) return fail(c, R3N_ERR_HIP, std::string("textures update: ") + hipGetErrorString(e2));
+    ++c->tex_stats.update_calls;
+    c->tex_stats.kernel_launches += launches;
+    c->tex_stats.bytes_staged += payload_bytes;
+    c->tex_stats.full_syncs += c->sync_serial - syncs_before;
+    return R3N_OK;
+}
+
+int r3n_textures_remove(r3n_ctx *c, const uint32_t *slots, uint32_t n) {
+    if (!c || (n && !slots)) return fail(c, R3N_ERR_INVALID_ARG, "textures remove: null");
+    if (!n) return R3N_OK;
+    std::vector<uint32_t> sorted(slots, slots + n);
+    std::sort(sorted.begin(), sorted.end());
+    if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) return fail(c, R3N_ERR_INVALID_ARG, "textures remove: one slot named twice");
+    for (uint32_t slot : sorted)
+        if (slot >= c->n_textures || !c->h_tex_live[slot]) return fail(c, R3N_ERR_INVALID_ARG, "textures remove: slot holds no texture (removed or never written)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    texture_note_syncs(c);
+    for (uint32_t slot : sorted) {
+        // a frame in flight may still sample the words: they are parked until the next full wait
+        c->tex_alloc.free(c->h_tex_descs[slot].offset, c->h_tex_words[slot], true);
+        c->h_tex_live[slot] = 0;
+        c->h_tex_words[slot] = 0;
+        c->h_tex_short[slot] = 0;  // a stale material id takes the general sampler
+        c->h_tex_descs[slot] = device_desc(c, slot);
+        c->h_tex_descs[slot].width = c->h_tex_descs[slot].height = 0;
+    }
+    c->classes_dirty = true; c->cutout_short_dirty = true;
+    ++c->main_epoch;
+    return upload_texture_slots(c, sorted, false);
+}
+
+int r3n_texture_stats(r3n_ctx *c, r3n_texture_counters *out, int reset) {
+    if (!c || (!out && !reset)) return fail(c, R3N_ERR_INVALID_ARG, "texture stats: null");
+    if (out) {
+        *out = c->tex_stats;
+        out->pool_words = c->tex_alloc.end();
+        out->live_words = 0;
+        for (uint32_t i = 0; i < c->n_textures && i < c->h_tex_live.size(); ++i)
+            if (c->h_tex_live[i]) out->live_words += texture_pool_words(c->h_tex_descs[i]);
+        out->free_ranges = c->tex_alloc.free_ranges();
+    }
+    if (reset) c->tex_stats = r3n_texture_counters{};
     return R3N_OK;
 }
 
@@ -3156,6 +3495,17 @@ int r3n_readback_joint_matrices(r3n_ctx *c, uint32_t first, float *dst, uint32_t
     return d2h(c, dst, c->skin_matrices.as<float>() + (size_t)first * 16, (size_t)n * 64);
 }
 
+int r3n_readback_texture_descs(r3n_ctx *c, r3n_texture_desc32 *descs, uint32_t capacity, uint32_t *n_slots) {
+    if (!c || !n_slots) return fail(c, R3N_ERR_INVALID_ARG, "readback_texture_descs: null");
+    const uint32_t n = c->n_textures;
+    *n_slots = n;
+    if (!descs || !n) return R3N_OK;  // the table's length alone
+    if (capacity < n) return fail(c, R3N_ERR_INVALID_ARG, "readback_texture_descs: buffer too small");
+    TRY(d2h(c, descs, c->tex_descs.p, (size_t)n * sizeof(r3n_texture_desc32)));
+    for (uint32_t i = 0; i < n; ++i)
+        if (i >= c->h_tex_live.size() || !c->h_tex_live[i]) descs[i].width = descs[i].height = 0;  // the device holds a 1 x 1 stand-in
+    return R3N_OK;
+}
 int r3n_readback_texels(r3n_ctx *c, uint64_t first_texel, uint32_t *rgba8, uint64_t n_texels) {
     if (!c || !rgba8 || (first_texel + n_texels) * 4 > c->tex_texels.bytes) return fail(c, R3N_ERR_INVALID_ARG, "readback_texels: range outside the texel pool");
     return d2h(c, rgba8, c->tex_texels.as<uint32_t>() + first_texel, n_texels * 4);

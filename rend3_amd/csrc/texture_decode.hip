@@ -12,6 +12,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/r3n.h"
+#include "texture_jobs.h"
+#include "vertex_gather.h"
 
 #define BC7_TABLE static __device__ const
 #include "bc7_tables.h"
@@ -183,10 +185,10 @@ __device__ void decode_bc7_block(uint64_t lo, uint64_t hi, uint32_t out[16]) {
     }
 }
 
-__global__ __launch_bounds__(256) void k_decode_blocks(uint32_t format, uint32_t w, uint32_t h, const uint32_t *__restrict__ src,
-                                                       uint32_t *__restrict__ dst) {
+// block g of a w x h level (shared by the per-level kernel and the job-table kernel below)
+__device__ __forceinline__ void decode_block_at(uint32_t format, uint32_t w, uint32_t h, const uint32_t *__restrict__ src,
+                                                uint32_t *__restrict__ dst, uint32_t g) {
     const uint32_t bw = (w + 3u) / 4u, bh = (h + 3u) / 4u;
-    const uint32_t g = blockIdx.x * 256u + threadIdx.x;
     if (g >= bw * bh) return;
     const uint32_t bx = g % bw, by = g / bw;
     uint32_t px[16];
@@ -249,9 +251,14 @@ __global__ __launch_bounds__(256) void k_decode_blocks(uint32_t format, uint32_t
     }
 }
 
+__global__ __launch_bounds__(256) void k_decode_blocks(uint32_t format, uint32_t w, uint32_t h, const uint32_t *__restrict__ src,
+                                                       uint32_t *__restrict__ dst) {
+    decode_block_at(format, w, h, src, dst, blockIdx.x * 256u + threadIdx.x);
+}
+
 // uncompressed sources: one thread per texel
-__global__ __launch_bounds__(256) void k_expand_texels(uint32_t format, uint64_t n, const uint8_t *__restrict__ src, uint32_t *__restrict__ dst) {
-    const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+__device__ __forceinline__ void expand_texel_at(uint32_t format, uint64_t n, const uint8_t *__restrict__ src, uint32_t *__restrict__ dst,
+                                                uint64_t i) {
     if (i >= n) return;
     uint32_t v;
     if (format == R3N_TEXTURE_R8_UNORM) v = pack(src[i], 0u, 0u, 255u);
@@ -262,6 +269,9 @@ __global__ __launch_bounds__(256) void k_expand_texels(uint32_t format, uint64_t
                 ? ((t & 0xFF00FF00u) | ((t >> 16) & 0xFFu) | ((t & 0xFFu) << 16)) : t;
     }
     dst[i] = v;
+}
+__global__ __launch_bounds__(256) void k_expand_texels(uint32_t format, uint64_t n, const uint8_t *__restrict__ src, uint32_t *__restrict__ dst) {
+    expand_texel_at(format, n, src, dst, (uint64_t)blockIdx.x * 256u + threadIdx.x);
 }
 
 // MipmapSource::Generated (rend3/src/util/mipmap.rs:139-236 + rend3/shaders/mipmap.wgsl, K11): level l is a blit of
@@ -332,8 +342,8 @@ __device__ inline float snorm8(uint32_t c) { return fmaxf((float)(int)(int8_t)c 
 __device__ inline float snorm16(uint32_t c) { return fmaxf((float)(int)(int16_t)c / 32767.0f, -1.0f); }
 
 // one thread per texel; `src` is read through the narrowest aligned type of the format
-__global__ __launch_bounds__(256) void k_expand_texels_f32(uint32_t format, uint64_t n, const uint8_t *__restrict__ src, float4 *__restrict__ dst) {
-    const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+__device__ __forceinline__ void expand_texel_f32_at(uint32_t format, uint64_t n, const uint8_t *__restrict__ src, float4 *__restrict__ dst,
+                                                    uint64_t i) {
     if (i >= n) return;
     const uint16_t *s16 = reinterpret_cast<const uint16_t *>(src);
     const uint32_t *s32 = reinterpret_cast<const uint32_t *>(src);
@@ -360,6 +370,9 @@ __global__ __launch_bounds__(256) void k_expand_texels_f32(uint32_t format, uint
     }
     }
     dst[i] = o;
+}
+__global__ __launch_bounds__(256) void k_expand_texels_f32(uint32_t format, uint64_t n, const uint8_t *__restrict__ src, float4 *__restrict__ dst) {
+    expand_texel_f32_at(format, n, src, dst, (uint64_t)blockIdx.x * 256u + threadIdx.x);
 }
 
 // RGTC signed block -> 16 floats (snorm8 endpoints, integer ordering, palette interpolated in f32)
@@ -480,10 +493,9 @@ __device__ void decode_bc6h_block(uint64_t lo, uint64_t hi, bool is_signed, floa
     }
 }
 
-__global__ __launch_bounds__(256) void k_decode_blocks_f32(uint32_t format, uint32_t w, uint32_t h, const uint32_t *__restrict__ src,
-                                                           float4 *__restrict__ dst) {
+__device__ __forceinline__ void decode_block_f32_at(uint32_t format, uint32_t w, uint32_t h, const uint32_t *__restrict__ src,
+                                                    float4 *__restrict__ dst, uint32_t g) {
     const uint32_t bw = (w + 3u) / 4u, bh = (h + 3u) / 4u;
-    const uint32_t g = blockIdx.x * 256u + threadIdx.x;
     if (g >= bw * bh) return;
     const uint32_t bx = g % bw, by = g / bw;
     const bool small = format == R3N_TEXTURE_BC4_R_SNORM;
@@ -508,6 +520,49 @@ __global__ __launch_bounds__(256) void k_decode_blocks_f32(uint32_t format, uint
             if (bx * 4u + x < w) dst[(size_t)ty * w + bx * 4u + x] = px[y * 4u + x];
     }
 }
+__global__ __launch_bounds__(256) void k_decode_blocks_f32(uint32_t format, uint32_t w, uint32_t h, const uint32_t *__restrict__ src,
+                                                           float4 *__restrict__ dst) {
+    decode_block_f32_at(format, w, h, src, dst, blockIdx.x * 256u + threadIdx.x);
+}
+
+// ---- job-table kernels (r3n_textures_update): ONE launch per family decodes every stored level of every texture of the call.
+// Wave slot -> job through the wave map of the vertex stages (texture_jobs.h, vertex_gather.h): the record is wave-uniform and
+// comes through scalar registers; lane l of a job's k-th wave slot takes unit 64 k + l (a 4x4 block, or a texel).  The per-unit
+// work is the functions above, so every word is the per-level kernels'.  Launched as (total_waves + 3) / 4 blocks of 256.
+using texture_jobs::Job;
+struct JobArgs {
+    const Job *jobs;
+    const uint32_t *wave_job, *wave_first;
+    uint32_t total_waves;
+    const uint8_t *staged;  // the call's payload
+    uint32_t *pool;
+};
+#define JOB_PROLOGUE                                                                                                      \
+    const uint32_t wv = vertex_gather::wave_index();                                                                     \
+    if (wv >= a.total_waves) return;                                                                                      \
+    uint32_t unit;                                                                                                        \
+    const Job j = vertex_gather::wave_record(wv, a.jobs, a.wave_job, a.wave_first, texture_jobs::UNITS_PER_WAVE, unit);   \
+    if (unit >= j.units) return;                                                                                          \
+    const uint8_t *src = a.staged + (((uint64_t)j.src_hi << 32) | j.src_lo);                                              \
+    uint32_t *dst = a.pool + j.dst
+
+__global__ __launch_bounds__(256) void k_decode_block_jobs(JobArgs a) {
+    JOB_PROLOGUE;
+    decode_block_at(j.format, j.w, j.h, reinterpret_cast<const uint32_t *>(src), dst, unit);
+}
+__global__ __launch_bounds__(256) void k_expand_texel_jobs(JobArgs a) {
+    JOB_PROLOGUE;
+    expand_texel_at(j.format, j.units, src, dst, unit);
+}
+__global__ __launch_bounds__(256) void k_decode_block_jobs_f32(JobArgs a) {
+    JOB_PROLOGUE;
+    decode_block_f32_at(j.format, j.w, j.h, reinterpret_cast<const uint32_t *>(src), reinterpret_cast<float4 *>(dst), unit);
+}
+__global__ __launch_bounds__(256) void k_expand_texel_jobs_f32(JobArgs a) {
+    JOB_PROLOGUE;
+    expand_texel_f32_at(j.format, j.units, src, reinterpret_cast<float4 *>(dst), unit);
+}
+#undef JOB_PROLOGUE
 
 
 // MipmapSource::Generated for the float-decoded formats the loader generates chains for (single-level R16Float / Rg16Float /
@@ -634,6 +689,29 @@ extern "C" int r3n_internal_decode_level_f32(uint32_t format, uint32_t w, uint32
         const uint64_t n = (uint64_t)w * h;
         hipLaunchKernelGGL(k_expand_texels_f32, dim3((unsigned)((n + 255u) / 256u)), dim3(256), 0, stream, format, n,
                            static_cast<const uint8_t *>(src), reinterpret_cast<float4 *>(dst));
+    }
+    return (int)hipGetLastError();
+}
+
+// One family's job table (texture_jobs.h; `block` = its device copy, `o_first` / `o_inst` = the layout's word offsets): every
+// stored level of the call in ONE launch.  staged = the call's payload on the device, pool = the texel pool.
+extern "C" int r3n_internal_decode_jobs(uint32_t family, const uint32_t *block, uint64_t o_first, uint64_t o_inst, uint32_t total_waves,
+                                        const void *staged, uint32_t *pool, hipStream_t stream) {
+    if (!total_waves) return (int)hipSuccess;
+    JobArgs a;
+    a.jobs = reinterpret_cast<const Job *>(block);
+    a.wave_first = block + o_first;
+    a.wave_job = block + o_inst;
+    a.total_waves = total_waves;
+    a.staged = static_cast<const uint8_t *>(staged);
+    a.pool = pool;
+    const dim3 grid((total_waves + 3u) / 4u), wg(256);
+    switch (family) {
+    case texture_jobs::RGBA8_BLOCK: hipLaunchKernelGGL(k_decode_block_jobs, grid, wg, 0, stream, a); break;
+    case texture_jobs::RGBA8_EXPAND: hipLaunchKernelGGL(k_expand_texel_jobs, grid, wg, 0, stream, a); break;
+    case texture_jobs::F32_BLOCK: hipLaunchKernelGGL(k_decode_block_jobs_f32, grid, wg, 0, stream, a); break;
+    case texture_jobs::F32_EXPAND: hipLaunchKernelGGL(k_expand_texel_jobs_f32, grid, wg, 0, stream, a); break;
+    default: return (int)hipErrorInvalidValue;
     }
     return (int)hipGetLastError();
 }

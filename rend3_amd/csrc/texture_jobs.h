@@ -1,0 +1,74 @@
+// texture_jobs.h -- host side of the batched texture decode (texture_decode.hip, r3n_internal_decode_jobs): the job table that
+// lets ONE launch per kernel family decode every stored level of every texture of an r3n_textures_update call.  Plain C++17, no
+// HIP, no context: tests/texel_alloc_check.cpp compiles it alone.
+//
+// A job is one stored level.  Its work units are its 4x4 blocks (block formats: one lane decodes one block) or its texels
+// (uncompressed formats: one lane expands one texel); a wave slot takes 64 consecutive units of ONE job, so the job record is
+// wave-uniform and a job's last wave slot is partly idle.  The map from wave slot to job is the wave map of the vertex stages
+// (vertex_block.h lays the block out, vertex_gather.h reads it): records | wave_first | wave_instance.
+#pragma once
+#include <stdint.h>
+
+#include <cstring>
+#include <vector>
+
+#include "../../include/r3n.h"
+#include "vertex_block.h"
+
+namespace texture_jobs {
+
+enum Family { RGBA8_BLOCK = 0, RGBA8_EXPAND = 1, F32_BLOCK = 2, F32_EXPAND = 3, FAMILIES = 4 };
+
+// one stored level; 8 words, so that a wave reads it as one scalar load
+struct Job {
+    uint32_t format, w, h;    // R3N_TEXTURE_* of the source, the level's extent
+    uint32_t units;           // blocks or texels of the level
+    uint32_t src_lo, src_hi;  // byte offset of the level in the staged payload
+    uint32_t dst;             // first pool word of the level
+    uint32_t pad;             // (the record is a power-of-two count of words; the work-unit prefix is the wave map's wave_first)
+};
+static_assert(sizeof(Job) == 32, "a job record is 8 words");
+constexpr uint32_t REC_WORDS = sizeof(Job) / 4u, UNITS_PER_WAVE = 64u;
+
+inline bool is_float(uint32_t format) { return format >= R3N_TEXTURE_R8_SNORM && format < R3N_TEXTURE_FORMAT_COUNT; }
+inline bool is_block(uint32_t format) {
+    return is_float(format) ? format >= R3N_TEXTURE_BC4_R_SNORM : format >= R3N_TEXTURE_BC1_RGBA_UNORM;
+}
+inline Family family_of(uint32_t format) {
+    return is_float(format) ? (is_block(format) ? F32_BLOCK : F32_EXPAND) : (is_block(format) ? RGBA8_BLOCK : RGBA8_EXPAND);
+}
+inline uint64_t units_of(uint32_t format, uint32_t w, uint32_t h) {
+    return is_block(format) ? (uint64_t)((w + 3u) / 4u) * ((h + 3u) / 4u) : (uint64_t)w * h;
+}
+
+// one family's upload: the block (vertex_block layout over `jobs`) and its totals
+struct Table {
+    std::vector<Job> jobs;
+    std::vector<uint32_t> block;
+    vertex_block::layout layout{};
+    uint64_t total_waves = 0, total_units = 0;
+};
+
+// appends one stored level to its family's table
+inline void add_level(Table tables[FAMILIES], uint32_t format, uint32_t w, uint32_t h, uint64_t src, uint32_t dst) {
+    Table &t = tables[family_of(format)];
+    const uint64_t units = units_of(format, w, h);  // < 2^32: extents are at most 65535
+    t.jobs.push_back(Job{format, w, h, (uint32_t)units, (uint32_t)src, (uint32_t)(src >> 32), dst, 0u});
+    t.total_units += units;
+    t.total_waves += vertex_block::waves(units, UNITS_PER_WAVE);
+}
+
+// lays every family's block out; false: a family has more wave slots or units than its kernel counts in 32 bits
+inline bool finish(Table tables[FAMILIES]) {
+    for (int f = 0; f < FAMILIES; ++f) {
+        Table &t = tables[f];
+        if (t.total_waves > vertex_block::MAX_WAVES || t.total_units > 0xFFFFFFFFull) return false;
+        const uint32_t n = (uint32_t)t.jobs.size();
+        t.layout = vertex_block::lay_out(t.block, n, REC_WORDS, t.total_waves,
+                                         [&](uint32_t i) { return vertex_block::waves(t.jobs[i].units, UNITS_PER_WAVE); });
+        if (n) std::memcpy(t.block.data(), t.jobs.data(), (size_t)n * sizeof(Job));
+    }
+    return true;
+}
+
+}  // namespace texture_jobs

@@ -195,10 +195,19 @@ class EvalOutput:
 class Renderer:
     """World bookkeeping feeding the object/mesh/material/light buffers of the C ABI."""
 
-    def __init__(self, handedness=host.LEFT, aspect_ratio=None, device=0, max_big_items=None, blend_sort="host"):
+    def __init__(self, handedness=host.LEFT, aspect_ratio=None, device=0, max_big_items=None, blend_sort="host", texture_upload="whole"):
         self.lib = _ffi.lib()
         if blend_sort not in ("host", "gpu"):
             raise ValueError("blend_sort: 'host' or 'gpu'")
+        if texture_upload not in ("whole", "stream"):
+            raise ValueError("texture_upload: 'whole' or 'stream'")
+        # how 2D textures reach the device: "whole" = the bindless array is re-sent when it changed (r3n_textures_write_encoded);
+        # "stream" = single entries are added, replaced and removed in place (r3n_textures_update / r3n_textures_remove,
+        # TextureManager::add / remove), the host keeps no copy of what it sent
+        self._texture_upload = texture_upload
+        self._tex_live = []       # "stream": per slot, True while the slot holds a texture (queued ones included)
+        self._tex_queue = []      # "stream": (slot, desc row without offset, bytes) not yet sent
+        self._tex_removals = []   # "stream": slots whose removal is not yet sent
         # where the transparent pass's back-to-front order is sorted: "host" = host.blend_draw_order + r3n_blend_order_write every
         # frame; "gpu" = the blend set goes up when the world changes (r3n_blend_objects_write), r3n_blend_sort orders it per frame
         self.blend_sort = blend_sort
@@ -594,10 +603,23 @@ class Renderer:
         mats = np.ascontiguousarray(np.concatenate([sk["matrices"] for sk in self.skeletons]))
         return self._skin_inputs, mats
 
+    @property
+    def texture_upload(self):
+        return self._texture_upload
+
+    @texture_upload.setter
+    def texture_upload(self, mode):
+        if mode not in ("whole", "stream"):
+            raise ValueError("texture_upload: 'whole' or 'stream'")
+        if mode != self._texture_upload and (len(self.tex_descs) or self._tex_live):
+            raise ValueError("texture_upload cannot change once textures exist")
+        self._texture_upload = mode
+
     def add_texture_2d(self, rgba8, srgb=True, mip_count=1, mip_source="uploaded"):
         """Renderer::add_texture_2d with Texture{data, format, size, mip_count, mip_source}: rgba8 = (H, W, 4) u8;
         format Rgba8UnormSrgb | Rgba8Unorm; mip_count int or "maximum"; mip_source "uploaded" | "generated".
-        The whole bindless array is re-sent (r3n_textures_write_encoded).  Returns the texture handle (index)."""
+        texture_upload="whole": the whole bindless array is re-sent (r3n_textures_write_encoded); "stream": the entry alone is sent
+        (r3n_textures_update) and takes the lowest free slot.  Returns the texture handle (index)."""
         data, w, h, mips, stored = host.prepare_texture(rgba8, srgb, mip_count, mip_source)
         return self._append_texture(data, w, h, mips, 1 if srgb else 0, stored)
 
@@ -619,6 +641,15 @@ class Renderer:
         return self._append_texture(np.frombuffer(b"".join(levels), dtype=np.uint8), width, height, len(levels), fmt)
 
     def _append_texture(self, data_u8, w, h, mips, fmt, stored=0):
+        if self._texture_upload == "stream":
+            # the lowest free slot (TextureManager's handle allocator); sent with everything else queued when the next frame is
+            # evaluated (TextureManager::evaluate)
+            slot = self._tex_live.index(False) if False in self._tex_live else len(self._tex_live)
+            if slot == len(self._tex_live):
+                self._tex_live.append(True)
+            self._tex_live[slot] = True
+            self._tex_queue.append((slot, (w, h, mips, fmt, stored), np.array(data_u8, dtype=np.uint8)))
+            return slot
         start = (self.tex_used + 3) & ~3  # level 0 of every texture starts on a 4-byte boundary
         end = start + len(data_u8)
         if end > len(self.tex_pool):
@@ -632,7 +663,39 @@ class Renderer:
         self._tex_dirty = True  # the array is re-sent once, when the next frame is evaluated (TextureManager::evaluate)
         return len(self.tex_descs) - 1
 
+    def remove_texture(self, handle):
+        """TextureManager::remove (the reference drops a texture with its handle): the slot's texels become reusable, the handle
+        may be handed out again.  texture_upload="stream" only.  Materials that still name the handle read an unspecified texel."""
+        if self._texture_upload != "stream":
+            raise ValueError("remove_texture needs Renderer(texture_upload='stream'): the whole-array path has no removal")
+        handle = int(handle)
+        if not (0 <= handle < len(self._tex_live)) or not self._tex_live[handle]:
+            raise ValueError(f"remove_texture: handle {handle} holds no texture")
+        if any(slot == handle for slot, _, _ in self._tex_queue):
+            self._flush_textures()  # it was never sent: send it, then remove it (keeps the table the library's)
+        self._tex_live[handle] = False
+        self._tex_removals.append(handle)
+
     def _flush_textures(self):
+        if self._tex_removals:
+            slots = np.array(self._tex_removals, dtype=np.uint32)
+            self._check(self.lib.r3n_textures_remove(self.ctx, _ffi.ptr(slots), len(slots)), "r3n_textures_remove")
+            self._tex_removals = []
+        if self._tex_queue:
+            slots = np.array([q[0] for q in self._tex_queue], dtype=np.uint32)
+            descs = np.zeros((len(slots), 8), dtype=np.uint32)
+            at, parts = 0, []
+            for row, (_, d, data) in zip(descs, self._tex_queue):
+                row[0], row[1:6] = at, d
+                parts.append(data)
+                pad = -len(data) & 3  # level 0 of every texture starts on a 4-byte boundary
+                if pad:
+                    parts.append(np.zeros(pad, dtype=np.uint8))
+                at += len(data) + pad
+            payload = np.ascontiguousarray(np.concatenate(parts)) if at else np.zeros(4, dtype=np.uint8)
+            self._check(self.lib.r3n_textures_update(self.ctx, _ffi.ptr(slots), _ffi.ptr(descs), len(slots), _ffi.ptr(payload), at),
+                        "r3n_textures_update")
+            self._tex_queue = []  # nothing sent is kept on the host
         if self._tex_dirty:
             self._check(self.lib.r3n_textures_write_encoded(self.ctx, _ffi.ptr(self.tex_descs), len(self.tex_descs),
                                                             _ffi.ptr(self.tex_pool), self.tex_used), "r3n_textures_write_encoded")
@@ -1193,6 +1256,22 @@ class Renderer:
         (r3n_textures_write_encoded); the gaps are dropped here."""
         from . import containers
         self._flush_textures()
+        if self._texture_upload == "stream":
+            descs = self.readback_texture_descs()
+            parts = []
+            for d in descs:
+                if d[1] == 0:  # a removed slot
+                    parts.append(None)
+                    continue
+                fl = int(d[4]) == 2  # R3N_POOL_FLOAT
+                n = sum(max(1, int(d[1]) >> k) * max(1, int(d[2]) >> k) for k in range(int(d[3]))) * (4 if fl else 1)
+                words = np.zeros(n, dtype=np.uint32)
+                self._check(self.lib.r3n_readback_texels(self.ctx, int(d[0]), _ffi.ptr(words), n), "r3n_readback_texels")
+                parts.append(words.view(np.float32).reshape(-1, 4) if fl else words.view(np.uint8).reshape(-1, 4))
+            if per_texture:
+                return parts
+            live = [p.view(np.uint8).reshape(-1, 4) for p in parts if p is not None]
+            return np.concatenate(live) if live else np.zeros((0, 4), dtype=np.uint8)
         is_float = [containers.is_float_format(int(d[4])) for d in self.tex_descs]
         sizes = [sum(max(1, int(d[1]) >> k) * max(1, int(d[2]) >> k) for k in range(int(d[3]))) * (4 if fl else 1)
                  for d, fl in zip(self.tex_descs, is_float)]
@@ -1208,6 +1287,24 @@ class Renderer:
         if per_texture:
             return [p.view(np.float32).reshape(-1, 4) if fl else p.view(np.uint8).reshape(-1, 4) for p, fl in zip(parts, is_float)]
         return (np.concatenate(parts) if parts else pool[:0]).view(np.uint8).reshape(-1, 4)
+
+    def readback_texture_descs(self):
+        """The texture table as the device holds it (r3n_readback_texture_descs): (n, 8) u32 rows of r3n_texture_desc32 -- offset in
+        pool words, width, height, mips, pool format class (0 RGBA8, 1 RGBA8 sRGB, 2 four f32 per texel); removed slots have
+        width = height = 0."""
+        self._flush_textures()
+        n = ctypes.c_uint32(0)
+        self._check(self.lib.r3n_readback_texture_descs(self.ctx, None, 0, ctypes.byref(n)), "r3n_readback_texture_descs")  # the length alone
+        descs = np.zeros((n.value, 8), dtype=np.uint32)
+        if n.value:
+            self._check(self.lib.r3n_readback_texture_descs(self.ctx, _ffi.ptr(descs), n.value, ctypes.byref(n)), "r3n_readback_texture_descs")
+        return descs
+
+    def texture_stats(self, reset=False):
+        """Counters of the streamed texture path (r3n_texture_stats) as a dict; reset=True zeroes them after the read."""
+        out = _ffi.TextureCounters()
+        self._check(self.lib.r3n_texture_stats(self.ctx, ctypes.byref(out), 1 if reset else 0), "r3n_texture_stats")
+        return {name: int(getattr(out, name)) for name, _ in _ffi.TextureCounters._fields_}
 
     def readback_hiz(self, width, height):
         n = 0

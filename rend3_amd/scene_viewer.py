@@ -83,6 +83,9 @@ def add_arguments(ap):
     ap.add_argument("--blend-sort", choices=("host", "gpu"), default="host",
                     help="where the transparent pass's back-to-front order is sorted (not in the reference, whose CPU batcher sorts): "
                          "host = every frame on the CPU, gpu = r3n_blend_sort")
+    ap.add_argument("--texture-upload", choices=("whole", "stream"), default="whole",
+                    help="how 2D textures reach the device: whole = the bindless array is re-sent when it changed, stream = single "
+                         "entries are added and removed in place (r3n_textures_update), as the reference's TextureManager does")
     ap.add_argument("--morph-normals", choices=("base", "recompute"), default="base",
                     help="normals of morphed primitives without NORMAL: base = those of the bind shape under any weights, "
                          "recompute = recomputed from the morphed positions on the GPU (r3n_vertex_normals)")
@@ -109,7 +112,8 @@ def settings_from(args):
                 shadow_resolution=args.shadow_resolution, enable_directional=not args.gltf_disable_directional_lights,
                 camera=args.camera or DEFAULT_CAMERA, skybox=getattr(args, "skybox", None),
                 blend_sort=getattr(args, "blend_sort", "host"), morph_normals=getattr(args, "morph_normals", "base"),
-                build_tangents=getattr(args, "build_tangents", False), morph_tangents=getattr(args, "morph_tangents", "base"))
+                build_tangents=getattr(args, "build_tangents", False), morph_tangents=getattr(args, "morph_tangents", "base"),
+                texture_upload=getattr(args, "texture_upload", "whole"))
 
 
 def default_settings(**over):
@@ -159,6 +163,10 @@ def build(r, hm, mk, settings):
         if not hasattr(r, "blend_sort"):
             raise ValueError("--blend-sort gpu: this renderer has no device sort")
         r.blend_sort = settings["blend_sort"]
+    if settings.get("texture_upload", "whole") != "whole":  # (a renderer that cannot stream textures fails here)
+        if not hasattr(r, "texture_upload"):
+            raise ValueError("--texture-upload stream: this renderer re-sends the whole array")
+        r.texture_upload = settings["texture_upload"]
     light = None
     if settings["directional_light"] is not None:  # setup (mod.rs:463-472)
         light = r.add_directional_light(color=(1.0, 1.0, 1.0), intensity=settings["directional_light_intensity"],
