@@ -378,7 +378,9 @@ int r3n_blend_objects_write(r3n_ctx *ctx, const uint32_t *slots, const float *lo
  *      mode) it does nothing and returns R3N_OK. */
 int r3n_blend_sort(r3n_ctx *ctx, const float camera_location[3]);
 /*      DirectionalLightManager / PointLightManager buffers, byte-identical:
- *      u32 count @0, array @16 (stride 128 / 32): rend3/src/managers/directional.rs:31-53,135-153, point.rs:14-74 */
+ *      u32 count @0, array @16 (stride 128 / 32): rend3/src/managers/directional.rs:31-53,135-153, point.rs:14-74.
+ *      At most 16 directional and 256 point lights; a longer list (R3N_ERR_UNSUPPORTED) or a count beyond its buffer
+ *      (R3N_ERR_INVALID_ARG) is refused with a message that names the list, and a refused call changes neither list. */
 int r3n_lights_write(r3n_ctx *ctx, const void *directional_buffer, uint64_t directional_bytes,
                      const void *point_buffer, uint64_t point_bytes);
 

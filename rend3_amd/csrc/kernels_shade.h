@@ -722,23 +722,28 @@ R3N_DEV void fragment_stage(const ShadeArgs &a, const LdsDirLight *s_dir, const 
 #pragma unroll
         for (int c = 0; c < 3; ++c) vv[c] = -vv[c];
         float color[3] = {px.emissive[0], px.emissive[1], px.emissive[2]};
-        // A fully occluded light (shadow * ao == 0) adds (finite) * 0 = +-0 when every factor of surface_shading is
-        // finite: skip its BRDF.  Finite is guaranteed by: all pixel inputs finite (the sum of magnitudes is finite;
-        // NaN fails the comparison), roughness^2 >= 1e-9 (D <= 1/(pi a^2) <= 3.2e17 without underflow of f^2,
-        // V <= 0.5/(1e-5 a) <= 5e13, Fresnel <= 2) and |light colour| <= 1e6 (checked when the lights are staged).
+        // A light whose k = nol * shadow * ao is zero adds (fd + fr) * colour * 0, which is +-0 only while (fd + fr) * colour is
+        // finite (inf * 0 and NaN * 0 are NaN, and the final max() then shows ambient * albedo): its BRDF may be skipped under
+        //   roughness a in [1e-3, 1e3]: f = (noh a^2 - noh) noh + 1 is 1 - noh^2 (1 - a^2) >= a^2 up to three roundings of values
+        //     <= 1 (2e-7 in all), so with a^2 >= 1e-6 f >= 0.8 a^2 and D = a^2 / (pi f^2) <= 5e5; above a = 1 f >= 1 and
+        //     D <= a^2 / pi <= 3.2e5.  (Below a^2 = 6e-8 the a^2 is absorbed and f is exactly 0 where noh rounds to 1: D = inf.)
+        //     Each square root of V is >= 0.9 min(a, 1) and nov >= 1e-5, so V <= 0.5 / (1e-5 * 0.9e-3) <= 5.6e7;
+        //   the magnitudes of the pixel inputs sum to less than 1e18 (NaN fails the comparison): |F| <= 2 |f0| + 1 <= 2e18 + 1
+        //     (f90 and x5 are in [0, 1]), fd <= 3.2e17, so |fd + fr| <= 5e5 * 5.6e7 * 2e18 + 3.2e17 <= 6e31;
+        //   |light colour| <= 1e6 and |l| <= 2 (`sane`, checked when the lights are staged): |(fd + fr) * colour| <= 6e37.
         const float mag = (((fabsf(px.normal[0]) + fabsf(px.normal[1])) + (fabsf(px.normal[2]) + fabsf(vv[0]))) +
                            ((fabsf(vv[1]) + fabsf(vv[2])) + (fabsf(px.f0[0]) + fabsf(px.f0[1])))) +
                           (((fabsf(px.f0[2]) + fabsf(px.diffuse[0])) + (fabsf(px.diffuse[1]) + fabsf(px.diffuse[2]))) + fabsf(px.ao));
-        const bool skip_ok = px.roughness >= 1e-9f && px.roughness <= 1e9f && mag < 1e30f;
+        const bool skip_ok = px.roughness >= 1e-3f && px.roughness <= 1e3f && mag < 1e18f;
         const BrdfPixel pre_v = brdf_pixel<M>(px, vv);
         const BrdfPixel *pre = &pre_v;
         for (uint32_t i = 0; i < n_dir; ++i) {
             const LdsDirLight L = load_light<LdsDirLight, SL>(s_dir + i);
-            // surface_shading scales by k = nol * occlusion.  With nol == 0 and roughness > 0 every factor is finite
-            // (D <= 1/(pi a^2), V <= 0.5/(nov a), nov >= 1e-5), so the light adds exactly +0: skip the shadow lookup
-            // and the BRDF.  `+= 0.0f` keeps the -0 -> +0 behaviour of the full expression.
+            // surface_shading scales by k = nol * occlusion.  With nol == 0 the light adds +0 under the conditions above (the
+            // occlusion is finite: shadow in [0, 1], ao < 1e18): skip the shadow lookup and the BRDF.  `+= 0.0f` keeps the
+            // -0 -> +0 behaviour of the full expression.
             const float nl_raw = dot3m<M>(px.normal, L.l);
-            if (px.roughness > 0.0f && nl_raw == nl_raw && sat(nl_raw) == 0.0f) {  // (a NaN normal must stay NaN)
+            if (skip_ok && L.sane != 0.0f && nl_raw == nl_raw && sat(nl_raw) == 0.0f) {  // (a NaN normal must stay NaN)
 #pragma unroll
                 for (int c = 0; c < 3; ++c) color[c] += 0.0f;
                 continue;

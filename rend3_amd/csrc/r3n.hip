@@ -1640,19 +1640,23 @@ int r3n_lights_write(r3n_ctx *c, const void *dir, uint64_t dir_bytes, const void
     if (!c) return R3N_ERR_INVALID_ARG;
     // kept on the host; r3n_frame_begin uploads them into the frame's own copy (frames in flight: the previous frame's
     // resolve may still be reading its lights)
-    auto take = [&](std::vector<uint8_t> &h, const void *src, uint64_t bytes, uint32_t stride, uint32_t cap) -> int {
+    auto take = [&](std::vector<uint8_t> &h, const char *list, const void *src, uint64_t bytes, uint32_t stride, uint32_t cap) -> int {
         if (!src || bytes < 16) { h.assign(16, 0); return R3N_OK; }
         uint32_t count;
         std::memcpy(&count, src, 4);
-        if ((uint64_t)count * stride + 16 > bytes) return fail(c, R3N_ERR_INVALID_ARG, "lights write: count exceeds buffer");
-        if (count > cap) return fail(c, R3N_ERR_UNSUPPORTED, "lights write: more lights than the LDS light list holds");
+        if ((uint64_t)count * stride + 16 > bytes) return fail(c, R3N_ERR_INVALID_ARG, std::string("lights write: ") + list + " light list: count exceeds buffer");
+        if (count > cap) return fail(c, R3N_ERR_UNSUPPORTED, std::string("lights write: ") + list + " light list: more lights than the LDS light list holds");
         h.assign(static_cast<const uint8_t *>(src), static_cast<const uint8_t *>(src) + 16u + (size_t)count * stride);  // what the shader reads: count + array
         return R3N_OK;
     };
-    const std::vector<uint8_t> old_dir = c->h_dir, old_point = c->h_point;
-    TRY(take(c->h_dir, dir, dir_bytes, 128, R3N_MAX_DIR_LIGHTS));
-    TRY(take(c->h_point, point, point_bytes, 32, R3N_MAX_POINT_LIGHTS));
-    if (old_dir != c->h_dir || old_point != c->h_point) ++c->lights_version;  // unchanged lights: nothing to upload
+    // both lists are validated before either is committed: a refused call leaves the context's lights as they were (the
+    // directional list goes up every frame, so a half-taken call would light the next frame with it)
+    std::vector<uint8_t> new_dir, new_point;
+    TRY(take(new_dir, "directional", dir, dir_bytes, 128, R3N_MAX_DIR_LIGHTS));
+    TRY(take(new_point, "point", point, point_bytes, 32, R3N_MAX_POINT_LIGHTS));
+    if (new_dir != c->h_dir || new_point != c->h_point) ++c->lights_version;  // unchanged lights: nothing to upload
+    c->h_dir.swap(new_dir);
+    c->h_point.swap(new_point);
     return R3N_OK;
 }
 
