@@ -307,7 +307,11 @@ int r3n_textures_write(r3n_ctx *ctx, const r3n_texture_desc32 *descs, uint32_t n
  *      back in ITS OWN format (block-compressed levels: ceil(w/4) x ceil(h/4) blocks, 8 or 16 B each), desc.offset =
  *      BYTE offset of level 0 in `payload`.  The library expands / decodes everything on the GPU into its RGBA8 texel
  *      pool (the texture unit's job in the reference: formats go straight to wgpu, rend3/src/managers/texture.rs:59-
- *      150).  Snorm / float / 16-bit / ETC2 / ASTC / BC6H formats -> R3N_ERR_UNSUPPORTED. */
+ *      150).  Snorm / float / 16-bit / ETC2 / ASTC / BC6H formats -> R3N_ERR_UNSUPPORTED.  Every stored level of the call is
+ *      decoded by at most four launches, one per kernel family, as in r3n_textures_update; more than 2^31 wave slots (64 blocks
+ *      or texels of one level each) in one family -> R3N_ERR_CAPACITY with nothing changed, which takes a pool near the 2^32-word
+ *      limit filled with one-texel levels.  The call waits for every frame in flight first and returns when its work has run; its
+ *      staging memory is freed before it returns. */
 int r3n_textures_write_encoded(r3n_ctx *ctx, const r3n_texture_desc32 *descs, uint32_t n_textures, const void *payload,
                                uint64_t payload_bytes);
 /*      TextureManager::add (rend3/src/managers/texture.rs: one texture per handle, handed over while frames are being drawn), for n

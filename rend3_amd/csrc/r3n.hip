@@ -1160,6 +1160,8 @@ static TextureArgs texture_args(r3n_ctx *c) {
     return t;
 }
 
+// pool words per texel of a descriptor as the device holds it; the levels themselves are walked by texture_jobs::level_of alone
+static uint32_t words_per_texel(const r3n_texture_desc32 &d) { return d.format == R3N_POOL_FLOAT ? 4u : 1u; }
 // First word (pool index) of every level of every texture: R3N_TEX_LEVELS entries per texture, so that the sampler does not
 // walk the chain.  `descs` = the descriptors as the device holds them (offsets in pool words; a texel is one word, or four
 // for R3N_POOL_FLOAT textures).
@@ -1167,7 +1169,7 @@ static void level_row(const r3n_texture_desc32 &d, uint32_t *row) {
     uint64_t at = d.offset;
     for (uint32_t k = 0; k < R3N_TEX_LEVELS; ++k) {
         row[k] = (uint32_t)at;
-        if (k < d.mips) at += (uint64_t)std::max(1u, d.width >> k) * std::max(1u, d.height >> k) * (d.format == R3N_POOL_FLOAT ? 4u : 1u);
+        if (k < d.mips) at += texture_jobs::level_of(d.width, d.height, k, words_per_texel(d)).words;
     }
 }
 // which textures the sampler's short path covers (texture.h tex_sample_grad): power-of-two extents, RGBA8 pool texels
@@ -1177,10 +1179,11 @@ static uint8_t texture_is_short(const r3n_texture_desc32 &d) {
     // shift by 32; it goes to the general sampler instead)
     return (w && h && ((w & (w - 1u)) | (h & (h - 1u))) == 0u && (uint64_t)w * h <= (1ull << 29) && d.format < R3N_POOL_FLOAT) ? 1 : 0;
 }
-static uint64_t texture_pool_words(const r3n_texture_desc32 &d) {
-    uint64_t words = 0;
-    for (uint32_t k = 0; k < d.mips; ++k) words += (uint64_t)std::max(1u, d.width >> k) * std::max(1u, d.height >> k) * (d.format == R3N_POOL_FLOAT ? 4u : 1u);
-    return words;
+static uint64_t texture_pool_words(const r3n_texture_desc32 &d) { return texture_jobs::chain_words(d.width, d.height, d.mips, words_per_texel(d)); }
+// the extent-and-mips check of every texture call (`what` names the call in the message)
+static int check_chain(r3n_ctx *c, const std::string &what, const r3n_texture_desc32 &d) {
+    const char *fault = texture_jobs::chain_fault(d.width, d.height, d.mips);
+    return fault ? fail(c, R3N_ERR_INVALID_ARG, what + ": " + fault) : R3N_OK;
 }
 
 static int upload_level_offsets(r3n_ctx *c, const r3n_texture_desc32 *descs, uint32_t n, uint64_t n_texels) {
@@ -1217,13 +1220,8 @@ int r3n_textures_write(r3n_ctx *c, const r3n_texture_desc32 *descs, uint32_t n, 
     for (uint32_t i = 0; i < n; ++i) {
         const r3n_texture_desc32 &d = descs[i];
         if (d.format > R3N_TEXTURE_RGBA8_UNORM_SRGB) return fail(c, R3N_ERR_UNSUPPORTED, "textures write: RGBA8 texels only here; other formats go through r3n_textures_write_encoded");
-        if (!d.width || !d.height || !d.mips || d.width > 65535u || d.height > 65535u) return fail(c, R3N_ERR_INVALID_ARG, "textures write: bad extent");
-        uint32_t max_mips = 0;
-        for (uint32_t m = std::max(d.width, d.height); m; m >>= 1) ++max_mips;
-        if (d.mips > max_mips) return fail(c, R3N_ERR_INVALID_ARG, "textures write: more mips than the extent has");
-        uint64_t need = d.offset;
-        for (uint32_t k = 0; k < d.mips; ++k) need += (uint64_t)std::max(1u, d.width >> k) * std::max(1u, d.height >> k);
-        if (need > n_texels) return fail(c, R3N_ERR_INVALID_ARG, "textures write: mip chain outside the texel pool");
+        TRY(check_chain(c, "textures write", d));
+        if (d.offset + texture_pool_words(d) > n_texels) return fail(c, R3N_ERR_INVALID_ARG, "textures write: mip chain outside the texel pool");
     }
     HIP_TRY(c, hipSetDevice(c->device));
     TRY(sync_all(c));  // no frame may still sample the old array
@@ -1247,8 +1245,6 @@ extern "C" int r3n_internal_skinning_mfma(uint32_t *mesh, const void *inputs, co
 extern "C" int r3n_internal_generate_mip(uint32_t srgb, uint32_t sw, uint32_t sh, uint32_t dw, uint32_t dh, const uint32_t *src,
                                          uint32_t *dst, const float *decode, const float *thr, hipStream_t stream);
 extern "C" uint64_t r3n_internal_level_bytes(uint32_t format, uint32_t w, uint32_t h);
-extern "C" int r3n_internal_decode_level(uint32_t format, uint32_t w, uint32_t h, const void *src, uint32_t *dst, hipStream_t stream);
-extern "C" int r3n_internal_decode_level_f32(uint32_t format, uint32_t w, uint32_t h, const void *src, float *dst, hipStream_t stream);
 extern "C" int r3n_internal_format_is_float(uint32_t format);
 extern "C" uint32_t r3n_internal_format_align(uint32_t format);
 extern "C" int r3n_internal_format_generates_mips_f32(uint32_t format);
@@ -1263,22 +1259,18 @@ static int check_encoded_desc(r3n_ctx *c, const std::string &what, const r3n_tex
                               uint64_t &words) {
     if (d.format >= R3N_TEXTURE_FORMAT_COUNT) return fail(c, R3N_ERR_UNSUPPORTED, what + ": unknown format id");
     const bool is_float = r3n_internal_format_is_float(d.format) != 0;
-    if (!d.width || !d.height || !d.mips || d.width > 65535u || d.height > 65535u) return fail(c, R3N_ERR_INVALID_ARG, what + ": bad extent");
-    uint32_t max_mips = 0;
-    for (uint32_t m = std::max(d.width, d.height); m; m >>= 1) ++max_mips;
-    if (d.mips > max_mips) return fail(c, R3N_ERR_INVALID_ARG, what + ": more mips than the extent has");
+    TRY(check_chain(c, what, d));
     if (d.stored_mips > d.mips) return fail(c, R3N_ERR_INVALID_ARG, what + ": more stored levels than mips");
     const uint32_t stored = d.stored_mips ? d.stored_mips : d.mips;
     if (stored < d.mips && d.format >= R3N_TEXTURE_BC1_RGBA_UNORM && !r3n_internal_format_generates_mips_f32(d.format))
         return fail(c, R3N_ERR_UNSUPPORTED, what + (is_float ? ": among the float-decoded formats mips are generated for R16Float / Rg16Float / Rgba16Float / Rgb10a2Unorm only (filterable render targets); the others must carry their levels"
                                                              : ": mips are generated for uncompressed formats only (block formats are not render targets)"));
     uint64_t end = d.offset;
-    words = 0;
-    for (uint32_t k = 0; k < d.mips; ++k) {
-        const uint32_t w = std::max(1u, d.width >> k), h = std::max(1u, d.height >> k);
-        if (k < stored) end += r3n_internal_level_bytes(d.format, w, h);
-        words += (uint64_t)w * h * (is_float ? 4u : 1u);  // pool words
+    for (uint32_t k = 0; k < stored; ++k) {
+        const texture_jobs::Level l = texture_jobs::level_of(d.width, d.height, k, 1u);
+        end += r3n_internal_level_bytes(d.format, l.w, l.h);
     }
+    words = texture_jobs::chain_words(d.width, d.height, d.mips, is_float ? 4u : 1u);
     if (end > payload_bytes) return fail(c, R3N_ERR_INVALID_ARG, what + ": levels outside the payload");
     if ((d.offset & 3u) != 0u) return fail(c, R3N_ERR_INVALID_ARG, what + ": level 0 must start on a 4-byte boundary");
     const bool srgb = d.format == R3N_TEXTURE_RGBA8_UNORM_SRGB || d.format == R3N_TEXTURE_BGRA8_UNORM_SRGB ||
@@ -1288,6 +1280,81 @@ static int check_encoded_desc(r3n_ctx *c, const std::string &what, const r3n_tex
     internal.stored_mips = 0;
     internal.format = is_float ? R3N_POOL_FLOAT : (srgb ? R3N_TEXTURE_RGBA8_UNORM_SRGB : R3N_TEXTURE_RGBA8_UNORM);
     return R3N_OK;
+}
+
+// ---- the ingestion core of r3n_textures_write_encoded and r3n_textures_update: what one call decodes and generates, planned on
+// the host before anything changes, then enqueued on the caller's stream with the caller's scratch blocks.
+
+// MipmapSource::Generated: a blit of the level above, written in the texture's format.  src / dst in pool words.
+struct GeneratedLevel {
+    uint32_t format, pool_format;  // the source's R3N_TEXTURE_*, the class of its pool texels
+    uint32_t sw, sh, w, h;
+    uint64_t src, dst;
+};
+// one job record per stored level, per kernel family (texture_jobs.h), the four tables as ONE block with every table on an 8-word
+// boundary; the generated levels in launch order
+struct TextureWork {
+    texture_jobs::Table tables[texture_jobs::FAMILIES];
+    size_t job_at[texture_jobs::FAMILIES];
+    std::vector<uint32_t> job_block;
+    std::vector<GeneratedLevel> generated;
+};
+// descs: the caller's (source format, byte offset in the payload); internal: what the device holds, placed.  false: a family has
+// more wave slots than its kernel counts.
+static bool plan_texture_work(const r3n_texture_desc32 *descs, const r3n_texture_desc32 *internal, uint32_t n, TextureWork &work) {
+    for (uint32_t i = 0; i < n; ++i) {
+        const r3n_texture_desc32 &d = descs[i];
+        const uint32_t stored = d.stored_mips ? d.stored_mips : d.mips;
+        uint64_t src = d.offset, dst = internal[i].offset;
+        texture_jobs::Level above{};
+        for (uint32_t k = 0; k < d.mips; ++k) {
+            const texture_jobs::Level l = texture_jobs::level_of(d.width, d.height, k, words_per_texel(internal[i]));
+            if (k < stored) {
+                texture_jobs::add_level(work.tables, d.format, l.w, l.h, src, (uint32_t)dst);
+                src += r3n_internal_level_bytes(d.format, l.w, l.h);
+            } else {
+                work.generated.push_back(GeneratedLevel{d.format, internal[i].format, above.w, above.h, l.w, l.h, dst - above.words, dst});
+            }
+            dst += l.words;
+            above = l;
+        }
+    }
+    if (!texture_jobs::finish(work.tables)) return false;
+    size_t words = 0;
+    for (int f = 0; f < texture_jobs::FAMILIES; ++f) {
+        work.job_at[f] = words;
+        words += (work.tables[f].block.size() + 7u) & ~(size_t)7u;
+    }
+    work.job_block.assign(std::max<size_t>(words, 1), 0u);
+    for (int f = 0; f < texture_jobs::FAMILIES; ++f) std::copy(work.tables[f].block.begin(), work.tables[f].block.end(), work.job_block.begin() + work.job_at[f]);
+    return true;
+}
+// Copy, decode: the payload once into `stage`, the tables into `job_dev` (the caller's blocks: payload_bytes, job_block.size() words
+// on a 32-byte boundary), at most four launches for every stored level of the call, the generated levels level by level behind
+// them.  Only enqueues, counting its kernels into `launches`; `payload` and `work` must outlive the caller's wait for `stream`.
+static hipError_t enqueue_texture_work(r3n_ctx *c, const TextureWork &work, const void *payload, uint64_t payload_bytes, hipStream_t stream, void *stage,
+                                       uint32_t *job_dev, uint64_t &launches) {
+    uint32_t *pool = c->tex_texels.as<uint32_t>();
+    hipError_t e = hipMemcpyAsync(stage, payload, payload_bytes, hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(job_dev, work.job_block.data(), work.job_block.size() * 4u, hipMemcpyHostToDevice, stream);
+    for (int f = 0; f < texture_jobs::FAMILIES && e == hipSuccess; ++f) {
+        const texture_jobs::Table &t = work.tables[f];
+        if (!t.total_waves) continue;
+        e = (hipError_t)r3n_internal_decode_jobs((uint32_t)f, job_dev + work.job_at[f], t.layout.o_first, t.layout.o_inst, (uint32_t)t.total_waves, stage, pool, stream);
+        ++launches;
+    }
+    for (size_t i = 0; i < work.generated.size() && e == hipSuccess; ++i) {
+        const GeneratedLevel &g = work.generated[i];
+        if (g.pool_format == R3N_POOL_FLOAT) {
+            e = (hipError_t)r3n_internal_generate_mip_f32(g.format, g.sw, g.sh, g.w, g.h, reinterpret_cast<const float *>(pool + g.src),
+                                                          reinterpret_cast<float *>(pool + g.dst), stream);
+        } else {
+            e = (hipError_t)r3n_internal_generate_mip(g.pool_format == R3N_TEXTURE_RGBA8_UNORM_SRGB, g.sw, g.sh, g.w, g.h, pool + g.src, pool + g.dst,
+                                                      c->srgb8_decode.as<float>(), c->srgb_thr.as<float>(), stream);
+        }
+        ++launches;
+    }
+    return e;
 }
 
 int r3n_textures_write_encoded(r3n_ctx *c, const r3n_texture_desc32 *descs, uint32_t n, const void *payload, uint64_t payload_bytes) {
@@ -1302,48 +1369,24 @@ int r3n_textures_write_encoded(r3n_ctx *c, const r3n_texture_desc32 *descs, uint
         internal[i].offset = (uint32_t)n_texels;
         n_texels += texels;
     }
+    TextureWork work;
+    if (!plan_texture_work(descs, internal.data(), n, work)) return fail(c, R3N_ERR_CAPACITY, "textures write (encoded): more than 2^31 wave slots of decode work in one call");
     HIP_TRY(c, hipSetDevice(c->device));
     TRY(sync_all(c));  // no frame may still sample the old array
     TRY(ensure(c, c->tex_descs, std::max<size_t>(n, 1) * sizeof(r3n_texture_desc32), false, -1));
     TRY(ensure(c, c->tex_texels, std::max<uint64_t>(n_texels, 1) * 4 + 16, false, -1));  // (+16: the sampler reads a footprint row as one 8-byte load -- the pool's last texel has a word behind it)
     if (n) {
-        void *staged = nullptr;
-        HIP_TRY(c, hipMalloc(&staged, std::max<uint64_t>(payload_bytes, 4)));
-        hipError_t e = hipMemcpyAsync(staged, payload, payload_bytes, hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(c->tex_descs.p, internal.data(), (size_t)n * sizeof(r3n_texture_desc32), hipMemcpyHostToDevice, c->stream);
-        for (uint32_t i = 0; i < n && e == hipSuccess; ++i) {
-            uint64_t src = descs[i].offset, dst = internal[i].offset;
-            const uint32_t stored = descs[i].stored_mips ? descs[i].stored_mips : descs[i].mips;
-            for (uint32_t k = 0; k < descs[i].mips && e == hipSuccess; ++k) {
-                const uint32_t w = std::max(1u, descs[i].width >> k), h = std::max(1u, descs[i].height >> k);
-                if (internal[i].format == R3N_POOL_FLOAT) {
-                    float *level = reinterpret_cast<float *>(c->tex_texels.as<uint32_t>() + dst);
-                    if (k < stored) {
-                        // sources are read through their own width (format_align): every level of those formats is a multiple of it
-                        e = (hipError_t)r3n_internal_decode_level_f32(descs[i].format, w, h, static_cast<const char *>(staged) + src, level, c->stream);
-                        src += r3n_internal_level_bytes(descs[i].format, w, h);
-                    } else {  // MipmapSource::Generated: blit of the level above, written in the texture's format
-                        const uint32_t sw = std::max(1u, descs[i].width >> (k - 1u)), sh = std::max(1u, descs[i].height >> (k - 1u));
-                        e = (hipError_t)r3n_internal_generate_mip_f32(descs[i].format, sw, sh, w, h, level - (uint64_t)sw * sh * 4u, level, c->stream);
-                    }
-                    dst += (uint64_t)w * h * 3u;  // + w * h below: four words per texel
-                } else if (k < stored) {
-                    // block-compressed and 32-bit sources are read as dwords: every level of those formats is a multiple of 4 B
-                    e = (hipError_t)r3n_internal_decode_level(descs[i].format, w, h, static_cast<const char *>(staged) + src,
-                                                              c->tex_texels.as<uint32_t>() + dst, c->stream);
-                    src += r3n_internal_level_bytes(descs[i].format, w, h);
-                } else {  // MipmapSource::Generated: blit of the level above, in the texture's format
-                    const uint32_t sw = std::max(1u, descs[i].width >> (k - 1u)), sh = std::max(1u, descs[i].height >> (k - 1u));
-                    e = (hipError_t)r3n_internal_generate_mip(internal[i].format == R3N_TEXTURE_RGBA8_UNORM_SRGB, sw, sh, w, h,
-                                                              c->tex_texels.as<uint32_t>() + dst - (uint64_t)sw * sh,
-                                                              c->tex_texels.as<uint32_t>() + dst, c->srgb8_decode.as<float>(),
-                                                              c->srgb_thr.as<float>(), c->stream);
-                }
-                dst += (uint64_t)w * h;
-            }
-        }
+        // a block of the call's own, payload | job tables, freed before it returns: nothing payload-sized stays resident behind a
+        // whole-array write (the grow-only tex_stage / tex_jobs are the update path's)
+        const uint64_t jobs_at = (std::max<uint64_t>(payload_bytes, 4) + 255u) & ~255ull;
+        void *scratch = nullptr;
+        HIP_TRY(c, hipMalloc(&scratch, jobs_at + work.job_block.size() * 4u));
+        uint64_t launches = 0;  // (r3n_texture_stats counts the update path alone)
+        hipError_t e = hipMemcpyAsync(c->tex_descs.p, internal.data(), (size_t)n * sizeof(r3n_texture_desc32), hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess)
+            e = enqueue_texture_work(c, work, payload, payload_bytes, c->stream, scratch, reinterpret_cast<uint32_t *>(static_cast<char *>(scratch) + jobs_at), launches);
         const hipError_t e2 = hipStreamSynchronize(c->stream);  // the caller owns the sources only for the duration of the call
-        (void)hipFree(staged);
+        (void)hipFree(scratch);
         if (e != hipSuccess) return fail(c, R3N_ERR_HIP, std::string("textures write (encoded): ") + hipGetErrorString(e));
         if (e2 != hipSuccess) return fail(c, R3N_ERR_HIP, std::string("textures write (encoded): ") + hipGetErrorString(e2));
     }
@@ -1486,30 +1529,8 @@ int r3n_textures_update(r3n_ctx *c, const uint32_t *slots, const r3n_texture_des
     const bool grow_pool = pool_bytes > c->tex_texels.bytes;
     wait = wait || grow_pool;
 
-    // the job tables: one record per stored level, per kernel family (texture_jobs.h); generated levels follow per level
-    texture_jobs::Table tables[texture_jobs::FAMILIES];
-    uint64_t generated = 0;
-    for (uint32_t i = 0; i < n; ++i) {
-        const r3n_texture_desc32 &d = descs[i];
-        const uint32_t stored = d.stored_mips ? d.stored_mips : d.mips, per = internal[i].format == R3N_POOL_FLOAT ? 4u : 1u;
-        uint64_t src = d.offset, dst = internal[i].offset;
-        for (uint32_t k = 0; k < d.mips; ++k) {
-            const uint32_t w = std::max(1u, d.width >> k), h = std::max(1u, d.height >> k);
-            if (k < stored) {
-                texture_jobs::add_level(tables, d.format, w, h, src, (uint32_t)dst);
-                src += r3n_internal_level_bytes(d.format, w, h);
-            } else {
-                ++generated;
-            }
-            dst += (uint64_t)w * h * per;
-        }
-    }
-    if (!texture_jobs::finish(tables)) return fail(c, R3N_ERR_CAPACITY, "textures update: more than 2^31 wave slots of decode work in one call");
-    size_t job_words = 0, job_at[texture_jobs::FAMILIES];
-    for (int f = 0; f < texture_jobs::FAMILIES; ++f) {
-        job_at[f] = job_words;
-        job_words += (tables[f].block.size() + 7u) & ~(size_t)7u;
-    }
+    TextureWork work;  // the job tables of the stored levels, the generated levels behind them
+    if (!plan_texture_work(descs, internal.data(), n, work)) return fail(c, R3N_ERR_CAPACITY, "textures update: more than 2^31 wave slots of decode work in one call");
 
     // ---- device side: wait if a frame may read what changes, grow, stage
     if (wait) {
@@ -1524,7 +1545,7 @@ int r3n_textures_update(r3n_ctx *c, const uint32_t *slots, const r3n_texture_des
         ++c->tex_stats.pool_grows;
     }
     TRY(grow_texture_scratch(c, c->tex_stage, (size_t)std::max<uint64_t>(payload_bytes, 4)));
-    TRY(grow_texture_scratch(c, c->tex_jobs, std::max<size_t>(job_words, 1) * 4u));
+    TRY(grow_texture_scratch(c, c->tex_jobs, work.job_block.size() * 4u));
 
     // ---- the host mirror follows
     c->h_tex_descs.resize(new_table, r3n_texture_desc32{});
@@ -1550,44 +1571,12 @@ int r3n_textures_update(r3n_ctx *c, const uint32_t *slots, const r3n_texture_des
     c->classes_dirty = true; c->cutout_short_dirty = true;
     ++c->main_epoch;  // the shadow lanes' cutout rasterisers sample the array
 
-    // ---- copy, decode: the payload once, the tables, at most four launches for every stored level of the call
-    uint64_t launches = 0;
-    std::vector<uint32_t> job_block(std::max<size_t>(job_words, 1), 0u);
-    for (int f = 0; f < texture_jobs::FAMILIES; ++f) std::copy(tables[f].block.begin(), tables[f].block.end(), job_block.begin() + job_at[f]);
+    // ---- the touched table rows, then copy and decode
     // (the main stream is idle or busy with frames that cannot name what is written here: nothing on it has to come first -- a
     // growth, a whole-array write and an earlier update all ended in a wait, a removal's table rows belong to hot slots)
-    HIP_TRY(c, hipMemcpyAsync(c->tex_stage.p, payload, payload_bytes, hipMemcpyHostToDevice, c->tex_stream));
-    HIP_TRY(c, hipMemcpyAsync(c->tex_jobs.p, job_block.data(), job_block.size() * 4u, hipMemcpyHostToDevice, c->tex_stream));
     TRY(upload_texture_slots(c, touched, true));
-    uint32_t *pool = c->tex_texels.as<uint32_t>();
-    hipError_t e = hipSuccess;
-    for (int f = 0; f < texture_jobs::FAMILIES && e == hipSuccess; ++f) {
-        if (!tables[f].total_waves) continue;
-        e = (hipError_t)r3n_internal_decode_jobs((uint32_t)f, c->tex_jobs.as<uint32_t>() + job_at[f], tables[f].layout.o_first, tables[f].layout.o_inst,
-                                                 (uint32_t)tables[f].total_waves, c->tex_stage.p, pool, c->tex_stream);
-        ++launches;
-    }
-    for (uint32_t i = 0; i < n && generated && e == hipSuccess; ++i) {  // MipmapSource::Generated: level by level, behind the decode
-        const r3n_texture_desc32 &d = descs[i];
-        const uint32_t stored = d.stored_mips ? d.stored_mips : d.mips;
-        const bool is_float = internal[i].format == R3N_POOL_FLOAT;
-        uint64_t dst = internal[i].offset;
-        for (uint32_t k = 0; k < d.mips && e == hipSuccess; ++k) {
-            const uint32_t w = std::max(1u, d.width >> k), h = std::max(1u, d.height >> k);
-            if (k >= stored) {
-                const uint32_t sw = std::max(1u, d.width >> (k - 1u)), sh = std::max(1u, d.height >> (k - 1u));
-                if (is_float) {
-                    float *level = reinterpret_cast<float *>(pool + dst);
-                    e = (hipError_t)r3n_internal_generate_mip_f32(d.format, sw, sh, w, h, level - (uint64_t)sw * sh * 4u, level, c->tex_stream);
-                } else {
-                    e = (hipError_t)r3n_internal_generate_mip(internal[i].format == R3N_TEXTURE_RGBA8_UNORM_SRGB, sw, sh, w, h, pool + dst - (uint64_t)sw * sh,
-                                                              pool + dst, c->srgb8_decode.as<float>(), c->srgb_thr.as<float>(), c->tex_stream);
-                }
-                ++launches;
-            }
-            dst += (uint64_t)w * h * (is_float ? 4u : 1u);
-        }
-    }
+    uint64_t launches = 0;
+    const hipError_t e = enqueue_texture_work(c, work, payload, payload_bytes, c->tex_stream, c->tex_stage.p, c->tex_jobs.as<uint32_t>(), launches);
     const hipError_t e2 = hipStreamSynchronize(c->tex_stream);  // its own work alone; the caller owns the payload only for the duration of the call
     if (e != hipSuccess) return fail(c, R3N_ERR_HIP, std::string("textures update: ") + hipGetErrorString(e));
     if (e2 != hipSuccess) return fail(c, R3N_ERR_HIP, std::string("textures update: ") + hipGetErrorString(e2));

@@ -185,7 +185,7 @@ __device__ void decode_bc7_block(uint64_t lo, uint64_t hi, uint32_t out[16]) {
     }
 }
 
-// block g of a w x h level (shared by the per-level kernel and the job-table kernel below)
+// block g of a w x h level (the unit of work of the job-table kernel below)
 __device__ __forceinline__ void decode_block_at(uint32_t format, uint32_t w, uint32_t h, const uint32_t *__restrict__ src,
                                                 uint32_t *__restrict__ dst, uint32_t g) {
     const uint32_t bw = (w + 3u) / 4u, bh = (h + 3u) / 4u;
@@ -234,7 +234,8 @@ __device__ __forceinline__ void decode_block_at(uint32_t format, uint32_t w, uin
         break;
     }
     // rows of a block are 16 B; whole, 16-byte-aligned rows (level width a multiple of 4 and an aligned level start,
-    // which r3n_textures_write_encoded arranges for every texture) go out as one dwordx4 store per row
+    // which the 4-word-aligned texture starts of r3n_textures_write_encoded and r3n_textures_update arrange) go out as one
+    // dwordx4 store per row
     const bool vec = (w & 3u) == 0u && (reinterpret_cast<uintptr_t>(dst) & 15u) == 0u;
 #pragma unroll
     for (uint32_t y = 0; y < 4u; ++y) {
@@ -251,11 +252,6 @@ __device__ __forceinline__ void decode_block_at(uint32_t format, uint32_t w, uin
     }
 }
 
-__global__ __launch_bounds__(256) void k_decode_blocks(uint32_t format, uint32_t w, uint32_t h, const uint32_t *__restrict__ src,
-                                                       uint32_t *__restrict__ dst) {
-    decode_block_at(format, w, h, src, dst, blockIdx.x * 256u + threadIdx.x);
-}
-
 // uncompressed sources: one thread per texel
 __device__ __forceinline__ void expand_texel_at(uint32_t format, uint64_t n, const uint8_t *__restrict__ src, uint32_t *__restrict__ dst,
                                                 uint64_t i) {
@@ -269,9 +265,6 @@ __device__ __forceinline__ void expand_texel_at(uint32_t format, uint64_t n, con
                 ? ((t & 0xFF00FF00u) | ((t >> 16) & 0xFFu) | ((t & 0xFFu) << 16)) : t;
     }
     dst[i] = v;
-}
-__global__ __launch_bounds__(256) void k_expand_texels(uint32_t format, uint64_t n, const uint8_t *__restrict__ src, uint32_t *__restrict__ dst) {
-    expand_texel_at(format, n, src, dst, (uint64_t)blockIdx.x * 256u + threadIdx.x);
 }
 
 // MipmapSource::Generated (rend3/src/util/mipmap.rs:139-236 + rend3/shaders/mipmap.wgsl, K11): level l is a blit of
@@ -370,9 +363,6 @@ __device__ __forceinline__ void expand_texel_f32_at(uint32_t format, uint64_t n,
     }
     }
     dst[i] = o;
-}
-__global__ __launch_bounds__(256) void k_expand_texels_f32(uint32_t format, uint64_t n, const uint8_t *__restrict__ src, float4 *__restrict__ dst) {
-    expand_texel_f32_at(format, n, src, dst, (uint64_t)blockIdx.x * 256u + threadIdx.x);
 }
 
 // RGTC signed block -> 16 floats (snorm8 endpoints, integer ordering, palette interpolated in f32)
@@ -520,15 +510,11 @@ __device__ __forceinline__ void decode_block_f32_at(uint32_t format, uint32_t w,
             if (bx * 4u + x < w) dst[(size_t)ty * w + bx * 4u + x] = px[y * 4u + x];
     }
 }
-__global__ __launch_bounds__(256) void k_decode_blocks_f32(uint32_t format, uint32_t w, uint32_t h, const uint32_t *__restrict__ src,
-                                                           float4 *__restrict__ dst) {
-    decode_block_f32_at(format, w, h, src, dst, blockIdx.x * 256u + threadIdx.x);
-}
 
-// ---- job-table kernels (r3n_textures_update): ONE launch per family decodes every stored level of every texture of the call.
-// Wave slot -> job through the wave map of the vertex stages (texture_jobs.h, vertex_gather.h): the record is wave-uniform and
-// comes through scalar registers; lane l of a job's k-th wave slot takes unit 64 k + l (a 4x4 block, or a texel).  The per-unit
-// work is the functions above, so every word is the per-level kernels'.  Launched as (total_waves + 3) / 4 blocks of 256.
+// ---- the decode kernels (r3n_textures_write_encoded, r3n_textures_update): ONE launch per family decodes every stored level of
+// every texture of the call.  Wave slot -> job through the wave map of the vertex stages (texture_jobs.h, vertex_gather.h): the
+// record is wave-uniform and comes through scalar registers; lane l of a job's k-th wave slot takes unit 64 k + l (a 4x4 block, or
+// a texel) and runs the per-unit function above on it.  Launched as (total_waves + 3) / 4 blocks of 256.
 using texture_jobs::Job;
 struct JobArgs {
     const Job *jobs;
@@ -654,7 +640,7 @@ extern "C" uint64_t r3n_internal_level_bytes(uint32_t format, uint32_t w, uint32
     }
 }
 
-// 1: the format decodes to four f32 per texel (r3n_internal_decode_level_f32), 0: to RGBA8
+// 1: the format decodes to four f32 per texel (the f32 job families), 0: to RGBA8
 extern "C" int r3n_internal_format_is_float(uint32_t format) { return format >= R3N_TEXTURE_R8_SNORM && format < R3N_TEXTURE_FORMAT_COUNT; }
 // required alignment of a level's first byte in the payload (the decoders read it through that type)
 extern "C" uint32_t r3n_internal_format_align(uint32_t format) {
@@ -663,34 +649,6 @@ extern "C" uint32_t r3n_internal_format_align(uint32_t format) {
     case R3N_TEXTURE_RG8_SNORM: case R3N_TEXTURE_R16_FLOAT: return 2u;
     default: return 4u;
     }
-}
-
-// one level: device source (its own format) -> w * h RGBA8 texels at `dst` (device)
-extern "C" int r3n_internal_decode_level(uint32_t format, uint32_t w, uint32_t h, const void *src, uint32_t *dst, hipStream_t stream) {
-    if (format >= R3N_TEXTURE_BC1_RGBA_UNORM) {
-        const uint32_t blocks = ((w + 3u) / 4u) * ((h + 3u) / 4u);
-        hipLaunchKernelGGL(k_decode_blocks, dim3((blocks + 255u) / 256u), dim3(256), 0, stream, format, w, h,
-                           static_cast<const uint32_t *>(src), dst);
-    } else {
-        const uint64_t n = (uint64_t)w * h;
-        hipLaunchKernelGGL(k_expand_texels, dim3((unsigned)((n + 255u) / 256u)), dim3(256), 0, stream, format, n,
-                           static_cast<const uint8_t *>(src), dst);
-    }
-    return (int)hipGetLastError();
-}
-
-// one level: device source (its own format) -> w * h float texels at `dst` (device, 16-byte aligned)
-extern "C" int r3n_internal_decode_level_f32(uint32_t format, uint32_t w, uint32_t h, const void *src, float *dst, hipStream_t stream) {
-    if (format >= R3N_TEXTURE_BC4_R_SNORM) {
-        const uint32_t blocks = ((w + 3u) / 4u) * ((h + 3u) / 4u);
-        hipLaunchKernelGGL(k_decode_blocks_f32, dim3((blocks + 255u) / 256u), dim3(256), 0, stream, format, w, h,
-                           static_cast<const uint32_t *>(src), reinterpret_cast<float4 *>(dst));
-    } else {
-        const uint64_t n = (uint64_t)w * h;
-        hipLaunchKernelGGL(k_expand_texels_f32, dim3((unsigned)((n + 255u) / 256u)), dim3(256), 0, stream, format, n,
-                           static_cast<const uint8_t *>(src), reinterpret_cast<float4 *>(dst));
-    }
-    return (int)hipGetLastError();
 }
 
 // One family's job table (texture_jobs.h; `block` = its device copy, `o_first` / `o_inst` = the layout's word offsets): every

@@ -1,6 +1,6 @@
-// texture_jobs.h -- host side of the batched texture decode (texture_decode.hip, r3n_internal_decode_jobs): the job table that
-// lets ONE launch per kernel family decode every stored level of every texture of an r3n_textures_update call.  Plain C++17, no
-// HIP, no context: tests/texel_alloc_check.cpp compiles it alone.
+// texture_jobs.h -- host side of the batched texture decode (texture_decode.hip, r3n_internal_decode_jobs): the walk over a
+// texture's levels, and the job table that lets ONE launch per kernel family decode every stored level of every texture of a call
+// (r3n_textures_write_encoded, r3n_textures_update).  Plain C++17, no HIP, no context: tests/texel_alloc_check.cpp compiles it alone.
 //
 // A job is one stored level.  Its work units are its 4x4 blocks (block formats: one lane decodes one block) or its texels
 // (uncompressed formats: one lane expands one texel); a wave slot takes 64 consecutive units of ONE job, so the job record is
@@ -9,6 +9,7 @@
 #pragma once
 #include <stdint.h>
 
+#include <algorithm>
 #include <cstring>
 #include <vector>
 
@@ -16,6 +17,29 @@
 #include "vertex_block.h"
 
 namespace texture_jobs {
+
+// ---- the chain walk.  A texture is (width, height, mips, pool words per texel: 1 for RGBA8, 4 for f32 texels); its levels lie back
+// to back in the pool, level 0 first.  Level k halves each side k times, rounded down, and never goes below 1.
+struct Level {
+    uint32_t w, h;
+    uint64_t words;  // pool words of the level
+};
+inline Level level_of(uint32_t width, uint32_t height, uint32_t k, uint32_t per_texel) {
+    const uint32_t w = std::max(1u, width >> k), h = std::max(1u, height >> k);
+    return Level{w, h, (uint64_t)w * h * per_texel};
+}
+inline uint64_t chain_words(uint32_t width, uint32_t height, uint32_t mips, uint32_t per_texel) {
+    uint64_t words = 0;
+    for (uint32_t k = 0; k < mips; ++k) words += level_of(width, height, k, per_texel).words;
+    return words;
+}
+// what a texture array refuses about a chain's shape, nullptr when nothing: sides 1 .. 65535, 1 .. floor(log2(longer side)) + 1 levels
+inline const char *chain_fault(uint32_t width, uint32_t height, uint32_t mips) {
+    if (!width || !height || !mips || width > 65535u || height > 65535u) return "bad extent";
+    uint32_t max_mips = 0;
+    for (uint32_t m = std::max(width, height); m; m >>= 1) ++max_mips;
+    return mips > max_mips ? "more mips than the extent has" : nullptr;
+}
 
 enum Family { RGBA8_BLOCK = 0, RGBA8_EXPAND = 1, F32_BLOCK = 2, F32_EXPAND = 3, FAMILIES = 4 };
 

@@ -1,6 +1,7 @@
 """The streamed texture path on the GPU: r3n_textures_update / r3n_textures_remove (single entries added, replaced and removed in a
 resident texel pool; every stored level of a call decoded by one launch per kernel family, texture_decode.hip) against the whole-array
-write r3n_textures_write_encoded, word for word, through the C ABI; the launch, copy and wait structure from r3n_texture_stats; and
+write r3n_textures_write_encoded, word for word, through the C ABI -- the two calls share their decode kernels, so the whole-array
+write is itself pinned on the oracle's CPU decoders first; the launch, copy and wait structure from r3n_texture_stats; and
 Renderer(texture_upload="stream") against "whole" and the oracle, frame by frame.
 
 Pool words that belong to no texture -- the up to three words in front of a texture's 4-word boundary -- are written by neither
@@ -169,6 +170,33 @@ def whole(r3):
     return dict(texs=texs, descs=d, extent=extent, pool=pool, mask=mask)
 
 
+def test_whole_write_equals_the_oracle(whole):
+    """The pin of the `whole` fixture, and through it of every comparison below: each texture of the list decoded on the CPU by
+    the oracle (oracle/bcn.c, the blit chains of r3o.c) against the GPU pool range of that texture, word for word.  Per texture,
+    not by pool offset: the oracle aligns only its float textures.  The list holds no NaN, so the words compare as integers."""
+    o = OracleRenderer()
+    c = o.lib.c
+    for t in whole["texs"]:
+        levels, at = [], 0
+        for k in range(t.stored or t.mips):
+            size = int(c.r3o_texture_level_bytes(t.fmt, max(1, t.w >> k), max(1, t.h >> k)))
+            levels.append(t.data[at: at + size])
+            at += size
+        assert at == len(t.data), "the stored levels are the whole payload of the texture"
+        o.add_texture_2d_encoded(t.fmt, t.w, t.h, levels, generate_mips=t.generated != 0)
+    assert len(o.tex_descs) == len(whole["descs"]) == len(whole["texs"])
+    compared = 0
+    for i, (t, od, gd) in enumerate(zip(whole["texs"], o.tex_descs, whole["descs"])):
+        assert od[1:5].tolist() == gd[1:5].tolist() and od[1:4].tolist() == [t.w, t.h, t.mips], f"texture {i}: extent, mips, pool class"
+        assert desc_words(od) == t.words
+        want = o.tex_pool[int(od[0]): int(od[0]) + t.words]
+        got = whole["pool"][int(gd[0]): int(gd[0]) + t.words]
+        bad = np.nonzero(want != got)[0]
+        assert not len(bad), f"texture {i} (format {t.fmt}, {t.w} x {t.h}): {len(bad)} of {t.words} words differ, first at {bad[:4]}"
+        compared += t.words
+    assert compared == int(whole["mask"].sum()) == sum(t.words for t in whole["texs"])  # no texture and no word left out
+
+
 def assert_same_as_whole(b, whole, tag):
     d, extent, pool, mask = owned_words(b)
     assert np.array_equal(d, whole["descs"]), tag + " descriptors"
@@ -233,8 +261,14 @@ def test_updates_behind_a_whole_write_equal_the_whole_write(r3, whole):
     c.ok(c.update(range(7, 9), texs[7:9]))
     c.ok(c.update(range(9, len(texs)), texs[9:]))
     assert_same_as_whole(c, whole, "update, whole write, updates")
+    d = Ctx(r3)
+    d.ok(d.write(texs))
+    d.ok(d.write(texs[:7]))  # the shrinking order: table, pool extent and allocator fall back to the shorter write's prefix
+    d.ok(d.update(range(7, len(texs)), texs[7:]))
+    assert_same_as_whole(d, whole, "whole write, shorter whole write, update of the rest")
     b.close()
     c.close()
+    d.close()
 
 
 # ------------------------------------------------------------------ 6: remove, reuse, replace

@@ -6,6 +6,7 @@
 #include <stdio.h>
 
 #include <map>
+#include <string>
 #include <vector>
 
 #include "../rend3_amd/csrc/texel_alloc.h"
@@ -219,7 +220,34 @@ static void jobs() {
     CHECK(texture_jobs::finish(none) && none[0].block.empty() && none[3].total_waves == 0);
 }
 
+static bool refuses(const char *fault, const char *want) { return fault && std::string(fault) == want; }
+
+// the chain walk against a chain written out by hand: 37 x 21, six levels; four pool words per texel for the words
+static void chain_walk() {
+    const uint32_t want[6][2] = {{37, 21}, {18, 10}, {9, 5}, {4, 2}, {2, 1}, {1, 1}};
+    uint64_t texels = 0;
+    for (uint32_t k = 0; k < 6; ++k) {
+        const texture_jobs::Level l = texture_jobs::level_of(37, 21, k, 4);
+        CHECK(l.w == want[k][0] && l.h == want[k][1] && l.words == 4ull * want[k][0] * want[k][1]);
+        texels += (uint64_t)want[k][0] * want[k][1];
+    }
+    CHECK(texels == 777 + 180 + 45 + 8 + 2 + 1);
+    CHECK(texture_jobs::chain_words(37, 21, 6, 1) == texels && texture_jobs::chain_words(37, 21, 6, 4) == 4 * texels);
+    CHECK(texture_jobs::chain_words(37, 21, 1, 1) == 777 && texture_jobs::chain_words(37, 21, 0, 1) == 0);
+    CHECK(texture_jobs::level_of(65535, 1, 15, 1).w == 1 && texture_jobs::level_of(65535, 1, 15, 1).h == 1);
+    CHECK(texture_jobs::chain_words(65535, 65535, 1, 4) == 4ull * 65535 * 65535);  // past 2^32: counted in 64 bits
+    // the shape check: 37 has six bits, so six levels and no more
+    CHECK(texture_jobs::chain_fault(37, 21, 6) == nullptr && texture_jobs::chain_fault(1, 1, 1) == nullptr);
+    CHECK(texture_jobs::chain_fault(65535, 65535, 16) == nullptr);
+    CHECK(refuses(texture_jobs::chain_fault(37, 21, 7), "more mips than the extent has"));
+    CHECK(refuses(texture_jobs::chain_fault(21, 37, 7), "more mips than the extent has"));
+    CHECK(refuses(texture_jobs::chain_fault(1, 1, 2), "more mips than the extent has"));
+    const uint32_t bad[5][3] = {{0, 4, 1}, {4, 0, 1}, {4, 4, 0}, {65536, 4, 1}, {4, 65536, 1}};
+    for (const auto &b : bad) CHECK(refuses(texture_jobs::chain_fault(b[0], b[1], b[2]), "bad extent"));
+}
+
 int main() {
+    chain_walk();
     appends();
     first_fit_and_coalescing();
     tail();

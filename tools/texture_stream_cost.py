@@ -10,10 +10,12 @@ on its bits, the copy cost not at all), two ways of loading them:
       hand-over (it ends in the call's own device synchronise) and of the whole load, frames included; medians and ranges over
       the loads.
   (b) the whole set in ONE call: r3n_textures_write_encoded against r3n_textures_update on fresh contexts, host wall time around
-      the call (each synchronises before it returns), `--repeats` times each, alternated; medians and ranges.
+      the call (each synchronises before it returns), `--repeats` times each, alternated; medians and ranges.  Both calls plan
+      the same job tables and run the same kernels, so what is left between them is the host side: the whole write's staging
+      block of its own (allocated and freed in the call) and its full wait, the update's resident buffers and allocator.
 Next to the times: what the program counts -- bytes copied and kernels launched.  The streamed path's come from r3n_texture_stats;
-the whole-array path's are ARITHMETIC from the shapes (it copies every texture present and launches once per level per texture on
-every re-send: k textures present -> k * bytes and k * levels launches), not measurements.  After (a) the two renderers' decoded
+the whole-array path's are ARITHMETIC from the shapes (it copies every texture present on every re-send and decodes one kernel
+family -- every texture here is BC7 -- with one launch: k textures present -> k * bytes, one launch), not measurements.  After (a) the two renderers' decoded
 texels are compared word for word.
 
 usage: python tools/texture_stream_cost.py [--textures 256] [--size 256] [--repeats 3] [--out profiles/texture_stream.md]"""
@@ -119,7 +121,7 @@ def main():
              f"{size} x {size} with full stored chains ({levels} levels, {tex_bytes} B each, {n * tex_bytes / 1e6:.1f} MB in all), random block data.  "
              "Times are host wall clock around calls that end in their own device synchronise.  Bytes and launches of the streamed path are "
              "`r3n_texture_stats` counters; those of the whole-array path are arithmetic from the shapes (k textures present: k x bytes, "
-             "k x levels launches per re-send), not measured.", ""]
+             "one launch per re-send -- one kernel family), not measured.", ""]
 
     # (a) one texture per frame
     stream_in(r3, "stream", textures[:4], size)  # warm-up of both paths' kernels and of the allocator's first growth
@@ -143,7 +145,7 @@ def main():
         return f"{np.median(v):.{digits}f} ({v.min():.{digits}f} - {v.max():.{digits}f}) ms"
     for mode in ("whole", "stream"):
         if mode == "whole":
-            copied, launches, waits = f"{n * (n + 1) // 2 * tex_bytes / 1e6:.1f} MB (arithmetic)", f"{n * (n + 1) // 2 * levels} (arithmetic)", f"{n} (one per re-send)"
+            copied, launches, waits = f"{n * (n + 1) // 2 * tex_bytes / 1e6:.1f} MB (arithmetic)", f"{n} (arithmetic)", f"{n} (one per re-send)"
         else:
             copied, launches, waits = f"{st['bytes_staged'] / 1e6:.1f} MB", str(st["kernel_launches"]), f"{st['full_syncs']} ({st['pool_grows']} growths)"
         sums, medians, totals = zip(*loads[mode])
@@ -165,7 +167,7 @@ def main():
     lines += ["## The whole set in one call", "", "| call | host wall time, median (range) | kernel launches |", "|---|---|---|"]
     for update, name in ((False, "r3n_textures_write_encoded"), (True, "r3n_textures_update")):
         a = np.array(t[update]) * 1e3
-        launches = str(stats["kernel_launches"]) if update else f"{n * levels} (arithmetic)"
+        launches = str(stats["kernel_launches"]) if update else "1 (arithmetic)"
         lines.append(f"| `{name}` | {np.median(a):.2f} ms ({a.min():.2f} - {a.max():.2f}) | {launches} |")
     ratio_b = np.median(t[False]) / np.median(t[True])
     lines += ["", f"Whole-array write over update, medians of {args.repeats} alternated calls on fresh contexts: {ratio_b:.2f} x (measured).  "
