@@ -310,6 +310,26 @@ pub struct r3n_config {
 
 #[repr(C)]
 #[derive(Clone, Copy)]
+pub struct r3n_texture_compact_opts {
+    pub max_words: u64,
+    pub stage_words: u64,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct r3n_texture_compact_result {
+    pub textures_moved: u64,
+    pub words_moved: u64,
+    pub passes: u64,
+    pub kernel_launches: u64,
+    pub full_syncs: u64,
+    pub pool_words_before: u64,
+    pub pool_words_after: u64,
+    pub free_ranges_after: u64,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
 pub struct r3n_texture_counters {
     pub update_calls: u64,
     pub kernel_launches: u64,
@@ -414,6 +434,7 @@ extern "C" {
     pub fn r3n_textures_write_encoded(ctx: *mut r3n_ctx, descs: *const r3n_texture_desc32, n_textures: u32, payload: *const c_void, payload_bytes: u64) -> c_int;
     pub fn r3n_textures_update(ctx: *mut r3n_ctx, slots: *const u32, descs: *const r3n_texture_desc32, n: u32, payload: *const c_void, payload_bytes: u64) -> c_int;
     pub fn r3n_textures_remove(ctx: *mut r3n_ctx, slots: *const u32, n: u32) -> c_int;
+    pub fn r3n_textures_compact(ctx: *mut r3n_ctx, opts: *const r3n_texture_compact_opts, out: *mut r3n_texture_compact_result) -> c_int;
     pub fn r3n_texture_stats(ctx: *mut r3n_ctx, out: *mut r3n_texture_counters, reset: c_int) -> c_int;
     pub fn r3n_texture_cubes_write(ctx: *mut r3n_ctx, descs: *const r3n_texture_desc32, n_cubes: u32, texels: *const u32, n_texels: u64) -> c_int;
     pub fn r3n_skybox_set(ctx: *mut r3n_ctx, cube_id: u32) -> c_int;

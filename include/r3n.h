@@ -337,6 +337,37 @@ int r3n_textures_update(r3n_ctx *ctx, const uint32_t *slots, const r3n_texture_d
  *      slot twice -> R3N_ERR_INVALID_ARG, nothing changed.  Never waits for the GPU.  (After a raw r3n_textures_write whose ranges
  *      are not ascending, disjoint and 4-word aligned the slots own no words: removing them frees none.) */
 int r3n_textures_remove(r3n_ctx *ctx, const uint32_t *slots, uint32_t n);
+/*      Compaction of the streamed pool (no counterpart in the reference, which keeps one wgpu texture per handle and has no pool to
+ *      fragment): slides the live textures towards pool word 0, in ascending address order, each to the 4-word boundary behind the
+ *      one before, so that the holes below the high-water mark disappear and the mark comes down.  The decoded words are moved on the
+ *      device; nothing is copied from the host or decoded again, no texture is reordered, and the words of every live texture are
+ *      unchanged -- `offset` is the only field of its descriptor that changes.  Removed slots stay removed entries at pool word 0.
+ *      The device block is neither shrunk nor freed: later textures reuse the words behind the lowered mark.
+ *      opts (NULL = all zero): max_words != 0 stops in front of the first texture whose padded words would take the call past that
+ *      many words moved -- the prefix is packed, one hole follows it, the rest is untouched and a later call goes on from there.
+ *      stage_words = the most words of scratch memory the call may use, a multiple of 4 and at least 256 (anything else ->
+ *      R3N_ERR_INVALID_ARG); 0 = 16 Mi words, 64 MiB: a launch never writes a word it reads elsewhere, so a stretch whose shift
+ *      is shorter than itself goes through scratch in pieces of this size, two launches each: launches <= 2 * (ceil(words_moved /
+ *      stage_words) + 1), which is 34 for a 1 GiB pool and 514 for a 16 GiB pool moved entirely through the default scratch.  The
+ *      default bounds the scratch block, which stays resident like the update path's staging.
+ *      When nothing would move the call returns R3N_OK without a wait or a launch (full_syncs == 0) and releases no removed range.
+ *      Otherwise it waits ONCE for every frame in flight -- ranges removed since the last such wait then count as holes -- enqueues
+ *      its passes, uploads the descriptor and level-offset rows of the moved slots, and waits for its own work before it returns;
+ *      what is enqueued after the call sees the new offsets.  Between r3n_frame_begin and r3n_frame_end -> R3N_ERR_STATE; a live slot
+ *      that owns no words (after a raw r3n_textures_write whose ranges are not ascending, disjoint and 4-word aligned) ->
+ *      R3N_ERR_STATE; both with nothing changed.  R3N_ERR_HIP (a launch, a copy or the wait failed): the context's offsets, allocator
+ *      and mark are the ones from before the call, but passes may have run, so the pool's words are unspecified -- re-send the
+ *      textures with a whole-array write.
+ *      out (may be NULL): textures_moved, words_moved (padded), passes (a pass is one launch, or two through scratch),
+ *      kernel_launches, full_syncs (0 or 1), the high-water mark before and after, and the holes left below it (0 after a call
+ *      without a budget).  r3n_texture_stats counts none of this: its counters stay the update path's. */
+typedef struct r3n_texture_compact_opts {
+    uint64_t max_words, stage_words;
+} r3n_texture_compact_opts;
+typedef struct r3n_texture_compact_result {
+    uint64_t textures_moved, words_moved, passes, kernel_launches, full_syncs, pool_words_before, pool_words_after, free_ranges_after;
+} r3n_texture_compact_result;
+int r3n_textures_compact(r3n_ctx *ctx, const r3n_texture_compact_opts *opts, r3n_texture_compact_result *out);
 /*      Counters of the streamed texture path since creation or the last reset, and the pool's state now.  update_calls: successful
  *      r3n_textures_update calls; kernel_launches: every kernel they enqueued; bytes_staged: payload bytes they copied; full_syncs:
  *      waits for every frame in flight they made; pool_grows: calls in which the pool, the descriptor table or the level-offset

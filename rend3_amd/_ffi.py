@@ -44,6 +44,7 @@ SIGNATURES = {
     "r3n_textures_write_encoded": (cint, [vp, vp, u32, vp, u64]),
     "r3n_textures_update": (cint, [vp, vp, vp, u32, vp, u64]),
     "r3n_textures_remove": (cint, [vp, vp, u32]),
+    "r3n_textures_compact": (cint, [vp, vp, vp]),
     "r3n_texture_stats": (cint, [vp, vp, cint]),
     "r3n_texture_cubes_write": (cint, [vp, vp, u32, vp, u64]),
     "r3n_skybox_set": (cint, [vp, u32]),
@@ -168,6 +169,17 @@ class TextureCounters(ctypes.Structure):
     """r3n_texture_counters"""
     _fields_ = [(name, u64) for name in ("update_calls", "kernel_launches", "bytes_staged", "full_syncs", "pool_grows", "pool_words",
                                          "live_words", "free_ranges")]
+
+
+class TextureCompactOpts(ctypes.Structure):
+    """r3n_texture_compact_opts"""
+    _fields_ = [("max_words", u64), ("stage_words", u64)]
+
+
+class TextureCompactResult(ctypes.Structure):
+    """r3n_texture_compact_result"""
+    _fields_ = [(name, u64) for name in ("textures_moved", "words_moved", "passes", "kernel_launches", "full_syncs", "pool_words_before",
+                                         "pool_words_after", "free_ranges_after")]
 
 
 class Config(ctypes.Structure):

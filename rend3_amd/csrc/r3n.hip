@@ -25,6 +25,7 @@
 #include "normals.h"
 #include "tangents.h"
 #include "texel_alloc.h"
+#include "texel_compact.h"
 #include "texture_jobs.h"
 #include "vertex_block.h"
 
@@ -1609,6 +1610,93 @@ int r3n_textures_remove(r3n_ctx *c, const uint32_t *slots, uint32_t n) {
     c->classes_dirty = true; c->cutout_short_dirty = true;
     ++c->main_epoch;
     return upload_texture_slots(c, sorted, false);
+}
+
+extern "C" int r3n_internal_move_segments(const uint32_t *block, uint64_t o_first, uint64_t o_inst, uint32_t first_wave, uint32_t waves,
+                                          const uint32_t *src, uint32_t *dst, hipStream_t stream);
+
+// Slides the live textures towards pool word 0 (texel_compact.h plans, texture_compact.hip moves).  The plan follows from the live
+// ranges alone -- a wait changes none of them -- so it is made first and a call with nothing to move returns without a wait.
+int r3n_textures_compact(r3n_ctx *c, const r3n_texture_compact_opts *opts, r3n_texture_compact_result *out) {
+    if (!c) return R3N_ERR_INVALID_ARG;
+    const uint64_t max_words = opts ? opts->max_words : 0;
+    const uint64_t stage_words = opts && opts->stage_words ? opts->stage_words : texel_compact::DEFAULT_STAGE_WORDS;
+    if ((stage_words & 3u) != 0u || stage_words < texel_compact::MIN_STAGE_WORDS)
+        return fail(c, R3N_ERR_INVALID_ARG, "textures compact: stage_words must be a multiple of 4 and at least 256");
+    if (c->in_frame) return fail(c, R3N_ERR_STATE, "textures compact: inside a frame");
+    std::vector<texel_compact::Live> live;
+    for (uint32_t slot = 0; slot < c->n_textures && slot < c->h_tex_live.size(); ++slot) {
+        if (!c->h_tex_live[slot]) continue;
+        if (!c->h_tex_words[slot])
+            return fail(c, R3N_ERR_STATE, "textures compact: a live slot owns no words (a raw r3n_textures_write whose ranges are not ascending, disjoint and 4-word aligned)");
+        live.push_back(texel_compact::Live{c->h_tex_descs[slot].offset, c->h_tex_words[slot], slot});
+    }
+    const texel_compact::Plan plan = texel_compact::plan(live, max_words, stage_words);
+    r3n_texture_compact_result res{};
+    res.pool_words_before = res.pool_words_after = c->tex_alloc.end();
+    res.free_ranges_after = c->tex_alloc.free_ranges();
+    if (plan.moves.empty()) {  // no wait, no launch; parked ranges stay parked
+        if (out) *out = res;
+        return R3N_OK;
+    }
+    std::vector<uint32_t> block;
+    vertex_block::layout layout{};
+    if (!texel_compact::lay_out(plan, block, layout)) return fail(c, R3N_ERR_CAPACITY, "textures compact: more than 2^31 wave slots of copy work in one call");
+    // padded copies stay inside the block: the last texture's padding lies in the 16 bytes of slack behind the mark
+    const texel_compact::Move &last = plan.moves.back();
+    if ((last.src + last.words) * 4u > c->tex_texels.bytes) return fail(c, R3N_ERR_STATE, "textures compact: a live texture ends outside the texel pool");
+
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (!c->tex_stream) HIP_TRY(c, hipStreamCreateWithFlags(&c->tex_stream, hipStreamNonBlocking));
+    const uint64_t syncs_before = c->sync_serial;
+    TRY(sync_all(c));  // a frame in flight may read every word that moves, and every word moved over
+    texture_note_syncs(c);
+    TRY(grow_texture_scratch(c, c->tex_stage, (size_t)std::max<uint64_t>(plan.scratch_words, 1) * 4u));
+    TRY(grow_texture_scratch(c, c->tex_jobs, block.size() * 4u));
+
+    // ---- the passes, in stream order on the texture stream
+    uint32_t *pool = c->tex_texels.as<uint32_t>(), *scratch = c->tex_stage.as<uint32_t>();
+    const uint32_t *table = c->tex_jobs.as<uint32_t>();
+    hipError_t e = hipMemcpyAsync(c->tex_jobs.p, block.data(), block.size() * 4u, hipMemcpyHostToDevice, c->tex_stream);
+    for (size_t i = 0; i < plan.launches.size() && e == hipSuccess; ++i) {
+        const texel_compact::Launch &l = plan.launches[i];
+        e = (hipError_t)r3n_internal_move_segments(table, layout.o_first, layout.o_inst, (uint32_t)l.first_wave, (uint32_t)l.waves,
+                                                   l.kind == texel_compact::SCATTER ? scratch : pool, l.kind == texel_compact::GATHER ? scratch : pool,
+                                                   c->tex_stream);
+    }
+    // ---- the moved slots' table rows: upload_texture_slots reads them from the mirror, so the new offsets go in first and come out
+    // again if anything fails -- allocator, mark and dirty flags follow only when launches, copies and the wait have all succeeded
+    uint32_t lo = ~0u, hi = 0u;
+    for (const texel_compact::Move &m : plan.moves) {
+        c->h_tex_descs[m.slot].offset = (uint32_t)m.dst;
+        lo = std::min(lo, m.slot);
+        hi = std::max(hi, m.slot);
+    }
+    // the rows of every slot from the lowest to the highest moved one, as ONE run: the rows in between hold what the device
+    // already has, and one copy pair costs less than a pair per run of moved slots
+    std::vector<uint32_t> moved(hi - lo + 1u);
+    for (uint32_t s = lo; s <= hi; ++s) moved[s - lo] = s;
+    const int up = e == hipSuccess ? upload_texture_slots(c, moved, true) : R3N_OK;
+    const hipError_t e2 = hipStreamSynchronize(c->tex_stream);  // the update path relies on it: everything that rewrote the pool ended in a wait
+    if (e != hipSuccess || e2 != hipSuccess || up != R3N_OK) {
+        for (const texel_compact::Move &m : plan.moves) c->h_tex_descs[m.slot].offset = (uint32_t)m.src;  // the mirror as it was (r3n.h: the pool's words are not)
+        if (e != hipSuccess) return fail(c, R3N_ERR_HIP, std::string("textures compact: ") + hipGetErrorString(e));
+        if (e2 != hipSuccess) return fail(c, R3N_ERR_HIP, std::string("textures compact: ") + hipGetErrorString(e2));
+        return up;  // (upload_texture_slots has set the message)
+    }
+    texel_compact::rebuild(c->tex_alloc, plan);
+    c->n_texels = c->tex_alloc.end();
+    c->classes_dirty = true; c->cutout_short_dirty = true;
+    ++c->main_epoch;  // the shadow lanes' cutout rasterisers sample the array
+    res.textures_moved = plan.moves.size();
+    res.words_moved = plan.words_moved;
+    res.passes = plan.passes.size();
+    res.kernel_launches = plan.launches.size();
+    res.full_syncs = c->sync_serial - syncs_before;
+    res.pool_words_after = c->tex_alloc.end();
+    res.free_ranges_after = c->tex_alloc.free_ranges();
+    if (out) *out = res;
+    return R3N_OK;
 }
 
 int r3n_texture_stats(r3n_ctx *c, r3n_texture_counters *out, int reset) {

@@ -79,6 +79,20 @@ public:
         trim();
     }
 
+    // The state a compaction leaves (texel_compact.h): `live` = the textures' words [start, end), ascending and disjoint in padded
+    // form, start a multiple of 4 (end need not be).  Holes are the complement below the last texture's end, nothing is parked --
+    // the caller has waited for every reader.
+    void rebuild(const std::vector<Range> &live) {
+        free_.clear();
+        parked_.clear();
+        uint64_t cur = 0;
+        for (const Range &r : live) {
+            if (r.start > cur) free_.push_back(Range{cur, r.start});
+            cur = align4(r.end);
+        }
+        end_ = live.empty() ? 0 : live.back().end;
+    }
+
 private:
     std::vector<Range> free_, parked_;  // each sorted by start, coalesced; disjoint from each other
     uint64_t end_ = 0;

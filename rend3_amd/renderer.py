@@ -195,7 +195,8 @@ class EvalOutput:
 class Renderer:
     """World bookkeeping feeding the object/mesh/material/light buffers of the C ABI."""
 
-    def __init__(self, handedness=host.LEFT, aspect_ratio=None, device=0, max_big_items=None, blend_sort="host", texture_upload="whole"):
+    def __init__(self, handedness=host.LEFT, aspect_ratio=None, device=0, max_big_items=None, blend_sort="host", texture_upload="whole",
+                 texture_compact=None):
         self.lib = _ffi.lib()
         if blend_sort not in ("host", "gpu"):
             raise ValueError("blend_sort: 'host' or 'gpu'")
@@ -208,6 +209,11 @@ class Renderer:
         self._tex_live = []       # "stream": per slot, True while the slot holds a texture (queued ones included)
         self._tex_queue = []      # "stream": (slot, desc row without offset, bytes) not yet sent
         self._tex_removals = []   # "stream": slots whose removal is not yet sent
+        # "stream": None = the pool is never compacted by itself; a fraction f in (0, 1] = r3n_textures_compact at a texture flush in
+        # front of a frame, when more than f of the pool below its high-water mark is holes
+        if texture_compact is not None and not (0.0 < float(texture_compact) <= 1.0):
+            raise ValueError("texture_compact: None or a fraction in (0, 1]")
+        self._texture_compact = None if texture_compact is None else float(texture_compact)
         # where the transparent pass's back-to-front order is sorted: "host" = host.blend_draw_order + r3n_blend_order_write every
         # frame; "gpu" = the blend set goes up when the world changes (r3n_blend_objects_write), r3n_blend_sort orders it per frame
         self.blend_sort = blend_sort
@@ -615,6 +621,16 @@ class Renderer:
             raise ValueError("texture_upload cannot change once textures exist")
         self._texture_upload = mode
 
+    @property
+    def texture_compact(self):
+        return self._texture_compact
+
+    @texture_compact.setter
+    def texture_compact(self, fraction):
+        if fraction is not None and not (0.0 < float(fraction) <= 1.0):
+            raise ValueError("texture_compact: None or a fraction in (0, 1]")
+        self._texture_compact = None if fraction is None else float(fraction)
+
     def add_texture_2d(self, rgba8, srgb=True, mip_count=1, mip_source="uploaded"):
         """Renderer::add_texture_2d with Texture{data, format, size, mip_count, mip_source}: rgba8 = (H, W, 4) u8;
         format Rgba8UnormSrgb | Rgba8Unorm; mip_count int or "maximum"; mip_source "uploaded" | "generated".
@@ -676,7 +692,28 @@ class Renderer:
         self._tex_live[handle] = False
         self._tex_removals.append(handle)
 
-    def _flush_textures(self):
+    def compact_textures(self, max_words=0, stage_words=0):
+        """Slides the live textures towards pool word 0 on the GPU (r3n_textures_compact), so that what removals left free is reused
+        and the pool stops growing.  texture_upload="stream" only.  max_words: stop after that many words (0 = all); stage_words:
+        scratch words the call may use (0 = the library's default).  Pending textures and removals are sent first.  Returns
+        r3n_texture_compact_result as a dict."""
+        if self._texture_upload != "stream":
+            raise ValueError("compact_textures needs Renderer(texture_upload='stream'): the whole-array path lays its pool out densely")
+        self._flush_textures()
+        opts = _ffi.TextureCompactOpts(max_words=int(max_words), stage_words=int(stage_words))
+        out = _ffi.TextureCompactResult()
+        self._check(self.lib.r3n_textures_compact(self.ctx, ctypes.byref(opts), ctypes.byref(out)), "r3n_textures_compact")
+        return {name: int(getattr(out, name)) for name, _ in _ffi.TextureCompactResult._fields_}
+
+    def _flush_textures(self, before_frame=False):
+        changed = bool(self._tex_removals or self._tex_queue)
+        self._send_textures()
+        if before_frame and changed and self._texture_compact is not None and self._texture_upload == "stream":
+            st = self.texture_stats()
+            if st["pool_words"] - st["live_words"] > self._texture_compact * st["pool_words"]:
+                self.compact_textures()
+
+    def _send_textures(self):
         if self._tex_removals:
             slots = np.array(self._tex_removals, dtype=np.uint32)
             self._check(self.lib.r3n_textures_remove(self.ctx, _ffi.ptr(slots), len(slots)), "r3n_textures_remove")
@@ -967,7 +1004,7 @@ class Renderer:
 
     # ------------------------------------------------------------------ per-frame evaluation
     def evaluate_instructions(self):
-        self._flush_textures()
+        self._flush_textures(before_frame=True)
         self._flush_cubes()
         return self._evaluate_instructions()
 
@@ -1092,7 +1129,7 @@ class Renderer:
             d.viewport_header = base + _ffi.HostFrame.viewport_header.offset
             d.shadow_views = base + _ffi.HostFrame.shadow_views.offset
             d.directional_buffer = base + _ffi.HostFrame.directional_buffer.offset
-        self._flush_textures()
+        self._flush_textures(before_frame=True)
         self._flush_cubes()
         self._flush_objects()
         self._flush_morphs()  # morph, then skin (the skinning node is inside r3n_render_frame)

@@ -83,6 +83,9 @@ def add_arguments(ap):
     ap.add_argument("--blend-sort", choices=("host", "gpu"), default="host",
                     help="where the transparent pass's back-to-front order is sorted (not in the reference, whose CPU batcher sorts): "
                          "host = every frame on the CPU, gpu = r3n_blend_sort")
+    ap.add_argument("--texture-compact", type=float, default=None, metavar="F",
+                    help="with --texture-upload stream: compact the texel pool on the GPU (r3n_textures_compact) in front of a frame when "
+                         "more than the fraction F in (0, 1] of it is holes; default: never")
     ap.add_argument("--texture-upload", choices=("whole", "stream"), default="whole",
                     help="how 2D textures reach the device: whole = the bindless array is re-sent when it changed, stream = single "
                          "entries are added and removed in place (r3n_textures_update), as the reference's TextureManager does")
@@ -113,7 +116,7 @@ def settings_from(args):
                 camera=args.camera or DEFAULT_CAMERA, skybox=getattr(args, "skybox", None),
                 blend_sort=getattr(args, "blend_sort", "host"), morph_normals=getattr(args, "morph_normals", "base"),
                 build_tangents=getattr(args, "build_tangents", False), morph_tangents=getattr(args, "morph_tangents", "base"),
-                texture_upload=getattr(args, "texture_upload", "whole"))
+                texture_upload=getattr(args, "texture_upload", "whole"), texture_compact=getattr(args, "texture_compact", None))
 
 
 def default_settings(**over):
@@ -167,6 +170,10 @@ def build(r, hm, mk, settings):
         if not hasattr(r, "texture_upload"):
             raise ValueError("--texture-upload stream: this renderer re-sends the whole array")
         r.texture_upload = settings["texture_upload"]
+    if settings.get("texture_compact") is not None:
+        if settings.get("texture_upload", "whole") != "stream":
+            raise ValueError("--texture-compact needs --texture-upload stream: the whole-array path lays its pool out densely")
+        r.texture_compact = settings["texture_compact"]
     light = None
     if settings["directional_light"] is not None:  # setup (mod.rs:463-472)
         light = r.add_directional_light(color=(1.0, 1.0, 1.0), intensity=settings["directional_light_intensity"],
