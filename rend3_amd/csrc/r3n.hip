@@ -104,9 +104,16 @@ struct r3n_ctx {
     // Frames in flight.  The resolve is VALU-bound and everything before it (culls, rasterisers, Hi-Z) is latency- and
     // atomic-bound, so frame N's resolve runs on its own stream while the main stream and the lanes already work on frame
     // N + 1.  Everything the resolve reads that the next frame rewrites exists twice; the two sets swap at frame_begin:
-    //   vis, atlas, viewport.baked  <->  alt_*;  fu, dir_buf, point_buf, every camera's d_hdr: the frame-constants block of the slot
+    //   vis, atlas, viewport.baked, tri_rec  <->  alt_*;  fu, dir_buf, point_buf, every camera's d_hdr: the frame-constants block of the slot
     // shade_done[slot] (recorded on the shade stream after the resolve of the frame that used `slot`) is what the main
     // stream waits for before it clears that slot's targets two frames later.  R3N_PIPELINE=0 disables the overlap.
+    // The shadow lanes run from frame to frame without joining the main stream: what a lane kernel writes besides its camera's own
+    // buffers -- the atlas, the work-queue counters -- and the constants it reads are per frame slot too, so the main stream's head
+    // of frame N + 1 (constants copy, clears) does not wait for the lanes of frame N; it waits for shade_done of frame N - 1, whose
+    // resolve waited for ITS lanes.  The resolve's prepass (triangle records, one set per slot) ends the viewport chain on the main
+    // stream, so the shade stream carries the resolve alone and one frame's resolve follows the previous one's directly.
+    // close_frame keeps the join wherever the frame's resolve did not go to the shade stream, or outside work is ordered against
+    // the streams (communicators, exchange callbacks); join_lanes / join_frames give everything else the order it needs.
     hipStream_t shade = nullptr;
     hipEvent_t vp_ev = nullptr, shade_done[2] = {nullptr, nullptr};
     bool shade_pending[2] = {false, false};
@@ -132,7 +139,11 @@ struct r3n_ctx {
     bool fb_pending[kFbHost] = {};
     // fork_lane is a no-op while nothing the lanes depend on has been enqueued on the main stream since their last fork
     uint64_t main_epoch = 1, lane_epoch[R3N_AUX_STREAMS] = {};
-    DevBuf big_count_all;  // the work-queue counters of every lane: zeroed once per frame
+    // the work-queue counters of every lane, one block per frame slot (big_count[] views the current slot's): r3n_frame_begin zeroes
+    // its slot's block on the main stream while the lanes may still be consuming the other block's counters (previous frame)
+    DevBuf big_count_all;
+    static constexpr size_t kBigCountWords = (size_t)(1 + R3N_QLANES) * 64 * R3N_BIGQ;  // per slot
+    bool exchanged_this_frame = false;  // an exchange callback / r3n_exchange_*: outside work was ordered against this frame's streams
     std::vector<uint8_t> h_dir, h_point;   // the light buffers as last written (uploaded into the frame's slot at frame_begin)
     uint64_t lights_version = 1, slot_lights_version[2] = {0, 0};
     hipEvent_t join_ev[R3N_AUX_STREAMS] = {};
@@ -204,7 +215,9 @@ struct r3n_ctx {
     r3n_hiz_desc hizd{};
     bool hiz_plane_ready = false;  // mip 0 already holds the (merged) pass-1 depth: r3n_exchange_depth
     // transparent pass (row N3)
-    DevBuf tri_rec, tri_seen;  // per-triangle vertex-stage records of the resolve (kernels_raster.h TriRecord)
+    // per-triangle vertex-stage records of the resolve (kernels_raster.h TriRecord), written by the prepass on the main stream; one
+    // set per frame slot while frames are pipelined (swapped at frame_begin: the previous frame's resolve still reads the other)
+    DevBuf tri_rec, alt_tri_rec, tri_seen;
     DevBuf blend_order, blend_rank_base, frag_keys, frag_vals, frag_count, frag_head, samples16;
     uint32_t *status_host = nullptr, *status_dev = nullptr;  // host-mapped word the kernels raise when a fixed-size buffer ran out
     std::vector<uint32_t> h_blend_order;
@@ -324,6 +337,7 @@ static void crumb(const r3n_ctx *c, const char *what, long long a = -1, long lon
 int sync_all(r3n_ctx *c);
 int join_shade(r3n_ctx *c);
 int join_lanes(r3n_ctx *c);
+int join_frames(r3n_ctx *c);
 
 // Grow-only device buffer.  preserve: keep old contents; fill: byte value for the newly allocated tail.
 int ensure(r3n_ctx *c, DevBuf &b, size_t bytes, bool preserve, int fill) {
@@ -517,6 +531,12 @@ int join_shade(r3n_ctx *c) {
     }
     return R3N_OK;
 }
+// Order the main stream after every frame still in flight: the shadow lanes' views (r3n_frame_end leaves them running while
+// frames are pipelined) and the latest resolve.  Whatever rewrites, on the main stream, a buffer they read calls this first.
+int join_frames(r3n_ctx *c) {
+    int r = join_lanes(c);
+    return r != R3N_OK ? r : join_shade(c);
+}
 int sync_all(r3n_ctx *c) {
     crumb(c, "sync_all");
     int r = join_lanes(c);
@@ -670,7 +690,7 @@ int run_bake_and_object_pass(r3n_ctx *c, CamState &s, int idx, ObjOwn own, hipSt
 int refresh_tri_base(r3n_ctx *c) {
     if (!c->tri_base_dirty) return R3N_OK;
     if (c->capacity == 0) { c->tri_base_dirty = false; return R3N_OK; }
-    TRY(join_shade(c));  // frames in flight: the previous frame's resolve reads tri_base / slot_table
+    TRY(join_frames(c));  // frames in flight: the previous frame's resolve and shadow lanes read tri_base / slot_table
     TRY(ensure(c, c->tri_base, (size_t)c->capacity * 4u, false, 0));
     r3n_camera_header240 h{};
     h.object_count = c->capacity;
@@ -919,9 +939,9 @@ r3n_ctx *r3n_create(int hip_device, const r3n_config *config) {
         c->dir_buf.p = c->fb_dev[0].as<uint8_t>() + r3n_ctx::kFbDir; c->dir_buf.bytes = r3n_ctx::kFbShadowHdr - r3n_ctx::kFbDir;
         c->point_buf.p = c->fb_dev[0].as<uint8_t>() + r3n_ctx::kFbPoint; c->point_buf.bytes = 8448;
     }
-    ok = ok && ensure(c, c->big_count_all, (size_t)(1 + R3N_QLANES) * 64 * R3N_BIGQ * 4, false, 0) == R3N_OK;
+    ok = ok && ensure(c, c->big_count_all, 2 * r3n_ctx::kBigCountWords * 4, false, 0) == R3N_OK;
     for (int lane = 0; ok && lane < 1 + R3N_QLANES; ++lane) {
-        c->big_count[lane].p = c->big_count_all.as<uint32_t>() + (size_t)lane * 64 * R3N_BIGQ;  // not owned
+        c->big_count[lane].p = c->big_count_all.as<uint32_t>() + (size_t)lane * 64 * R3N_BIGQ;  // not owned; r3n_frame_begin points it into the frame slot's block
         c->big_count[lane].bytes = 64 * R3N_BIGQ * 4;
         ok = ensure(c, c->big_items[lane], (size_t)c->big_capacity * R3N_BIGQ * sizeof(r3n_big_item), false, -1) == R3N_OK &&
              ensure(c, c->big_uv[lane], (size_t)c->big_capacity * R3N_BIGQ * sizeof(r3n_big_uv), false, -1) == R3N_OK;
@@ -987,7 +1007,7 @@ void r3n_destroy(r3n_ctx *c) {
     DevBuf *bufs[] = {&c->mesh, &c->objects, &c->spheres, &c->obj_meta, &c->materials, &c->material_keys, &c->fb_dev[0], &c->fb_dev[1], &c->big_count_all, &c->owners,
                       &c->tri_base, &c->slot_table, &c->skin_inputs, &c->skin_matrices, &c->skin_wave_skeleton,
                       &c->skin_wave_first, &c->skin_joint_counts, &c->morph_block, &c->normals_block, &c->tangents_block, &c->vis, &c->hdr16, &c->out8, &c->out_f32, &c->atlas, &c->hiz, &c->alt_vis, &c->alt_atlas, &c->alt_vp_baked, &c->srgb_lut, &c->srgb_thr, &c->tex_descs, &c->tex_texels, &c->tex_level_off, &c->srgb8_decode, &c->tex_stage, &c->tex_jobs,
-                      &c->tri_rec, &c->tri_seen, &c->blend_order, &c->blend_rank_base, &c->frag_keys, &c->frag_vals, &c->frag_head,
+                      &c->tri_rec, &c->alt_tri_rec, &c->tri_seen, &c->blend_order, &c->blend_rank_base, &c->frag_keys, &c->frag_vals, &c->frag_head,
                       &c->frag_count, &c->samples16, &c->anim_rigs, &c->anim_joints, &c->anim_clips, &c->anim_tracks,
                       &c->anim_times, &c->anim_values, &c->pose_requests, &c->edge_list, &c->edge_count, &c->material_feat, &c->view_lights[0],
                       &c->view_lights[1], &c->cube_texels, &c->blend_set_slots, &c->blend_set_locations, &c->blend_sort_scratch};
@@ -1035,7 +1055,7 @@ void *r3n_stream(r3n_ctx *c) { return c ? (void *)c->stream : nullptr; }
 int r3n_mesh_buffer_write(r3n_ctx *c, uint64_t byte_offset, const void *data, uint64_t bytes) {
     if (!c || (!data && bytes) || (byte_offset & 3u) || (bytes & 3u)) return fail(c, R3N_ERR_INVALID_ARG, "mesh write: bad args");
     HIP_TRY(c, hipSetDevice(c->device));
-    TRY(join_shade(c));  // frames in flight: world buffers are read by the previous frame's resolve
+    TRY(join_frames(c));  // frames in flight: world buffers are read by the previous frame's resolve and shadow lanes
     TRY(ensure(c, c->mesh, byte_offset + bytes, true, 0));
     if (bytes) {
         HIP_TRY(c, hipMemcpyAsync(static_cast<char *>(c->mesh.p) + byte_offset, data, bytes, hipMemcpyHostToDevice, c->stream));
@@ -1051,7 +1071,7 @@ int r3n_objects_write(r3n_ctx *c, const uint32_t *slots, const r3n_object128 *re
         if (slots[i] >= capacity) return fail(c, R3N_ERR_INVALID_ARG, "objects write: slot >= capacity");
     if (n == 0 && capacity == c->capacity) return R3N_OK;  // nothing dirty: no upload, no synchronisation
     HIP_TRY(c, hipSetDevice(c->device));
-    TRY(join_shade(c));
+    TRY(join_frames(c));
     TRY(ensure(c, c->objects, (size_t)capacity * sizeof(r3n_object128), true, 0));
     TRY(ensure(c, c->spheres, (size_t)capacity * sizeof(float4), true, 0));
     TRY(ensure(c, c->obj_meta, (size_t)capacity * 4u, true, 0));
@@ -1118,7 +1138,7 @@ int r3n_objects_write(r3n_ctx *c, const uint32_t *slots, const r3n_object128 *re
 int r3n_materials_write(r3n_ctx *c, const uint32_t *slots, const r3n_material208 *records, const uint8_t *keys, uint32_t n) {
     if (!c || (n && (!slots || !records || !keys))) return fail(c, R3N_ERR_INVALID_ARG, "materials write: null");
     HIP_TRY(c, hipSetDevice(c->device));
-    TRY(join_shade(c));
+    TRY(join_frames(c));
     uint32_t need = c->n_materials;
     for (uint32_t i = 0; i < n; ++i) {
         if (keys[i] > R3N_KEY_BLEND) return fail(c, R3N_ERR_INVALID_ARG, "materials write: bad key");
@@ -1608,6 +1628,7 @@ int r3n_textures_remove(r3n_ctx *c, const uint32_t *slots, uint32_t n) {
         c->h_tex_descs[slot].width = c->h_tex_descs[slot].height = 0;
     }
     c->classes_dirty = true; c->cutout_short_dirty = true;
+    TRY(join_lanes(c));  // the table rows go up on the main stream: behind the cutout rasterisers of the shadow views still in flight
     ++c->main_epoch;
     return upload_texture_slots(c, sorted, false);
 }
@@ -1761,6 +1782,7 @@ static int frame_begin_impl(r3n_ctx *c, const r3n_frame_uniforms496 *u, uint32_t
     c->slot = (int)(c->frame_no++ & 1u);
     std::swap(c->vis, c->alt_vis);
     std::swap(c->atlas, c->alt_atlas);
+    if (c->overlap && c->multi_stream) std::swap(c->tri_rec, c->alt_tri_rec);  // (a context that never pipelines keeps one set)
     std::swap(c->viewport.baked, c->alt_vp_baked);
     uint8_t *dev = c->fb_dev[c->slot].as<uint8_t>();
     c->fu.p = dev + r3n_ctx::kFbUniforms;
@@ -1768,6 +1790,8 @@ static int frame_begin_impl(r3n_ctx *c, const r3n_frame_uniforms496 *u, uint32_t
     c->point_buf.p = dev + r3n_ctx::kFbPoint;
     c->viewport.d_hdr.p = dev + r3n_ctx::kFbViewportHdr; c->viewport.d_hdr.bytes = 256;
     for (auto &kv : c->shadows) { kv.second.d_hdr.p = dev + r3n_ctx::kFbShadowHdr + 256u * (size_t)kv.first; kv.second.d_hdr.bytes = 256; }
+    uint32_t *const slot_counts = c->big_count_all.as<uint32_t>() + (size_t)c->slot * r3n_ctx::kBigCountWords;
+    for (int lane = 0; lane < 1 + R3N_QLANES; ++lane) c->big_count[lane].p = slot_counts + (size_t)lane * 64 * R3N_BIGQ;
     if (c->shade_pending[c->slot]) {  // the resolve that last read this set (two frames ago)
         HIP_TRY(c, hipStreamWaitEvent(c->stream, c->shade_done[c->slot], 0));
         c->shade_pending[c->slot] = false;
@@ -1808,9 +1832,11 @@ static int frame_begin_impl(r3n_ctx *c, const r3n_frame_uniforms496 *u, uint32_t
     {
         Timed t(c, R3N_STAGE_CLEAR);
         // ONE launch: depth clear 0.0 / no triangle (base.rs:259-263), shadow atlas clear 0.0 (clear.rs:4-20), and the work-queue
-        // counters of every r3n_forward of the frame, every lane (r3n_frame_end ordered the main stream behind the lanes' last use)
+        // counters of every r3n_forward of the frame, every lane.  All three belong to this frame slot: the lanes may still be
+        // drawing the previous frame's views into the other slot's atlas through the other slot's counters (close_frame); what
+        // last used THIS slot's is two frames old and lies behind the shade_done[slot] wait above, or behind a join.
         hipLaunchKernelGGL(k_frame_clear, dim3(2048), dim3(256), 0, c->stream, c->vis.as<uint32_t>(), npix * samples * 2, c->atlas.as<uint32_t>(), apix,
-                           c->big_count_all.as<uint32_t>(), c->big_count_all.bytes / 4);
+                           slot_counts, r3n_ctx::kBigCountWords);
         TRY(check_launch(c, "k_frame_clear"));
     }
     ++c->main_epoch;
@@ -1819,6 +1845,8 @@ static int frame_begin_impl(r3n_ctx *c, const r3n_frame_uniforms496 *u, uint32_t
     c->in_frame = true;
     for (auto &f : c->forward_index_lane) f = 0;
     c->resolved_this_frame = false;
+    c->resolve_on_shade = false;  // (a frame without a resolve is joined like an unpipelined one: close_frame)
+    c->exchanged_this_frame = false;
     c->blended_this_frame = false;
     c->sky_window = false;
     c->hiz_plane_ready = false;
@@ -1839,7 +1867,7 @@ int r3n_skinning(r3n_ctx *c, const r3n_skinning_input40 *inputs, uint32_t n, con
     if (!joint_matrices && c->n_pose_requests == 0) return fail(c, R3N_ERR_INVALID_ARG, "skinning: no joint matrices and no queued poses");
     if (c->pose_matrix_end > n_joints) return fail(c, R3N_ERR_INVALID_ARG, "skinning: a queued pose writes past the joint matrices");
     HIP_TRY(c, hipSetDevice(c->device));
-    TRY(join_shade(c));  // frames in flight: the previous frame's resolve reads the skinned attribute runs this rewrites
+    TRY(join_frames(c));  // frames in flight: the previous frame's resolve and shadow lanes read the skinned attribute runs this rewrites
     const size_t mesh_words = c->mesh.bytes / 4;
     for (uint32_t i = 0; i < n; ++i) {
         const r3n_skinning_input40 &in = inputs[i];
@@ -1958,7 +1986,7 @@ int r3n_morph(r3n_ctx *c, const r3n_morph_input48 *inputs, uint32_t n, const flo
     }
     if (total_waves > MAX_WAVES) return fail(c, R3N_ERR_UNSUPPORTED, "morph: more than 2^31 wave slots in one call");
     HIP_TRY(c, hipSetDevice(c->device));
-    TRY(join_shade(c));  // frames in flight: the previous frame's resolve reads the runs this rewrites
+    TRY(join_frames(c));  // frames in flight: the previous frame's resolve and shadow lanes read the runs this rewrites
     if (total_waves == 0) return R3N_OK;  // (instances of zero vertices)
     std::vector<uint32_t> block;
     const layout l = lay_out(block, n, sizeof(r3n_morph_rec64) / 4, total_waves,
@@ -2016,7 +2044,7 @@ int r3n_vertex_normals(r3n_ctx *c, const r3n_normals_input32 *inputs, uint32_t n
     }
     if (total_waves > MAX_WAVES) return fail(c, R3N_ERR_UNSUPPORTED, "normals: more than 2^31 wave slots in one call");
     HIP_TRY(c, hipSetDevice(c->device));
-    TRY(join_shade(c));  // frames in flight: the previous frame's resolve reads the runs this rewrites
+    TRY(join_frames(c));  // frames in flight: the previous frame's resolve and shadow lanes read the runs this rewrites
     std::vector<uint32_t> block;
     const layout l = lay_out(block, n, sizeof *inputs / 4, total_waves, [&](uint32_t i) { return waves(inputs[i].vertex_count, R3N_NORMALS_WAVE_VERTICES); });
     std::memcpy(block.data(), inputs, (size_t)n * sizeof *inputs);
@@ -2055,7 +2083,7 @@ int r3n_vertex_tangents(r3n_ctx *c, const r3n_tangents_input32 *inputs, uint32_t
     }
     if (total_waves > MAX_WAVES) return fail(c, R3N_ERR_UNSUPPORTED, "tangents: more than 2^31 wave slots in one call");
     HIP_TRY(c, hipSetDevice(c->device));
-    TRY(join_shade(c));  // frames in flight: the previous frame's resolve reads the runs this rewrites
+    TRY(join_frames(c));  // frames in flight: the previous frame's resolve and shadow lanes read the runs this rewrites
     std::vector<uint32_t> block;
     const layout l = lay_out(block, n, sizeof *inputs / 4, total_waves, [&](uint32_t i) { return waves(inputs[i].vertex_count, R3N_TANGENTS_WAVE_VERTICES); });
     std::memcpy(block.data(), inputs, (size_t)n * sizeof *inputs);
@@ -2564,6 +2592,31 @@ int r3n_resolve_opaque(r3n_ctx *c) {
     // follows (it continues on the main stream with the HDR target) or while stage timing is on.
     const bool on_shade = c->overlap && c->multi_stream && (!c->timing || c->tune.timed_pipeline != 0u) && c->blend_tris == 0;
     hipStream_t stream = on_shade ? c->shade : c->stream;
+    ShadeArgs a = make_shade_args(c, r0, r1);
+    const bool tex = c->n_textures > 0;
+    if (blend_samples || sky_samples) a.samples_out = c->samples16.as<ushort4>();
+    if (use_records && c->samples == 1) a.view_lights = c->view_lights[c->slot].as<ViewLights>();
+    if (classes && c->resolve_variants != 0u) {
+        a.material_feat = c->material_feat.as<uint32_t>();
+        a.variants = c->resolve_variants;
+    }
+    // the vertex stage runs once per visible triangle instead of once per pixel / sample (256 B per triangle slot;
+    // skipped for worlds whose record array would pass 8 GiB).  This prepass (k_mark_visible, k_vertex_stage) reads the viewport's
+    // keys and the world, nothing the shadow views write, and it ends the viewport chain on the MAIN stream: there it runs beside
+    // the previous frame's resolve and this frame's lanes instead of in front of the resolve on the shade stream, the frame's
+    // longest chain.  The records exist once per frame slot for that (tri_rec / alt_tri_rec: the previous frame's resolve is
+    // still reading the other set); the flags are the prepass's own, used on the main stream alone.
+    if (!on_shade) {
+        TRY(join_lanes(c));  // the shadow atlas must be complete
+        TRY(join_shade(c));  // an earlier frame's resolve may still be writing the HDR / output targets (or reading these records)
+    }
+    if (use_records) {
+        a.tri_rec = c->tri_rec.as<TriRecord>();
+        a.seen = c->tri_seen.as<unsigned char>();
+        Timed t(c, R3N_STAGE_VERTEX, c->stream);
+        const size_t first = (size_t)r0 * c->width * c->samples, npx = (size_t)(r1 - r0) * c->width * c->samples;  // keys, not pixels
+        HIP_TRY(c, (hipError_t)r3n_internal_shade_prepass(&a, tex ? 1 : 0, first, npx, c->stream));
+    }
     if (on_shade) {
         HIP_TRY(c, hipEventRecord(c->vp_ev, c->stream));
         HIP_TRY(c, hipStreamWaitEvent(c->shade, c->vp_ev, 0));
@@ -2571,31 +2624,11 @@ int r3n_resolve_opaque(r3n_ctx *c) {
             if (c->aux_used[k]) {  // the shadow atlas must be complete
                 HIP_TRY(c, hipEventRecord(c->join_ev[k], c->aux[k]));
                 HIP_TRY(c, hipStreamWaitEvent(c->shade, c->join_ev[k], 0));
-                // aux_used[k] stays set: r3n_frame_end still has to order the MAIN stream behind the lanes, because the
-                // next frame's r3n_uniform_bake uploads the shadow camera headers (single-buffered) on the main stream
+                // aux_used[k] stays set: the MAIN stream is not behind the lanes (close_frame decides whether it has to be; until
+                // then every join_lanes -- a read-back, a world edit -- still finds the lane)
             }
-    } else {
-        TRY(join_lanes(c));  // the shadow atlas must be complete
-        TRY(join_shade(c));  // an earlier frame's resolve may still be writing the HDR / output targets
-    }
-    ShadeArgs a = make_shade_args(c, r0, r1);
-    if (blend_samples || sky_samples) a.samples_out = c->samples16.as<ushort4>();
-    if (use_records && c->samples == 1) a.view_lights = c->view_lights[c->slot].as<ViewLights>();
-    if (classes && c->resolve_variants != 0u) {
-        a.material_feat = c->material_feat.as<uint32_t>();
-        a.variants = c->resolve_variants;
     }
     c->resolved_this_frame = true;
-    const bool tex = c->n_textures > 0;
-    // the vertex stage runs once per visible triangle instead of once per pixel / sample (256 B per triangle slot;
-    // skipped for worlds whose record array would pass 8 GiB)
-    if (use_records) {
-        a.tri_rec = c->tri_rec.as<TriRecord>();
-        a.seen = c->tri_seen.as<unsigned char>();
-        Timed t(c, R3N_STAGE_VERTEX, stream);
-        const size_t first = (size_t)r0 * c->width * c->samples, npx = (size_t)(r1 - r0) * c->width * c->samples;  // keys, not pixels
-        HIP_TRY(c, (hipError_t)r3n_internal_shade_prepass(&a, tex ? 1 : 0, first, npx, stream));
-    }
     {
         Timed t(c, R3N_STAGE_SHADE, stream);
         if (split) {
@@ -2986,7 +3019,16 @@ int r3n_tonemap(r3n_ctx *c, void *host_rgba8, uint64_t pitch) {
 // (r3n_render_frame's Closer) must not consume the report of an earlier frame's overflow.
 static int close_frame(r3n_ctx *c) {
     HIP_TRY(c, hipSetDevice(c->device));
-    TRY(join_lanes(c));  // the next frame's clears (main stream) must not overtake this frame's shadow work
+    // Pipelined frames (this frame's resolve went to the shade stream, nobody outside orders work against the streams): the lanes
+    // keep running and the main stream goes on to the next frame's head.  That head touches nothing the lanes use -- its constants
+    // copy and its clears (targets, atlas, work-queue counters) go to the OTHER frame slot, whose last users lie behind
+    // shade_done[slot] (that resolve waited for its frame's lanes); the lanes' own per-camera buffers and work queues are touched
+    // by their stream alone, in stream order.  aux_used[] stays set, so whatever does need the main stream behind the lanes
+    // (join_lanes: read-backs, r3n_sync, world edits, reallocations, an unpipelined resolve) still gets that order.
+    // Every other configuration: the next frame's clears (main stream) must not overtake this frame's shadow work.
+    const bool lanes_run_on = c->overlap && c->multi_stream && c->resolve_on_shade && !c->comm.on && !c->exchanged_this_frame &&
+                              (!c->timing || c->tune.timed_pipeline != 0u);
+    if (!lanes_run_on) TRY(join_lanes(c));
     auto flip = [](CamState &s) {
         if (s.culled) { s.cur = 1 - s.cur; s.has_prev = true; }
         s.culled = false;
@@ -3267,6 +3309,7 @@ int r3n_render_frame(r3n_ctx *c, const r3n_frame_desc *d) {
     } closer{c};
     struct Fused { r3n_ctx *c; ~Fused() { c->fused_frame = false; } } fused{c};
     c->fused_frame = true;
+    if (d->exchange) c->exchanged_this_frame = true;  // the callback orders its own work against the streams: the frame is joined at its end
     const bool masked = native || (d->flags & R3N_FRAME_SHADOW_MASK) != 0u;
     auto mine = [&](uint32_t v) {
         if (native) return shadow_part_of(c->comm.world, d->n_shadow_views, c->comm.rank, v) >= 0;
@@ -3382,6 +3425,7 @@ int r3n_exchange_depth(r3n_ctx *c, void **depth_f32, uint64_t *count) {
     }
     TRY(check_launch(c, "k_hiz_mip0"));
     c->hiz_plane_ready = true;
+    c->exchanged_this_frame = true;
     if (depth_f32) *depth_f32 = c->hiz.p;
     if (count) *count = n;
     return R3N_OK;
@@ -3389,6 +3433,7 @@ int r3n_exchange_depth(r3n_ctx *c, void **depth_f32, uint64_t *count) {
 int r3n_exchange_buffers(r3n_ctx *c, void **vis, uint64_t *vis_count, void **atlas, uint64_t *atlas_count) {
     if (!c || !c->vis.p) return fail(c, R3N_ERR_STATE, "exchange_buffers: no frame targets yet");
     TRY(join_lanes(c));  // collectives are ordered on the main stream
+    c->exchanged_this_frame = true;
     if (vis) *vis = c->vis.p;
     if (vis_count) *vis_count = (uint64_t)c->width * c->height * c->samples;
     if (atlas) *atlas = c->atlas.p;
@@ -3398,6 +3443,7 @@ int r3n_exchange_buffers(r3n_ctx *c, void **vis, uint64_t *vis_count, void **atl
 int r3n_exchange_shadow_stream(r3n_ctx *c, void **atlas, uint64_t *atlas_count, void **stream) {
     if (!c || !c->atlas.p) return fail(c, R3N_ERR_STATE, "exchange_shadow_stream: no shadow atlas yet");
     hipStream_t on = c->stream;
+    c->exchanged_this_frame = true;
     if (c->multi_stream) {
         // lane 1 carries the exchange: behind the main stream's clears / uploads of this frame, and behind the other lanes' views
         TRY(fork_lane(c, 1));
