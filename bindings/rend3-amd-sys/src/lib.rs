@@ -330,6 +330,25 @@ pub struct r3n_texture_compact_result {
 
 #[repr(C)]
 #[derive(Clone, Copy)]
+pub struct r3n_texture_tail16 {
+    pub dst_slot: u32,
+    pub src_slot: u32,
+    pub start_mip: u32,
+    pub mip_count: u32,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct r3n_texture_tail_result {
+    pub textures: u64,
+    pub words_copied: u64,
+    pub kernel_launches: u64,
+    pub full_syncs: u64,
+    pub pool_words_after: u64,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
 pub struct r3n_texture_counters {
     pub update_calls: u64,
     pub kernel_launches: u64,
@@ -435,6 +454,7 @@ extern "C" {
     pub fn r3n_textures_update(ctx: *mut r3n_ctx, slots: *const u32, descs: *const r3n_texture_desc32, n: u32, payload: *const c_void, payload_bytes: u64) -> c_int;
     pub fn r3n_textures_remove(ctx: *mut r3n_ctx, slots: *const u32, n: u32) -> c_int;
     pub fn r3n_textures_compact(ctx: *mut r3n_ctx, opts: *const r3n_texture_compact_opts, out: *mut r3n_texture_compact_result) -> c_int;
+    pub fn r3n_textures_from_texture(ctx: *mut r3n_ctx, items: *const r3n_texture_tail16, n: u32, out: *mut r3n_texture_tail_result) -> c_int;
     pub fn r3n_texture_stats(ctx: *mut r3n_ctx, out: *mut r3n_texture_counters, reset: c_int) -> c_int;
     pub fn r3n_texture_cubes_write(ctx: *mut r3n_ctx, descs: *const r3n_texture_desc32, n_cubes: u32, texels: *const u32, n_texels: u64) -> c_int;
     pub fn r3n_skybox_set(ctx: *mut r3n_ctx, cube_id: u32) -> c_int;

@@ -368,6 +368,40 @@ typedef struct r3n_texture_compact_result {
     uint64_t textures_moved, words_moved, passes, kernel_launches, full_syncs, pool_words_before, pool_words_after, free_ranges_after;
 } r3n_texture_compact_result;
 int r3n_textures_compact(r3n_ctx *ctx, const r3n_texture_compact_opts *opts, r3n_texture_compact_result *out);
+/*      Renderer::add_texture_2d_from_texture (TextureManager::fill_from_texture, rend3/src/managers/texture.rs:198-242: a new texture
+ *      of mip_level_size(start_mip) whose levels are GPU-side copies of levels start_mip .. of `src`), for n textures at once:
+ *      slot items[i].dst_slot receives levels [start_mip, start_mip + mip_count) of the texture in items[i].src_slot (mip_count 0 =
+ *      all that remain).  The new entry has the extents of level start_mip of the source, mip_count levels and the source's pool
+ *      class (RGBA8, RGBA8 sRGB, or four f32 per texel); its words are placed exactly as r3n_textures_update places a texture and
+ *      are copied from the source's inside the pool by ONE launch for the whole call -- a texture's levels lie back to back, so a
+ *      tail is one word range, starting on any word.  Nothing is copied from the host but the call's table and the touched
+ *      descriptor and level-offset rows; nothing is decoded or generated again, so the tail of a generated chain (stored_mips <
+ *      mips), which the host never had, can be kept.  The source is unchanged and may be removed afterwards; two items may name
+ *      one source.
+ *      Sources are resolved against the table as it is before the call: src_slot must hold a live texture that owns its words
+ *      (after a raw r3n_textures_write whose ranges are not ascending, disjoint and 4-word aligned no slot does).  dst_slot must
+ *      hold NO live texture -- removed, never written, or past the table, below table length + n as in r3n_textures_update -- and
+ *      may not be named twice: the reference only ever fills a freshly allocated handle, a live slot is not replaced.  start_mip >=
+ *      the source's mips, or start_mip + mip_count > the source's mips -> refused.  Everything refused returns
+ *      R3N_ERR_INVALID_ARG (a pool beyond 2^32 words, or more than 2^31 wave slots -- 256 16-byte units of one item each -- of copy
+ *      work: R3N_ERR_CAPACITY) before anything changes; n == 0 returns R3N_OK without a wait or a launch.  (R3N_ERR_STATE: a
+ *      destination range overlapping a source, which the allocator never hands out.)
+ *      Frames in flight are waited for under exactly the conditions of r3n_textures_update -- a buffer has to grow (word offsets are
+ *      kept), a destination slot held a texture at some time since the last such wait, or the words were freed since then;
+ *      otherwise the call runs on the texture path's own stream beside the frames and waits for its own work alone.  What is
+ *      enqueued after the call sees the new entries.  R3N_ERR_HIP (a copy, the launch or the wait failed): the context's table,
+ *      allocator and mark are the ones from before the call; the device's rows of the destination slots are unspecified until the
+ *      slots are written again.
+ *      out (may be NULL): textures (n), words_copied (unpadded), kernel_launches (1), full_syncs (0 or 1), and the pool's
+ *      high-water mark afterwards.  r3n_texture_stats counts none of this: its counters stay the update path's (bytes_staged does
+ *      not move; pool_words, live_words and free_ranges describe the pool as always). */
+typedef struct r3n_texture_tail16 {
+    uint32_t dst_slot, src_slot, start_mip, mip_count; /* mip_count 0 = all that remain */
+} r3n_texture_tail16;
+typedef struct r3n_texture_tail_result {
+    uint64_t textures, words_copied, kernel_launches, full_syncs, pool_words_after;
+} r3n_texture_tail_result;
+int r3n_textures_from_texture(r3n_ctx *ctx, const r3n_texture_tail16 *items, uint32_t n, r3n_texture_tail_result *out);
 /*      Counters of the streamed texture path since creation or the last reset, and the pool's state now.  update_calls: successful
  *      r3n_textures_update calls; kernel_launches: every kernel they enqueued; bytes_staged: payload bytes they copied; full_syncs:
  *      waits for every frame in flight they made; pool_grows: calls in which the pool, the descriptor table or the level-offset

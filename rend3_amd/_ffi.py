@@ -45,6 +45,7 @@ SIGNATURES = {
     "r3n_textures_update": (cint, [vp, vp, vp, u32, vp, u64]),
     "r3n_textures_remove": (cint, [vp, vp, u32]),
     "r3n_textures_compact": (cint, [vp, vp, vp]),
+    "r3n_textures_from_texture": (cint, [vp, vp, u32, vp]),
     "r3n_texture_stats": (cint, [vp, vp, cint]),
     "r3n_texture_cubes_write": (cint, [vp, vp, u32, vp, u64]),
     "r3n_skybox_set": (cint, [vp, u32]),
@@ -180,6 +181,16 @@ class TextureCompactResult(ctypes.Structure):
     """r3n_texture_compact_result"""
     _fields_ = [(name, u64) for name in ("textures_moved", "words_moved", "passes", "kernel_launches", "full_syncs", "pool_words_before",
                                          "pool_words_after", "free_ranges_after")]
+
+
+class TextureTail16(ctypes.Structure):
+    """r3n_texture_tail16"""
+    _fields_ = [("dst_slot", u32), ("src_slot", u32), ("start_mip", u32), ("mip_count", u32)]
+
+
+class TextureTailResult(ctypes.Structure):
+    """r3n_texture_tail_result"""
+    _fields_ = [(name, u64) for name in ("textures", "words_copied", "kernel_launches", "full_syncs", "pool_words_after")]
 
 
 class Config(ctypes.Structure):

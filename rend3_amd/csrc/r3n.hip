@@ -26,6 +26,7 @@
 #include "tangents.h"
 #include "texel_alloc.h"
 #include "texel_compact.h"
+#include "texel_tail.h"
 #include "texture_jobs.h"
 #include "vertex_block.h"
 
@@ -1508,94 +1509,169 @@ static int grow_texture_resident(r3n_ctx *c, DevBuf &b, size_t bytes, size_t mos
     return R3N_OK;
 }
 
-int r3n_textures_update(r3n_ctx *c, const uint32_t *slots, const r3n_texture_desc32 *descs, uint32_t n, const void *payload,
-                        uint64_t payload_bytes) {
-    if (!c || (n && (!slots || !descs || !payload))) return fail(c, R3N_ERR_INVALID_ARG, "textures update: null");
-    if (!n) return R3N_OK;
-    // ---- validation and planning: nothing of the context changes before both are through
-    const uint32_t table = c->n_textures;
-    std::vector<r3n_texture_desc32> internal(n);
-    std::vector<uint64_t> words(n);
-    for (uint32_t i = 0; i < n; ++i) {
-        TRY(check_encoded_desc(c, "textures update", descs[i], payload_bytes, internal[i], words[i]));
-        if ((uint64_t)slots[i] >= (uint64_t)table + n)
-            return fail(c, R3N_ERR_INVALID_ARG, "textures update: slot past table length + n (the lowest free index never is)");
-    }
-    std::vector<uint32_t> touched(slots, slots + n);
-    std::sort(touched.begin(), touched.end());
-    if (std::adjacent_find(touched.begin(), touched.end()) != touched.end()) return fail(c, R3N_ERR_INVALID_ARG, "textures update: one slot named twice");
-    const uint32_t new_table = std::max(table, touched.back() + 1u);
+// ---- placing new entries: what r3n_textures_update and r3n_textures_from_texture share.  place_textures plans (nothing of the
+// context changes), prepare_texture_placement waits and grows, commit_texture_placement makes the host mirror follow.
+struct TexturePlacement {
+    uint32_t table = 0, new_table = 0;  // table length before and after
+    std::vector<uint32_t> touched;      // slots whose rows go up, ascending
+    texel_alloc::Pool plan;             // the allocator afterwards
+    bool wait = false, grow_tables = false, grow_pool = false;
+    size_t descs_bytes = 0, rows_bytes = 0, pool_bytes = 0;
+    uint64_t syncs_before = 0;
+};
+// The entries internal[i] (words[i] pool words each) go into slots[i], each below table length + n: refuses a slot named twice and a
+// pool past 2^32 words, decides where the words go (internal[i].offset) and whether every frame in flight has to be waited for -- a
+// slot that was hot, words merged in from the parked list, growth of the pool or a table.  Creates the texture stream.
+static int place_textures(r3n_ctx *c, const std::string &what, const uint32_t *slots, r3n_texture_desc32 *internal, const uint64_t *words, uint32_t n,
+                          TexturePlacement &p) {
+    p.table = c->n_textures;
+    p.touched.assign(slots, slots + n);
+    std::sort(p.touched.begin(), p.touched.end());
+    if (std::adjacent_find(p.touched.begin(), p.touched.end()) != p.touched.end()) return fail(c, R3N_ERR_INVALID_ARG, what + ": one slot named twice");
+    p.new_table = std::max(p.table, p.touched.back() + 1u);
     HIP_TRY(c, hipSetDevice(c->device));
     if (!c->tex_stream) HIP_TRY(c, hipStreamCreateWithFlags(&c->tex_stream, hipStreamNonBlocking));
     texture_note_syncs(c);
-    const uint64_t syncs_before = c->sync_serial;
+    p.syncs_before = c->sync_serial;
 
-    texel_alloc::Pool plan = c->tex_alloc;
-    bool wait = false;  // for every frame in flight
-    for (uint32_t i = 0; i < n; ++i) wait = wait || (slots[i] < table && c->h_tex_hot[slots[i]] != 0);
-    const size_t descs_bytes = (size_t)new_table * sizeof(r3n_texture_desc32), rows_bytes = (size_t)new_table * R3N_TEX_LEVELS * 4u;
-    const bool grow_tables = descs_bytes > c->tex_descs.bytes || rows_bytes > c->tex_level_off.bytes;
-    wait = wait || grow_tables;
-    if (wait) plan.release();
+    p.plan = c->tex_alloc;
+    p.wait = false;  // for every frame in flight
+    for (uint32_t i = 0; i < n; ++i) p.wait = p.wait || (slots[i] < p.table && c->h_tex_hot[slots[i]] != 0);
+    p.descs_bytes = (size_t)p.new_table * sizeof(r3n_texture_desc32);
+    p.rows_bytes = (size_t)p.new_table * R3N_TEX_LEVELS * 4u;
+    p.grow_tables = p.descs_bytes > c->tex_descs.bytes || p.rows_bytes > c->tex_level_off.bytes;
+    p.wait = p.wait || p.grow_tables;
+    if (p.wait) p.plan.release();
     for (uint32_t i = 0; i < n; ++i)  // replaced textures give their words back first (a live slot is hot: the wait is certain)
-        if (slots[i] < table && c->h_tex_live[slots[i]]) plan.free(c->h_tex_descs[slots[i]].offset, c->h_tex_words[slots[i]], false);
+        if (slots[i] < p.table && c->h_tex_live[slots[i]]) p.plan.free(c->h_tex_descs[slots[i]].offset, c->h_tex_words[slots[i]], false);
     for (uint32_t i = 0; i < n; ++i) {
         bool merged = false;
-        const uint64_t at = plan.alloc(words[i], &merged);
-        if (at == texel_alloc::NONE) return fail(c, R3N_ERR_CAPACITY, "textures update: texel pool exceeds 2^32 texels");
-        wait = wait || merged;  // the range was freed since the last full wait
+        const uint64_t at = p.plan.alloc(words[i], &merged);
+        if (at == texel_alloc::NONE) return fail(c, R3N_ERR_CAPACITY, what + ": texel pool exceeds 2^32 texels");
+        p.wait = p.wait || merged;  // the range was freed since the last full wait
         internal[i].offset = (uint32_t)at;
     }
-    const size_t pool_bytes = (size_t)std::max<uint64_t>(plan.end(), 1) * 4u + 16u;  // (+16: see r3n_textures_write)
-    const bool grow_pool = pool_bytes > c->tex_texels.bytes;
-    wait = wait || grow_pool;
-
-    TextureWork work;  // the job tables of the stored levels, the generated levels behind them
-    if (!plan_texture_work(descs, internal.data(), n, work)) return fail(c, R3N_ERR_CAPACITY, "textures update: more than 2^31 wave slots of decode work in one call");
-
-    // ---- device side: wait if a frame may read what changes, grow, stage
-    if (wait) {
+    p.pool_bytes = (size_t)std::max<uint64_t>(p.plan.end(), 1) * 4u + 16u;  // (+16: see r3n_textures_write)
+    p.grow_pool = p.pool_bytes > c->tex_texels.bytes;
+    p.wait = p.wait || p.grow_pool;
+    return R3N_OK;
+}
+// device side: wait if a frame may read what changes, grow (word offsets are kept).  *grew: a resident buffer grew.
+static int prepare_texture_placement(r3n_ctx *c, TexturePlacement &p, bool *grew) {
+    *grew = false;
+    if (p.wait) {
         TRY(sync_all(c));
         texture_note_syncs(c);
-        plan.release();
+        p.plan.release();
     }
-    if (grow_tables || grow_pool) {
-        TRY(grow_texture_resident(c, c->tex_descs, descs_bytes, ~(size_t)0));
-        TRY(grow_texture_resident(c, c->tex_level_off, rows_bytes, ~(size_t)0));
-        TRY(grow_texture_resident(c, c->tex_texels, pool_bytes, (size_t)(texel_alloc::LIMIT + 1u) * 4u + 16u));
-        ++c->tex_stats.pool_grows;
+    if (p.grow_tables || p.grow_pool) {
+        TRY(grow_texture_resident(c, c->tex_descs, p.descs_bytes, ~(size_t)0));
+        TRY(grow_texture_resident(c, c->tex_level_off, p.rows_bytes, ~(size_t)0));
+        TRY(grow_texture_resident(c, c->tex_texels, p.pool_bytes, (size_t)(texel_alloc::LIMIT + 1u) * 4u + 16u));
+        *grew = true;
     }
-    TRY(grow_texture_scratch(c, c->tex_stage, (size_t)std::max<uint64_t>(payload_bytes, 4)));
-    TRY(grow_texture_scratch(c, c->tex_jobs, work.job_block.size() * 4u));
-
-    // ---- the host mirror follows
-    c->h_tex_descs.resize(new_table, r3n_texture_desc32{});
-    c->h_tex_words.resize(new_table, 0);
-    c->h_tex_live.resize(new_table, 0);
-    c->h_tex_hot.resize(new_table, 0);
-    c->h_tex_short.resize(new_table, 0);
-    for (uint32_t slot = table; slot < new_table; ++slot) {  // slots the call opens: its own, and any it leaves out (removed entries)
-        if (!std::binary_search(touched.begin(), touched.end(), slot)) touched.push_back(slot);
+    return R3N_OK;
+}
+// What a placement overwrites in the host mirror, for the call that has to take it back (r3n_textures_from_texture on
+// R3N_ERR_HIP): the touched slots below the old table length; slots behind it go with the table's old length.
+struct TextureMirrorUndo {
+    struct Slot {
+        uint32_t slot;
+        r3n_texture_desc32 desc;
+        uint64_t words;
+        uint8_t live, hot, is_short;
+    };
+    std::vector<Slot> slots;
+    texel_alloc::Pool alloc;
+    uint32_t table = 0;
+    uint64_t n_texels = 0;
+};
+// the host mirror follows; p.touched then names every slot whose row has to go up: the call's own, and any it opens and leaves out
+static void commit_texture_placement(r3n_ctx *c, TexturePlacement &p, const uint32_t *slots, const r3n_texture_desc32 *internal, const uint64_t *words,
+                                     uint32_t n, TextureMirrorUndo *undo) {
+    if (undo) {
+        undo->alloc = c->tex_alloc;
+        undo->table = p.table;
+        undo->n_texels = c->n_texels;
+        for (uint32_t i = 0; i < n; ++i)
+            if (slots[i] < p.table)
+                undo->slots.push_back(TextureMirrorUndo::Slot{slots[i], c->h_tex_descs[slots[i]], c->h_tex_words[slots[i]], c->h_tex_live[slots[i]],
+                                                              c->h_tex_hot[slots[i]], c->h_tex_short[slots[i]]});
+    }
+    c->h_tex_descs.resize(p.new_table, r3n_texture_desc32{});
+    c->h_tex_words.resize(p.new_table, 0);
+    c->h_tex_live.resize(p.new_table, 0);
+    c->h_tex_hot.resize(p.new_table, 0);
+    c->h_tex_short.resize(p.new_table, 0);
+    for (uint32_t slot = p.table; slot < p.new_table; ++slot) {  // slots the call opens: its own, and any it leaves out (removed entries)
+        if (!std::binary_search(p.touched.begin(), p.touched.end(), slot)) p.touched.push_back(slot);
         c->h_tex_descs[slot] = device_desc(c, slot);
         c->h_tex_descs[slot].width = c->h_tex_descs[slot].height = 0;
     }
-    std::sort(touched.begin(), touched.end());
+    std::sort(p.touched.begin(), p.touched.end());
     for (uint32_t i = 0; i < n; ++i) {
         c->h_tex_descs[slots[i]] = internal[i];
         c->h_tex_words[slots[i]] = words[i];
         c->h_tex_live[slots[i]] = c->h_tex_hot[slots[i]] = 1;
         c->h_tex_short[slots[i]] = texture_is_short(internal[i]);
     }
-    c->tex_alloc = plan;
-    c->n_textures = new_table;
-    c->n_texels = plan.end();
+    c->tex_alloc = p.plan;
+    c->n_textures = p.new_table;
+    c->n_texels = p.plan.end();
     c->classes_dirty = true; c->cutout_short_dirty = true;
     ++c->main_epoch;  // the shadow lanes' cutout rasterisers sample the array
+}
+static void undo_texture_placement(r3n_ctx *c, const TextureMirrorUndo &u) {
+    c->h_tex_descs.resize(u.table);
+    c->h_tex_words.resize(u.table);
+    c->h_tex_live.resize(u.table);
+    c->h_tex_hot.resize(u.table);
+    c->h_tex_short.resize(u.table);
+    for (const TextureMirrorUndo::Slot &s : u.slots) {
+        c->h_tex_descs[s.slot] = s.desc;
+        c->h_tex_words[s.slot] = s.words;
+        c->h_tex_live[s.slot] = s.live;
+        c->h_tex_hot[s.slot] = s.hot;
+        c->h_tex_short[s.slot] = s.is_short;
+    }
+    c->tex_alloc = u.alloc;
+    c->n_textures = u.table;
+    c->n_texels = u.n_texels;
+    c->classes_dirty = true; c->cutout_short_dirty = true;
+}
+
+int r3n_textures_update(r3n_ctx *c, const uint32_t *slots, const r3n_texture_desc32 *descs, uint32_t n, const void *payload,
+                        uint64_t payload_bytes) {
+    if (!c || (n && (!slots || !descs || !payload))) return fail(c, R3N_ERR_INVALID_ARG, "textures update: null");
+    if (!n) return R3N_OK;
+    // ---- validation and planning: nothing of the context changes before both are through
+    std::vector<r3n_texture_desc32> internal(n);
+    std::vector<uint64_t> words(n);
+    for (uint32_t i = 0; i < n; ++i) {
+        TRY(check_encoded_desc(c, "textures update", descs[i], payload_bytes, internal[i], words[i]));
+        if ((uint64_t)slots[i] >= (uint64_t)c->n_textures + n)
+            return fail(c, R3N_ERR_INVALID_ARG, "textures update: slot past table length + n (the lowest free index never is)");
+    }
+    TexturePlacement place;
+    TRY(place_textures(c, "textures update", slots, internal.data(), words.data(), n, place));
+
+    TextureWork work;  // the job tables of the stored levels, the generated levels behind them
+    if (!plan_texture_work(descs, internal.data(), n, work)) return fail(c, R3N_ERR_CAPACITY, "textures update: more than 2^31 wave slots of decode work in one call");
+
+    // ---- device side: wait if a frame may read what changes, grow, stage
+    bool grew = false;
+    TRY(prepare_texture_placement(c, place, &grew));
+    if (grew) ++c->tex_stats.pool_grows;
+    TRY(grow_texture_scratch(c, c->tex_stage, (size_t)std::max<uint64_t>(payload_bytes, 4)));
+    TRY(grow_texture_scratch(c, c->tex_jobs, work.job_block.size() * 4u));
+
+    // ---- the host mirror follows
+    commit_texture_placement(c, place, slots, internal.data(), words.data(), n, nullptr);
 
     // ---- the touched table rows, then copy and decode
     // (the main stream is idle or busy with frames that cannot name what is written here: nothing on it has to come first -- a
     // growth, a whole-array write and an earlier update all ended in a wait, a removal's table rows belong to hot slots)
-    TRY(upload_texture_slots(c, touched, true));
+    TRY(upload_texture_slots(c, place.touched, true));
     uint64_t launches = 0;
     const hipError_t e = enqueue_texture_work(c, work, payload, payload_bytes, c->tex_stream, c->tex_stage.p, c->tex_jobs.as<uint32_t>(), launches);
     const hipError_t e2 = hipStreamSynchronize(c->tex_stream);  // its own work alone; the caller owns the payload only for the duration of the call
@@ -1604,7 +1680,7 @@ int r3n_textures_update(r3n_ctx *c, const uint32_t *slots, const r3n_texture_des
     ++c->tex_stats.update_calls;
     c->tex_stats.kernel_launches += launches;
     c->tex_stats.bytes_staged += payload_bytes;
-    c->tex_stats.full_syncs += c->sync_serial - syncs_before;
+    c->tex_stats.full_syncs += c->sync_serial - place.syncs_before;
     return R3N_OK;
 }
 
@@ -1716,6 +1792,84 @@ int r3n_textures_compact(r3n_ctx *c, const r3n_texture_compact_opts *opts, r3n_t
     res.full_syncs = c->sync_serial - syncs_before;
     res.pool_words_after = c->tex_alloc.end();
     res.free_ranges_after = c->tex_alloc.free_ranges();
+    if (out) *out = res;
+    return R3N_OK;
+}
+
+extern "C" int r3n_internal_copy_tails(const uint32_t *block, uint64_t o_first, uint64_t o_inst, uint32_t waves, uint32_t *pool, hipStream_t stream);
+
+// Renderer::add_texture_2d_from_texture for n textures at once (texel_tail.h derives and lays out, texture_tail.hip copies): placed
+// exactly as r3n_textures_update places a texture, filled by ONE launch from the words the pool already holds.
+int r3n_textures_from_texture(r3n_ctx *c, const r3n_texture_tail16 *items, uint32_t n, r3n_texture_tail_result *out) {
+    if (!c || (n && !items)) return fail(c, R3N_ERR_INVALID_ARG, "textures from texture: null");
+    r3n_texture_tail_result res{};
+    res.pool_words_after = c->tex_alloc.end();
+    if (!n) {
+        if (out) *out = res;
+        return R3N_OK;
+    }
+    // ---- validation and planning against the table as it is: nothing of the context changes before both are through
+    const uint32_t table = c->n_textures;
+    std::vector<uint32_t> slots(n);
+    std::vector<r3n_texture_desc32> internal(n);
+    std::vector<uint64_t> words(n);
+    std::vector<texel_tail::Item> copies(n);
+    std::vector<texel_tail::Resolved> resolved;
+    const char *refused = texel_tail::resolve(table, [&](uint32_t slot) {
+        const r3n_texture_desc32 &d = c->h_tex_descs[slot];
+        return texel_tail::Slot{c->h_tex_live[slot] != 0, c->h_tex_words[slot], d.offset, texel_tail::Chain{d.width, d.height, d.mips, words_per_texel(d)}};
+    }, items, n, resolved);
+    if (refused) return fail(c, R3N_ERR_INVALID_ARG, std::string("textures from texture: ") + refused);
+    for (uint32_t i = 0; i < n; ++i) {
+        const texel_tail::Tail &t = resolved[i].tail;
+        slots[i] = resolved[i].dst_slot;
+        internal[i] = r3n_texture_desc32{};
+        internal[i].width = t.chain.width;
+        internal[i].height = t.chain.height;
+        internal[i].mips = t.chain.mips;
+        internal[i].format = c->h_tex_descs[items[i].src_slot].format;
+        words[i] = t.words;
+        copies[i].src = resolved[i].src;
+        copies[i].words = t.words;
+    }
+    TexturePlacement place;
+    TRY(place_textures(c, "textures from texture", slots.data(), internal.data(), words.data(), n, place));
+    for (uint32_t i = 0; i < n; ++i) copies[i].dst = internal[i].offset;
+    std::vector<uint32_t> block;
+    vertex_block::layout layout{};
+    if (!texel_tail::lay_out(copies, block, layout)) return fail(c, R3N_ERR_CAPACITY, "textures from texture: more than 2^31 wave slots of copy work in one call");
+    if (!texel_tail::disjoint(copies)) return fail(c, R3N_ERR_STATE, "textures from texture: a destination overlaps a source or another destination");
+    // whole units stay inside the block the call is about to have: reads end at most 3 words behind a tail, writes behind a destination
+    for (const texel_tail::Item &it : copies)
+        if ((std::max(it.src, it.dst) + texel_tail::reach(it)) * 4u > std::max(place.pool_bytes, c->tex_texels.bytes))
+            return fail(c, R3N_ERR_STATE, "textures from texture: a source texture ends outside the texel pool");
+
+    // ---- device side: wait if a frame may read what changes, grow; the host mirror follows and comes back if anything fails
+    bool grew = false;
+    TRY(prepare_texture_placement(c, place, &grew));  // (r3n_texture_stats counts no growth of this call: its counters stay the update path's)
+    TRY(grow_texture_scratch(c, c->tex_jobs, block.size() * 4u));
+    TextureMirrorUndo undo;
+    commit_texture_placement(c, place, slots.data(), internal.data(), words.data(), n, &undo);
+
+    // ---- the touched table rows, the table, ONE launch.  The sources' words are complete: every path that writes pool words ended
+    // in a wait for them (update, compaction, a whole-array write, a growth, an earlier call of this kind).
+    const int up = upload_texture_slots(c, place.touched, true);
+    hipError_t e = up == R3N_OK ? hipMemcpyAsync(c->tex_jobs.p, block.data(), block.size() * 4u, hipMemcpyHostToDevice, c->tex_stream) : hipSuccess;
+    const uint64_t waves = texel_tail::total_waves(copies);
+    if (up == R3N_OK && e == hipSuccess)
+        e = (hipError_t)r3n_internal_copy_tails(c->tex_jobs.as<uint32_t>(), layout.o_first, layout.o_inst, (uint32_t)waves, c->tex_texels.as<uint32_t>(), c->tex_stream);
+    const hipError_t e2 = hipStreamSynchronize(c->tex_stream);  // its own work alone; later calls rely on it: the new words are complete
+    if (up != R3N_OK || e != hipSuccess || e2 != hipSuccess) {
+        undo_texture_placement(c, undo);  // the mirror as it was (r3n.h: the device's rows of the destination slots are not)
+        if (e != hipSuccess) return fail(c, R3N_ERR_HIP, std::string("textures from texture: ") + hipGetErrorString(e));
+        if (e2 != hipSuccess) return fail(c, R3N_ERR_HIP, std::string("textures from texture: ") + hipGetErrorString(e2));
+        return up;  // (upload_texture_slots has set the message)
+    }
+    res.textures = n;
+    for (uint32_t i = 0; i < n; ++i) res.words_copied += words[i];
+    res.kernel_launches = 1;
+    res.full_syncs = c->sync_serial - place.syncs_before;
+    res.pool_words_after = c->tex_alloc.end();
     if (out) *out = res;
     return R3N_OK;
 }

@@ -176,30 +176,56 @@ def load_image(g, r, cache, image_index, srgb):
     gets a generated chain only when its format can be rendered to, i.e. is not block-compressed), else the `image`
     crate's decoders + util::convert_dynamic_image (:1157-1175): 8-bit luma (with or without alpha) becomes R8Unorm,
     RGB / RGBA become Rgba8Unorm[Srgb], MipmapCount::Maximum + MipmapSource::Generated.
-    Returns (texture handle, components)."""
+    `cache`: (image, srgb) -> (texture handle, components, levels).  Returns (texture handle, components)."""
     key = (image_index, bool(srgb))
     if key not in cache:
-        from . import containers
-        data = _image_bytes(g, g.json["images"][image_index])
-        parsed = containers.parse_ktx2(data, bool(srgb)) or containers.parse_dds(data, bool(srgb))
-        if parsed is not None:
-            fmt = parsed["format"]
-            generate = len(parsed["levels"]) == 1 and containers.generate_mips_allowed(fmt)
-            handle = r.add_texture_2d_encoded(fmt, parsed["width"], parsed["height"], parsed["levels"], generate_mips=generate)
-            comps = containers.COMPONENTS.get(fmt, 4)  # TextureFormat::describe().components
-            cache[key] = (handle, comps)
-        else:
-            import io
-            from PIL import Image
-            im = Image.open(io.BytesIO(data))
-            if im.mode in ("L", "LA"):
-                lum = np.ascontiguousarray(np.array(im.convert("L"), dtype=np.uint8))
-                cache[key] = (r.add_texture_2d_encoded(containers.R8, lum.shape[1], lum.shape[0], [lum.tobytes()],
-                                                       generate_mips=True), 1)
-            else:
-                rgba = np.array(im.convert("RGBA"), dtype=np.uint8)
-                cache[key] = (r.add_texture_2d(rgba, srgb=bool(srgb), mip_count="maximum", mip_source="generated"), 4)
-    return cache[key]
+        cache[key] = _load_image(g, r, image_index, srgb)
+    return cache[key][:2]
+
+
+def skip_texture_mips(r, cache, n):
+    """Every texture of `cache` (load_image's) with more than one level is replaced there by its levels from min(n, mips - 1) on
+    (Renderer::add_texture_2d_from_texture, a copy on the GPU) and removed: resolution given back under memory pressure.  Called
+    when every image of a file is loaded and before its materials are made, so that the uploads go in one call, the copies in a
+    second, and the materials name the copies."""
+    if not hasattr(r, "add_texture_2d_from_texture"):
+        raise ValueError("texture_skip_mips: this renderer cannot copy a texture's levels")
+    originals = []
+    for key, (handle, comps, mips) in list(cache.items()):
+        if mips > 1:
+            start = min(int(n), mips - 1)
+            originals.append(handle)
+            cache[key] = (r.add_texture_2d_from_texture(handle, start), comps, mips - start)
+    for handle in originals:  # (the first removal sends what is queued; the removals go with the next flush)
+        r.remove_texture(handle)
+
+
+def _load_image(g, r, image_index, srgb):
+    """(texture handle, components, levels)"""
+    from . import containers
+    data = _image_bytes(g, g.json["images"][image_index])
+    parsed = containers.parse_ktx2(data, bool(srgb)) or containers.parse_dds(data, bool(srgb))
+    if parsed is not None:
+        fmt = parsed["format"]
+        generate = len(parsed["levels"]) == 1 and containers.generate_mips_allowed(fmt)
+        handle = r.add_texture_2d_encoded(fmt, parsed["width"], parsed["height"], parsed["levels"], generate_mips=generate)
+        comps = containers.COMPONENTS.get(fmt, 4)  # TextureFormat::describe().components
+        return handle, comps, _full_chain(parsed["width"], parsed["height"]) if generate else len(parsed["levels"])
+    import io
+    from PIL import Image
+    im = Image.open(io.BytesIO(data))
+    if im.mode in ("L", "LA"):
+        lum = np.ascontiguousarray(np.array(im.convert("L"), dtype=np.uint8))
+        return (r.add_texture_2d_encoded(containers.R8, lum.shape[1], lum.shape[0], [lum.tobytes()], generate_mips=True), 1,
+                _full_chain(lum.shape[1], lum.shape[0]))
+    rgba = np.array(im.convert("RGBA"), dtype=np.uint8)
+    return (r.add_texture_2d(rgba, srgb=bool(srgb), mip_count="maximum", mip_source="generated"), 4,
+            _full_chain(rgba.shape[1], rgba.shape[0]))
+
+
+def _full_chain(width, height):
+    """MipmapCount::Maximum"""
+    return int(max(width, height)).bit_length()
 
 
 def material_from_gltf(g, index, mk, r=None, image_cache=None, normal_y_down=False):
@@ -271,7 +297,7 @@ def material_from_gltf(g, index, mk, r=None, image_cache=None, normal_y_down=Fal
 
 def instance_scene(g, r, hm, mk, scale=1.0, enable_directional=True, directional_light_shadow_distance=100.0,
                    directional_light_resolution=2048, normal_y_down=False, morph_normals="base",
-                   build_tangents=False, morph_tangents="base"):
+                   build_tangents=False, morph_tangents="base", texture_skip_mips=0):
     """load_gltf + instance_loaded_scene (rend3-gltf/src/lib.rs:335-379, 493-562): node transforms in topological order
     under parent_transform = scale(s, s, -s for a left-handed renderer); one object per mesh primitive; a skeleton per
     primitive of a skinned node (joint matrices start as identity, add_mesh_by_index :411-457); winding flipped for
@@ -283,12 +309,19 @@ def instance_scene(g, r, hm, mk, scale=1.0, enable_directional=True, directional
     (the keyword is passed for those primitives only).  build_tangents=True: a primitive with TEXCOORD_0 and without TANGENT is
     added with add_mesh(build_tangents=True), which is what rend3-gltf's MeshBuilder does for every primitive (the default, False,
     keeps such a primitive without tangents until the oracle follows); morph_tangents="recompute" is passed on, with it, for those of
-    them whose targets have POSITION and no TANGENT.  Returns dict(objects=[handles],
+    them whose targets have POSITION and no TANGENT.  texture_skip_mips=N > 0 (a renderer with texture_upload="stream"): every 2D
+    texture of the file with more than one level is replaced by its levels from min(N, mips - 1) on, copied on the GPU
+    (add_texture_2d_from_texture), and the original is removed -- resolution dropped under memory pressure; the pool keeps the
+    originals' holes until it is compacted.  Returns dict(objects=[handles],
     skeletons=[handles], inverse_bind_matrices=[per skin], node_transforms)."""
     if morph_normals not in ("base", "recompute"):
         raise ValueError("morph_normals: 'base' or 'recompute'")
     if morph_tangents not in ("base", "recompute"):
         raise ValueError("morph_tangents: 'base' or 'recompute'")
+    if int(texture_skip_mips) < 0:
+        raise ValueError("texture_skip_mips: a level count >= 0")
+    if int(texture_skip_mips) > 0 and getattr(r, "texture_upload", "whole") != "stream":
+        raise ValueError("texture_skip_mips needs a renderer with texture_upload='stream': the whole-array path keeps no resident pool to copy from")
     nodes = g.json.get("nodes", [])
     lh = r.handedness == 0
     parent_of = {}
@@ -305,6 +338,15 @@ def instance_scene(g, r, hm, mk, scale=1.0, enable_directional=True, directional
     meshes = {}
     materials = {}
     image_cache = {}
+    if int(texture_skip_mips) > 0:
+        # the images first, in the order the loop below would load them, then their tails; the loop finds the tails in the cache
+        for ni in order:
+            for prim in (g.json["meshes"][nodes[ni]["mesh"]]["primitives"] if "mesh" in nodes[ni] else []):
+                if prim.get("material") is not None and prim["material"] not in materials:
+                    materials[prim["material"]] = None
+                    material_from_gltf(g, prim["material"], mk, r, image_cache, normal_y_down=normal_y_down)
+        materials.clear()
+        skip_texture_mips(r, image_cache, int(texture_skip_mips))
     xf = [None] * len(nodes)
     out = dict(objects=[], skeletons=[], lights=[], inverse_bind_matrices=[], node_transforms=xf, topological_order=order,
                nodes=[dict(parent=parent_of.get(i), local_transform=None, objects=[], skin=None, skeletons=[], morphs=[]) for i in range(len(nodes))],

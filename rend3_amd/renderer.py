@@ -209,6 +209,8 @@ class Renderer:
         self._tex_live = []       # "stream": per slot, True while the slot holds a texture (queued ones included)
         self._tex_queue = []      # "stream": (slot, desc row without offset, bytes) not yet sent
         self._tex_removals = []   # "stream": slots whose removal is not yet sent
+        self._tex_tails = []      # "stream": (slot, source slot, start_mip, mip_count) of add_texture_2d_from_texture, not yet sent
+        self._tex_mips = []       # "stream": per slot, the levels of the texture it holds
         # "stream": None = the pool is never compacted by itself; a fraction f in (0, 1] = r3n_textures_compact at a texture flush in
         # front of a frame, when more than f of the pool below its high-water mark is holes
         if texture_compact is not None and not (0.0 < float(texture_compact) <= 1.0):
@@ -660,10 +662,11 @@ class Renderer:
         if self._texture_upload == "stream":
             # the lowest free slot (TextureManager's handle allocator); sent with everything else queued when the next frame is
             # evaluated (TextureManager::evaluate)
-            slot = self._tex_live.index(False) if False in self._tex_live else len(self._tex_live)
-            if slot == len(self._tex_live):
-                self._tex_live.append(True)
-            self._tex_live[slot] = True
+            if self._tex_tails:
+                # uploads go in front of the queued add_texture_2d_from_texture copies, in one call that may open at most as many
+                # slots as it has entries: an upload behind a queued copy's slot would be past that bound
+                self._flush_textures()
+            slot = self._take_texture_slot(mips)
             self._tex_queue.append((slot, (w, h, mips, fmt, stored), np.array(data_u8, dtype=np.uint8)))
             return slot
         start = (self.tex_used + 3) & ~3  # level 0 of every texture starts on a 4-byte boundary
@@ -679,6 +682,35 @@ class Renderer:
         self._tex_dirty = True  # the array is re-sent once, when the next frame is evaluated (TextureManager::evaluate)
         return len(self.tex_descs) - 1
 
+    def _take_texture_slot(self, mips):
+        slot = self._tex_live.index(False) if False in self._tex_live else len(self._tex_live)
+        if slot == len(self._tex_live):
+            self._tex_live.append(True)
+            self._tex_mips.append(0)
+        self._tex_live[slot] = True
+        self._tex_mips[slot] = int(mips)
+        return slot
+
+    def add_texture_2d_from_texture(self, src, start_mip, mip_count=None):
+        """Renderer::add_texture_2d_from_texture with TextureFromTexture{src, start_mip, mip_count}: a new texture of the size of
+        level start_mip of `src` whose levels are copies of levels start_mip .. of it, mip_count of them (None = all that remain) --
+        copied on the GPU inside the texel pool (r3n_textures_from_texture), nothing is sent from the host.  texture_upload="stream"
+        only.  `src` may be a texture that is itself still queued.  Takes the lowest free slot; returns the new handle."""
+        if self._texture_upload != "stream":
+            raise ValueError("add_texture_2d_from_texture needs Renderer(texture_upload='stream'): the whole-array path keeps no resident pool to copy from")
+        src, start_mip = int(src), int(start_mip)
+        if not (0 <= src < len(self._tex_live)) or not self._tex_live[src]:
+            raise ValueError(f"add_texture_2d_from_texture: handle {src} holds no texture")
+        mips = self._tex_mips[src]
+        count = mips - start_mip if mip_count is None else int(mip_count)
+        if not (0 <= start_mip < mips) or not (1 <= count <= mips - start_mip):
+            raise ValueError(f"add_texture_2d_from_texture: levels [{start_mip}, {start_mip + count}) of a texture with {mips}")
+        if any(t[0] == src for t in self._tex_tails):
+            self._flush_textures()  # sources are resolved against the table in front of the call: a queued tail goes first
+        slot = self._take_texture_slot(count)
+        self._tex_tails.append((slot, src, start_mip, count))
+        return slot
+
     def remove_texture(self, handle):
         """TextureManager::remove (the reference drops a texture with its handle): the slot's texels become reusable, the handle
         may be handed out again.  texture_upload="stream" only.  Materials that still name the handle read an unspecified texel."""
@@ -687,8 +719,10 @@ class Renderer:
         handle = int(handle)
         if not (0 <= handle < len(self._tex_live)) or not self._tex_live[handle]:
             raise ValueError(f"remove_texture: handle {handle} holds no texture")
-        if any(slot == handle for slot, _, _ in self._tex_queue):
-            self._flush_textures()  # it was never sent: send it, then remove it (keeps the table the library's)
+        if any(slot == handle for slot, _, _ in self._tex_queue) or any(handle in t[:2] for t in self._tex_tails):
+            # it was never sent, or a queued add_texture_2d_from_texture makes or reads it: send, then remove (keeps the table the
+            # library's; removals go in front of everything else queued)
+            self._flush_textures()
         self._tex_live[handle] = False
         self._tex_removals.append(handle)
 
@@ -706,7 +740,7 @@ class Renderer:
         return {name: int(getattr(out, name)) for name, _ in _ffi.TextureCompactResult._fields_}
 
     def _flush_textures(self, before_frame=False):
-        changed = bool(self._tex_removals or self._tex_queue)
+        changed = bool(self._tex_removals or self._tex_queue or self._tex_tails)
         self._send_textures()
         if before_frame and changed and self._texture_compact is not None and self._texture_upload == "stream":
             st = self.texture_stats()
@@ -733,6 +767,10 @@ class Renderer:
             self._check(self.lib.r3n_textures_update(self.ctx, _ffi.ptr(slots), _ffi.ptr(descs), len(slots), _ffi.ptr(payload), at),
                         "r3n_textures_update")
             self._tex_queue = []  # nothing sent is kept on the host
+        if self._tex_tails:  # behind the updates: a tail may name a texture queued in the same flush
+            items = (_ffi.TextureTail16 * len(self._tex_tails))(*[_ffi.TextureTail16(*t) for t in self._tex_tails])
+            self._check(self.lib.r3n_textures_from_texture(self.ctx, items, len(self._tex_tails), None), "r3n_textures_from_texture")
+            self._tex_tails = []
         if self._tex_dirty:
             self._check(self.lib.r3n_textures_write_encoded(self.ctx, _ffi.ptr(self.tex_descs), len(self.tex_descs),
                                                             _ffi.ptr(self.tex_pool), self.tex_used), "r3n_textures_write_encoded")

@@ -86,6 +86,10 @@ def add_arguments(ap):
     ap.add_argument("--texture-compact", type=float, default=None, metavar="F",
                     help="with --texture-upload stream: compact the texel pool on the GPU (r3n_textures_compact) in front of a frame when "
                          "more than the fraction F in (0, 1] of it is holes; default: never")
+    ap.add_argument("--texture-skip-mips", type=int, default=0, metavar="N",
+                    help="with --texture-upload stream: replace every 2D texture of the file that has more than one level by its "
+                         "levels from min(N, mips - 1) on, copied on the GPU (r3n_textures_from_texture), and remove the original; "
+                         "default 0: keep every level")
     ap.add_argument("--texture-upload", choices=("whole", "stream"), default="whole",
                     help="how 2D textures reach the device: whole = the bindless array is re-sent when it changed, stream = single "
                          "entries are added and removed in place (r3n_textures_update), as the reference's TextureManager does")
@@ -116,7 +120,8 @@ def settings_from(args):
                 camera=args.camera or DEFAULT_CAMERA, skybox=getattr(args, "skybox", None),
                 blend_sort=getattr(args, "blend_sort", "host"), morph_normals=getattr(args, "morph_normals", "base"),
                 build_tangents=getattr(args, "build_tangents", False), morph_tangents=getattr(args, "morph_tangents", "base"),
-                texture_upload=getattr(args, "texture_upload", "whole"), texture_compact=getattr(args, "texture_compact", None))
+                texture_upload=getattr(args, "texture_upload", "whole"), texture_compact=getattr(args, "texture_compact", None),
+                texture_skip_mips=getattr(args, "texture_skip_mips", 0))
 
 
 def default_settings(**over):
@@ -174,6 +179,11 @@ def build(r, hm, mk, settings):
         if settings.get("texture_upload", "whole") != "stream":
             raise ValueError("--texture-compact needs --texture-upload stream: the whole-array path lays its pool out densely")
         r.texture_compact = settings["texture_compact"]
+    if settings.get("texture_skip_mips", 0):
+        if settings["texture_skip_mips"] < 0:
+            raise ValueError("--texture-skip-mips: a level count >= 0")
+        if settings.get("texture_upload", "whole") != "stream":
+            raise ValueError("--texture-skip-mips needs --texture-upload stream: the whole-array path keeps no resident pool to copy from")
     light = None
     if settings["directional_light"] is not None:  # setup (mod.rs:463-472)
         light = r.add_directional_light(color=(1.0, 1.0, 1.0), intensity=settings["directional_light_intensity"],
@@ -185,6 +195,8 @@ def build(r, hm, mk, settings):
         recompute["build_tangents"] = True
     if settings.get("morph_tangents", "base") == "recompute":
         recompute["morph_tangents"] = "recompute"
+    if settings.get("texture_skip_mips", 0):
+        recompute["texture_skip_mips"] = settings["texture_skip_mips"]
     inst = gltf.instance_scene(g, r, hm, mk, scale=settings["scale"], enable_directional=settings["enable_directional"],
                                directional_light_shadow_distance=settings["shadow_distance"],
                                directional_light_resolution=settings["shadow_resolution"], normal_y_down=settings["normal_y_down"],
