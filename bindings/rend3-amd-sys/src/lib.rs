@@ -59,6 +59,15 @@ pub const R3N_TEXTURE_FORMAT_COUNT: u32 = 34;
 pub const R3N_MAX_MORPH_TARGETS: u32 = 256;
 pub const R3N_SHADE_EXACT: u32 = 0;
 pub const R3N_SHADE_FAST: u32 = 1;
+pub const R3N_PROBE_GRAD: i32 = 0;
+pub const R3N_PROBE_GRAD_RGB: i32 = 1;
+pub const R3N_PROBE_SHORT: i32 = 2;
+pub const R3N_PROBE_SHORT_RGB: i32 = 3;
+pub const R3N_PROBE_SHARE: i32 = 4;
+pub const R3N_PROBE_ALPHA: i32 = 5;
+pub const R3N_PROBE_ALPHA_SHORT: i32 = 6;
+pub const R3N_PROBE_BATCHED: i32 = 7;
+pub const R3N_PROBE_FORM_COUNT: i32 = 8;
 pub const R3N_OUTPUT_RGBA8_UNORM_SRGB: u32 = 0;
 pub const R3N_OUTPUT_BGRA8_UNORM_SRGB: u32 = 1;
 pub const R3N_OUTPUT_RGBA8_UNORM: u32 = 2;
@@ -362,6 +371,24 @@ pub struct r3n_texture_counters {
 
 #[repr(C)]
 #[derive(Clone, Copy)]
+pub struct r3n_sample_query40 {
+    pub id: [u32; 3],
+    pub nearest: u32,
+    pub u: f32,
+    pub v: f32,
+    pub ddx: [f32; 2],
+    pub ddy: [f32; 2],
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct r3n_sample_result52 {
+    pub rgba: [[f32; 4]; 3],
+    pub flags: u32,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
 pub struct r3n_shadow_view272 {
     pub header: r3n_camera_header240,
     pub x: u32,
@@ -456,6 +483,7 @@ extern "C" {
     pub fn r3n_textures_compact(ctx: *mut r3n_ctx, opts: *const r3n_texture_compact_opts, out: *mut r3n_texture_compact_result) -> c_int;
     pub fn r3n_textures_from_texture(ctx: *mut r3n_ctx, items: *const r3n_texture_tail16, n: u32, out: *mut r3n_texture_tail_result) -> c_int;
     pub fn r3n_texture_stats(ctx: *mut r3n_ctx, out: *mut r3n_texture_counters, reset: c_int) -> c_int;
+    pub fn r3n_sample_probe(ctx: *mut r3n_ctx, form: u32, queries: *const r3n_sample_query40, n: u32, out: *mut r3n_sample_result52) -> c_int;
     pub fn r3n_texture_cubes_write(ctx: *mut r3n_ctx, descs: *const r3n_texture_desc32, n_cubes: u32, texels: *const u32, n_texels: u64) -> c_int;
     pub fn r3n_skybox_set(ctx: *mut r3n_ctx, cube_id: u32) -> c_int;
     pub fn r3n_blend_order_write(ctx: *mut r3n_ctx, objects_back_to_front: *const u32, n: u32) -> c_int;

@@ -412,6 +412,46 @@ typedef struct r3n_texture_counters {
     uint64_t update_calls, kernel_launches, bytes_staged, full_syncs, pool_grows, pool_words, live_words, free_ranges;
 } r3n_texture_counters;
 int r3n_texture_stats(r3n_ctx *ctx, r3n_texture_counters *out, int reset);
+/*      Test entry: the texture sampler of the frame's kernels (csrc/texture.h) on a list of queries, against the context's own
+ *      texture state -- the pool, descriptors, level-offset table and decode tables the resolve and the rasterisers are handed, as
+ *      they are at the call.  Query i is textureSampleGrad(textures[id[k] - 1], nearest ? nearest : linear, (u, v), ddx, ddy);
+ *      result i holds up to three RGBA samples.  `form` names the instantiation the product launches (exact arithmetic only):
+ *        R3N_PROBE_GRAD / _GRAD_RGB    the general entry with / without the alpha channel (takes its own short path when it applies)
+ *        R3N_PROBE_SHORT / _SHORT_RGB  the short-path-only instantiations of the resolve's material classes
+ *        R3N_PROBE_SHARE               short-path-only, id[0], id[1], id[2] in slot order through ONE level-of-detail / footprint cache
+ *                                      that starts empty (the fragment stage); slots 0 and 1 with alpha, slot 2 without
+ *        R3N_PROBE_ALPHA / _ALPHA_SHORT  the rasterisers' alpha-only sampler (cutout test): the value lands in rgba[0][3]
+ *        R3N_PROBE_BATCHED             the PBR class's three maps in one pass; flags = 1 when it took the wave, 0 when it declined
+ *                                      (rgba is then zero)
+ *      Single-map forms sample id[0] into rgba[0].  A channel a form does not produce is zero: alpha of the _RGB forms and of
+ *      slot 2 of SHARE / BATCHED, rgba[1..2] of the single-map forms, everything but rgba[0][3] of the ALPHA forms.
+ *      ONE THREAD PER QUERY, QUERIES 64 i .. 64 i + 63 ARE ONE WAVEFRONT: the batched form declines or accepts per wavefront and
+ *      takes its wave-uniform branches (second level, wrapping rows) by what any of those 64 queries needs; a last partial wave
+ *      runs with its missing lanes idle.
+ *      The short-path-only and batched forms have preconditions the kernels do not check (the resolve's material classes establish
+ *      them): every id is 0 or a texture on the sampler's short path (power-of-two extents, RGBA8 pool texels, pool <= 2^30 words)
+ *      and nearest == 0.  The call checks every query on the host and returns R3N_ERR_INVALID_ARG without a launch when one
+ *      violates them, or when `form` is unknown.  The general forms take any id, one past the table or of a removed slot
+ *      included, like the product.  Waits for every frame in flight, allocates and frees its scratch, waits for its own launch. */
+#define R3N_PROBE_GRAD 0
+#define R3N_PROBE_GRAD_RGB 1
+#define R3N_PROBE_SHORT 2
+#define R3N_PROBE_SHORT_RGB 3
+#define R3N_PROBE_SHARE 4
+#define R3N_PROBE_ALPHA 5
+#define R3N_PROBE_ALPHA_SHORT 6
+#define R3N_PROBE_BATCHED 7
+#define R3N_PROBE_FORM_COUNT 8
+typedef struct r3n_sample_query40 {
+    uint32_t id[3];
+    uint32_t nearest;
+    float u, v, ddx[2], ddy[2];
+} r3n_sample_query40;
+typedef struct r3n_sample_result52 {
+    float rgba[3][4];
+    uint32_t flags;
+} r3n_sample_result52;
+int r3n_sample_probe(r3n_ctx *ctx, uint32_t form, const r3n_sample_query40 *queries, uint32_t n, r3n_sample_result52 *out);
 /*      The cube textures (the reference's d2c_texture_manager, rend3/src/managers/texture.rs; Renderer::add_texture_cube): replaces
  *      the context's whole cube array, which is separate from the bindless 2D array.  A cube is six square faces of width x width
  *      RGBA8 texels, contiguous from desc.offset (in texels) in `texels`, in layer order +X, -X, +Y, -Y, +Z, -Z (what scene_viewer

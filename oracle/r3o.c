@@ -731,6 +731,27 @@ static void tex_sample_grad(const r3o_textures *tt, uint32_t id, int nearest, fl
         for (int c = 0; c < 4; ++c) o[c] = o[c] * (1.0f - frac) + hi[c] * frac;
     }
 }
+/* The sampler on a list of queries (the layout of the product's r3n_sample_probe): slot k of result i is
+ * tex_sample_grad(id[k], nearest, (u, v), ddx, ddy) -- every slot on its own, as the contract has it; flags is unused (0). */
+typedef struct {
+    uint32_t id[3];
+    uint32_t nearest;
+    float u, v, ddx[2], ddy[2];
+} r3o_sample_query;
+typedef struct {
+    float rgba[3][4];
+    uint32_t flags;
+} r3o_sample_result;
+void r3o_sample_queries(const r3o_texture_desc *descs, uint32_t n, const uint32_t *texels, const r3o_sample_query *queries,
+                        uint64_t n_queries, r3o_sample_result *out) {
+    init_srgb8();
+    r3o_textures tt = {descs, n, texels};
+    for (uint64_t i = 0; i < n_queries; ++i) {
+        const r3o_sample_query *q = &queries[i];
+        for (int k = 0; k < 3; ++k) tex_sample_grad(&tt, q->id[k], q->nearest != 0u, q->u, q->v, q->ddx, q->ddy, out[i].rgba[k]);
+        out[i].flags = 0u;
+    }
+}
 /*
  * MipmapSource::Generated (rend3/src/util/mipmap.rs:139-236 + rend3/shaders/mipmap.wgsl): every level is a blit of the
  * previous one through a Linear / ClampToEdge sampler at the destination texel centres, rendered into the

@@ -47,6 +47,7 @@ SIGNATURES = {
     "r3n_textures_compact": (cint, [vp, vp, vp]),
     "r3n_textures_from_texture": (cint, [vp, vp, u32, vp]),
     "r3n_texture_stats": (cint, [vp, vp, cint]),
+    "r3n_sample_probe": (cint, [vp, u32, vp, u32, vp]),
     "r3n_texture_cubes_write": (cint, [vp, vp, u32, vp, u64]),
     "r3n_skybox_set": (cint, [vp, u32]),
     "r3n_animation_write": (cint, [vp, vp, u32, vp, u32, vp, u32, vp, u32, vp, u32, vp, u32]),

@@ -28,6 +28,7 @@ UNITS = {
     "shade_ms.hip": ["texture.h", "kernels_shade.h"],
     "shade_blend.hip": ["texture.h", "kernels_shade.h"],
     "skybox.hip": ["texture.h", "kernels_shade.h", "skybox.h"],
+    "sampler_probe.hip": ["texture.h", "exact_math.h"],
     "blend_sort.hip": ["blend_sort.h"],
     "morph.hip": ["morph.h", "vertex_gather.h", "exact_math.h"],
     "normals.hip": ["normals.h", "vertex_gather.h", "exact_math.h"],

@@ -1709,6 +1709,48 @@ int r3n_textures_remove(r3n_ctx *c, const uint32_t *slots, uint32_t n) {
     return upload_texture_slots(c, sorted, false);
 }
 
+extern "C" int r3n_internal_sample_probe(const TextureArgs *t, uint32_t form, const r3n_sample_query40 *queries, uint32_t n,
+                                         r3n_sample_result52 *out, hipStream_t stream);
+
+// The sampler on a list of queries (sampler_probe.hip), over texture_args(c) as the resolve gets it.  The short-path-only and batched
+// forms index the pool without a check -- the material classes' census (refresh_material_classes) is what makes that sound in a
+// frame -- so every query is held to the same census here, before anything is launched.
+int r3n_sample_probe(r3n_ctx *c, uint32_t form, const r3n_sample_query40 *queries, uint32_t n, r3n_sample_result52 *out) {
+    if (!c || (n && (!queries || !out))) return fail(c, R3N_ERR_INVALID_ARG, "sample probe: null");
+    if (form >= R3N_PROBE_FORM_COUNT) return fail(c, R3N_ERR_INVALID_ARG, "sample probe: unknown form");
+    const bool short_only = form == R3N_PROBE_SHORT || form == R3N_PROBE_SHORT_RGB || form == R3N_PROBE_SHARE ||
+                            form == R3N_PROBE_ALPHA_SHORT || form == R3N_PROBE_BATCHED;
+    if (short_only) {
+        const bool small_pool = c->n_texels <= (1ull << 30);
+        const uint32_t slots = (form == R3N_PROBE_SHARE || form == R3N_PROBE_BATCHED) ? 3u : 1u;
+        for (uint32_t i = 0; i < n; ++i) {
+            if (queries[i].nearest != 0u) return fail(c, R3N_ERR_INVALID_ARG, "sample probe: the short-path forms take the linear sampler only (query " + std::to_string(i) + ")");
+            for (uint32_t k = 0; k < slots; ++k) {
+                const uint32_t id = queries[i].id[k];
+                if (id && (!small_pool || id > c->n_textures || id > c->h_tex_short.size() || !c->h_tex_short[id - 1u]))
+                    return fail(c, R3N_ERR_INVALID_ARG, "sample probe: texture id " + std::to_string(id) + " of query " + std::to_string(i) + " is not on the sampler's short path");
+            }
+        }
+    }
+    if (!n) return R3N_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    TRY(sync_all(c));  // texture calls run on a stream of their own: what they wrote is there now
+    const TextureArgs t = texture_args(c);
+    void *dq = nullptr, *dr = nullptr;
+    int rc = R3N_OK;
+    const size_t qb = (size_t)n * sizeof(r3n_sample_query40), rb = (size_t)n * sizeof(r3n_sample_result52);
+    hipError_t e = hipMalloc(&dq, qb);
+    if (e == hipSuccess) e = hipMalloc(&dr, rb);
+    if (e == hipSuccess) e = hipMemcpyAsync(dq, queries, qb, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = (hipError_t)r3n_internal_sample_probe(&t, form, (const r3n_sample_query40 *)dq, n, (r3n_sample_result52 *)dr, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(out, dr, rb, hipMemcpyDeviceToHost, c->stream);
+    const hipError_t e2 = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess || e2 != hipSuccess) rc = fail(c, R3N_ERR_HIP, std::string("sample probe: ") + hipGetErrorString(e != hipSuccess ? e : e2));
+    if (dq) (void)hipFree(dq);
+    if (dr) (void)hipFree(dr);
+    return rc;
+}
+
 extern "C" int r3n_internal_move_segments(const uint32_t *block, uint64_t o_first, uint64_t o_inst, uint32_t first_wave, uint32_t waves,
                                           const uint32_t *src, uint32_t *dst, hipStream_t stream);
 

@@ -44,6 +44,11 @@ FLAGS_CC_BW_SPLIT = 0x1000
 FLAGS_UNLIT = 0x2000
 FLAGS_NEAREST = 0x4000
 
+# r3n_sample_probe (include/r3n.h): r3n_sample_query40 / r3n_sample_result52 and the R3N_PROBE_* form ids
+SAMPLE_QUERY = np.dtype([("id", np.uint32, 3), ("nearest", np.uint32), ("u", f32), ("v", f32), ("ddx", f32, 2), ("ddy", f32, 2)])
+SAMPLE_RESULT = np.dtype([("rgba", f32, (3, 4)), ("flags", np.uint32)])
+assert SAMPLE_QUERY.itemsize == 40 and SAMPLE_RESULT.itemsize == 52
+PROBE_FORMS = ("grad", "grad_rgb", "short", "short_rgb", "share", "alpha", "alpha_short", "batched")  # index = R3N_PROBE_*
 
 
 def material_texture_slots(ru, normal_texture, normal_mode, normal_y_down, aomr, reflectance_texture,
@@ -738,6 +743,16 @@ class Renderer:
         out = _ffi.TextureCompactResult()
         self._check(self.lib.r3n_textures_compact(self.ctx, ctypes.byref(opts), ctypes.byref(out)), "r3n_textures_compact")
         return {name: int(getattr(out, name)) for name, _ in _ffi.TextureCompactResult._fields_}
+
+    def sample_probe(self, form, queries):
+        """r3n_sample_probe: the frame kernels' texture sampler on a list of queries, over this renderer's textures (pending ones are
+        sent first).  form: an R3N_PROBE_* id; queries: array of SAMPLE_QUERY (40-byte records; 64 consecutive ones are one
+        wavefront).  Returns an array of SAMPLE_RESULT."""
+        self._flush_textures()
+        q = np.ascontiguousarray(queries, dtype=SAMPLE_QUERY)
+        out = np.zeros(len(q), dtype=SAMPLE_RESULT)
+        self._check(self.lib.r3n_sample_probe(self.ctx, int(form), _ffi.ptr(q), len(q), _ffi.ptr(out)), "r3n_sample_probe")
+        return out
 
     def _flush_textures(self, before_frame=False):
         changed = bool(self._tex_removals or self._tex_queue or self._tex_tails)
