@@ -10,8 +10,11 @@
 // Design: a 64-bit visibility buffer (depth bits << 32 | canonical triangle slot + 1) written
 // with 64-bit atomic max -- reverse-Z GreaterEqual + depth write is exactly "max" -- so opaque shading
 // runs once per pixel for the nearest fragment instead of once per rasterised fragment.  Triangles up to
-// 8x8 px are scanned by one thread; larger ones are split into <=64x64 px work items scanned by one
-// wavefront each (8x8 pixel blocks per step).
+// 8x8 px are scanned by one thread; larger ones are split into <= 32x32 px work items (R3N_TILE, columns on
+// R3N_ITEM_ALIGN) scanned by one wavefront each: four 8x2 pixel blocks per step (regions an opaque producer
+// queues), or one 8x8 block per step (wider regions: the transparent pass's).  The work-item kernel fetches
+// one record per step with a one-record-ahead prefetch (raster_big_body) or, in the two hot launches -- one
+// sample per pixel, opaque key -- R3N_BIG_BATCH records per wait (raster_big_batched_body).
 #pragma once
 #include "device_math.h"
 #include "texture.h"
@@ -445,7 +448,7 @@ R3N_DEV uint32_t pack_thresholds(const float thr[3]) {
 // the record after the next one pulled into the local L2 by an unwaited vector load (81.6 -> 81.3 us, frame 1.017 -> 1.024 ms).
 
 // Stage 1: one thread per list entry.  Small triangles are scanned in place; larger ones are split into
-// <=64x64 px items for stage 2.
+// <= R3N_TILE x R3N_TILE px items for stage 2.
 template <bool DEPTH_ONLY, int S = 1, bool TEX = false, bool NOCUT = false, bool SHORTA = false>
 R3N_DEV void raster_small_body(const RasterArgs &a) {
     // block b walks sub-list (b % R3N_SUBQ) of the region, and appends to work sub-queue (b % R3N_BIGQ)
@@ -597,8 +600,89 @@ R3N_DEV bool block_may_cover(const TriSetup &ts, int bx, int by, int rx1, int ry
     return may;
 }
 
-// Stage 2: scan of the work items (<= 64x64 px each): one wavefront per item, lane = 8x8 block for the rejection
-// test, then lane = pixel for every surviving block.  The item record is loaded once (lane j reads dword j) and
+// The consumer's side of pack_thresholds, on the SCALAR unit (the word is wave-uniform): same outcome as edge_threshold for every
+// non-NaN pair of coefficients; with a NaN coefficient the edge value is NaN and fails any threshold.
+R3N_DEV void unpack_thresholds(uint32_t mt, float thr[3]) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i) thr[i] = __uint_as_float((mt >> (R3N_BIG_THR_SHIFT + (uint32_t)i)) & 1u);  // 0 or the smallest subnormal
+}
+
+// The scan of ONE work item, shared by the two bodies of k_raster_big below: `w` holds the item's coefficients, thresholds and slot
+// (all wave-uniform), kxy0 / kxy1 its region (x | y << 16, inclusive corners).  Lane = block for the rejection test, then lane =
+// pixel for every surviving block.
+template <bool DEPTH_ONLY, int S, bool TEX, bool BLEND, bool SHORTA>
+R3N_DEV void scan_work_item(const RasterArgs &a, const TriWork &w, uint32_t kxy0, uint32_t kxy1, uint32_t lane) {
+    const int lx = (int)(lane & 7u), ly = (int)(lane >> 3);
+    const int rx0 = (int)(kxy0 & 0xFFFFu), ry0 = (int)(kxy0 >> 16);
+    const int rx1 = (int)(kxy1 & 0xFFFFu), ry1 = (int)(kxy1 >> 16);
+    const int gx0 = rx0 & ~(R3N_ITEM_ALIGN - 1);  // origin of the block grid: blocks sit on the target's cache lines
+    if (rx1 - gx0 < 32 && ry1 - ry0 < 32) {
+        // fine mode (regions up to 32x32 px): lane = 16-pixel block for the rejection test; every step then scans
+        // FOUR surviving blocks, 16 lanes each -- small triangles fill the wave far better than with 8x8 blocks.
+        // The block is FW x FH pixels (FW * FH = 16): the shape decides how many of the target's 64-byte lines one
+        // atomic instruction touches (a line is 16 depth texels / 8 keys of ONE row), which is what bounds this kernel.
+        constexpr int LW = DEPTH_ONLY ? R3N_FINE_LW_DEPTH : R3N_FINE_LW_VIS, FW = 1 << LW, FH = 16 >> LW, LC = 5 - LW;  // LC: log2 of the block columns
+        static_assert(LW >= 2 && LW <= 4, "blocks of 4x4, 8x2 or 16x1 pixels");
+        const int cbx = gx0 + (int)(lane & ((1u << LC) - 1u)) * FW, cby = ry0 + (int)(lane >> LC) * FH;
+        const bool cand = cbx <= rx1 && cbx + (FW - 1) >= rx0 && cby <= ry1 && block_may_cover<FW, (S > 1), FH>(w.ts, cbx, cby, rx1, ry1);
+        unsigned long long blocks = __ballot(cand);
+        const uint32_t grp = lane >> 4;
+        const int px = (int)(lane & (uint32_t)(FW - 1)), py = (int)((lane & 15u) >> LW);
+        if (S == 1 && !BLEND && !w.cutout) {
+            while (blocks) {
+                // four find-first / clear-bit pairs (an empty mask yields -1: no block, and clearing bit 63 of zero is harmless)
+                // (one statement: between separate asm statements the compiler pads every scalar write with a hazard s_nop)
+                uint32_t bsel[4];
+                asm("s_ff1_i32_b64 %0, %4\n\ts_bitset0_b64 %4, %0\n\t"
+                    "s_ff1_i32_b64 %1, %4\n\ts_bitset0_b64 %4, %1\n\t"
+                    "s_ff1_i32_b64 %2, %4\n\ts_bitset0_b64 %4, %2\n\t"
+                    "s_ff1_i32_b64 %3, %4\n\ts_bitset0_b64 %4, %3"
+                    : "=&s"(bsel[0]), "=&s"(bsel[1]), "=&s"(bsel[2]), "=&s"(bsel[3]), "+s"(blocks));
+                const uint32_t b = grp == 0u ? bsel[0] : (grp == 1u ? bsel[1] : (grp == 2u ? bsel[2] : bsel[3]));
+                int x, y;
+                asm("v_lshl_add_u32 %0, %1, %3, %2" : "=v"(x) : "v"(b & ((1u << LC) - 1u)), "v"(gx0 + px), "n"(LW));
+                asm("v_lshl_add_u32 %0, %1, %3, %2" : "=v"(y) : "v"(b >> LC), "v"(ry0 + py), "n"(4 - LW));
+                shade_pixel_cmpx<DEPTH_ONLY, true>(a, w, x, y, b, rx0, rx1, ry1);
+            }
+        } else
+        while (blocks) {
+            int bsel[4];
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                bsel[g] = blocks ? __builtin_ctzll(blocks) : 64;
+                blocks &= blocks - 1ull;
+            }
+            const int b = grp == 0u ? bsel[0] : (grp == 1u ? bsel[1] : (grp == 2u ? bsel[2] : bsel[3]));
+            // (field << 2) + base as ONE shift-add each (the compiler's canonical (b << 2) & 28 form costs an instruction
+            // more per coordinate and cannot be talked out of it)
+            int x, y;
+            asm("v_lshl_add_u32 %0, %1, %3, %2" : "=v"(x) : "v"(b & ((1 << LC) - 1)), "v"(gx0 + px), "n"(LW));
+            asm("v_lshl_add_u32 %0, %1, %3, %2" : "=v"(y) : "v"(b >> LC), "v"(ry0 + py), "n"(4 - LW));
+            if (b < 64 && x >= rx0 && x <= rx1 && y <= ry1) shade_pixel<DEPTH_ONLY, (R3N_PREREAD_BIG != 0) || (!DEPTH_ONLY && (S > 1 ? R3N_PREREAD_MS != 0 : R3N_PREREAD_VIEWPORT != 0)), S, TEX, BLEND, true, SHORTA>(a, w, x, y);
+        }
+    } else {
+        const int cbx = gx0 + lx * 8, cby = ry0 + ly * 8;
+        const bool cand = cbx <= rx1 && cbx + 7 >= rx0 && cby <= ry1 && block_may_cover<8, (S > 1)>(w.ts, cbx, cby, rx1, ry1);
+        unsigned long long blocks = __ballot(cand);
+        if (S == 1 && !BLEND && !w.cutout) {
+            while (blocks) {
+                int b;
+                asm("s_ff1_i32_b64 %0, %1\n\ts_bitset0_b64 %1, %0" : "=&s"(b), "+s"(blocks));
+                const int x = gx0 + (b & 7) * 8 + lx, y = ry0 + (b >> 3) * 8 + ly;
+                shade_pixel_cmpx<DEPTH_ONLY, false>(a, w, x, y, 0u, rx0, rx1, ry1);
+            }
+        } else
+        while (blocks) {
+            const int b = __builtin_ctzll(blocks);
+            blocks &= blocks - 1ull;
+            const int x = gx0 + (b & 7) * 8 + lx, y = ry0 + (b >> 3) * 8 + ly;
+            if (x >= rx0 && x <= rx1 && y <= ry1) shade_pixel<DEPTH_ONLY, (R3N_PREREAD_BIG != 0) || (!DEPTH_ONLY && (S > 1 ? R3N_PREREAD_MS != 0 : R3N_PREREAD_VIEWPORT != 0)), S, TEX, BLEND, true, SHORTA>(a, w, x, y);
+        }
+    }
+}
+
+// Stage 2: scan of the work items (<= R3N_TILE x R3N_TILE px each): one wavefront per item, lane = block for the rejection
+// test, then lane = pixel for every surviving block (scan_work_item).  The item record is loaded once (lane j reads dword j) and
 // broadcast through SGPRs with readlane, so the triangle's constants cost no vector registers or vector ALU work;
 // the next item's record is in flight while the current one is scanned.  Waves walk the concatenation of the
 // R3N_BIGQ producer sub-queues with a stride of the wave count, which spreads neighbouring (similar-cost) items
@@ -613,7 +697,6 @@ R3N_DEV void raster_big_body(RasterArgs a) {
     const uint32_t qgroup = 0u;
     const uint32_t wave_global = __builtin_amdgcn_readfirstlane(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
     const uint32_t nwaves = gridDim.x * (blockDim.x >> 6);
-    const int lx = (int)(lane & 7u), ly = (int)(lane >> 3);
     const uint32_t cap = a.big_capacity;
     // Sub-queue bounds live in registers: lane q < R3N_BIGQ holds [excl, incl), the flat indices of sub-queue q in the
     // concatenation (one vector load + a wave scan at kernel start, before any atomic is in flight).  Locating an item
@@ -669,12 +752,8 @@ R3N_DEV void raster_big_body(RasterArgs a) {
         }
         w.ts.det = 1.0f;  // (the scan does not use it)
         w.ts.valid = true;
-        // edge thresholds on the SCALAR unit: the coefficients are wave-uniform, the scalar unit compares integers only, and
-        // behind the (empty) asm the compiler can no longer turn the bit tests back into vector float compares.  Same outcome
-        // as edge_threshold for every non-NaN pair; with a NaN coefficient the edge value is NaN and fails any threshold.
         const uint32_t mt = bu(13);
-#pragma unroll
-        for (int i = 0; i < 3; ++i) w.thr[i] = __uint_as_float((mt >> (R3N_BIG_THR_SHIFT + (uint32_t)i)) & 1u);  // 0 or the smallest subnormal
+        unpack_thresholds(mt, w.thr);
         w.slot1 = bu(12);
         w.cutout = !BLEND && !NOCUT && a.key == R3N_KEY_CUTOUT;  // launch-uniform
         w.material = mt & R3N_BIG_MATERIAL_MASK;
@@ -709,82 +788,85 @@ R3N_DEV void raster_big_body(RasterArgs a) {
                 }
             }
         }
-        const uint32_t kxy0 = bu(14), kxy1 = bu(15);
-        const int rx0 = (int)(kxy0 & 0xFFFFu), ry0 = (int)(kxy0 >> 16);
-        const int rx1 = (int)(kxy1 & 0xFFFFu), ry1 = (int)(kxy1 >> 16);
-        const int gx0 = rx0 & ~(R3N_ITEM_ALIGN - 1);  // origin of the block grid: blocks sit on the target's cache lines
-        if (rx1 - gx0 < 32 && ry1 - ry0 < 32) {
-            // fine mode (regions up to 32x32 px): lane = 16-pixel block for the rejection test; every step then scans
-            // FOUR surviving blocks, 16 lanes each -- small triangles fill the wave far better than with 8x8 blocks.
-            // The block is FW x FH pixels (FW * FH = 16): the shape decides how many of the target's 64-byte lines one
-            // atomic instruction touches (a line is 16 depth texels / 8 keys of ONE row), which is what bounds this kernel.
-            constexpr int LW = DEPTH_ONLY ? R3N_FINE_LW_DEPTH : R3N_FINE_LW_VIS, FW = 1 << LW, FH = 16 >> LW, LC = 5 - LW;  // LC: log2 of the block columns
-            static_assert(LW >= 2 && LW <= 4, "blocks of 4x4, 8x2 or 16x1 pixels");
-            const int cbx = gx0 + (int)(lane & ((1u << LC) - 1u)) * FW, cby = ry0 + (int)(lane >> LC) * FH;
-            const bool cand = cbx <= rx1 && cbx + (FW - 1) >= rx0 && cby <= ry1 && block_may_cover<FW, (S > 1), FH>(w.ts, cbx, cby, rx1, ry1);
-            unsigned long long blocks = __ballot(cand);
-            const uint32_t grp = lane >> 4;
-            const int px = (int)(lane & (uint32_t)(FW - 1)), py = (int)((lane & 15u) >> LW);
-            if (S == 1 && !BLEND && !w.cutout) {
-                while (blocks) {
-                    // four find-first / clear-bit pairs (an empty mask yields -1: no block, and clearing bit 63 of zero is harmless)
-                    // (one statement: between separate asm statements the compiler pads every scalar write with a hazard s_nop)
-                    uint32_t bsel[4];
-                    asm("s_ff1_i32_b64 %0, %4\n\ts_bitset0_b64 %4, %0\n\t"
-                        "s_ff1_i32_b64 %1, %4\n\ts_bitset0_b64 %4, %1\n\t"
-                        "s_ff1_i32_b64 %2, %4\n\ts_bitset0_b64 %4, %2\n\t"
-                        "s_ff1_i32_b64 %3, %4\n\ts_bitset0_b64 %4, %3"
-                        : "=&s"(bsel[0]), "=&s"(bsel[1]), "=&s"(bsel[2]), "=&s"(bsel[3]), "+s"(blocks));
-                    const uint32_t b = grp == 0u ? bsel[0] : (grp == 1u ? bsel[1] : (grp == 2u ? bsel[2] : bsel[3]));
-                    int x, y;
-                    asm("v_lshl_add_u32 %0, %1, %3, %2" : "=v"(x) : "v"(b & ((1u << LC) - 1u)), "v"(gx0 + px), "n"(LW));
-                    asm("v_lshl_add_u32 %0, %1, %3, %2" : "=v"(y) : "v"(b >> LC), "v"(ry0 + py), "n"(4 - LW));
-                    shade_pixel_cmpx<DEPTH_ONLY, true>(a, w, x, y, b, rx0, rx1, ry1);
-                }
-            } else
-            while (blocks) {
-                int bsel[4];
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    bsel[g] = blocks ? __builtin_ctzll(blocks) : 64;
-                    blocks &= blocks - 1ull;
-                }
-                const int b = grp == 0u ? bsel[0] : (grp == 1u ? bsel[1] : (grp == 2u ? bsel[2] : bsel[3]));
-                // (field << 2) + base as ONE shift-add each (the compiler's canonical (b << 2) & 28 form costs an instruction
-                // more per coordinate and cannot be talked out of it)
-                int x, y;
-                asm("v_lshl_add_u32 %0, %1, %3, %2" : "=v"(x) : "v"(b & ((1 << LC) - 1)), "v"(gx0 + px), "n"(LW));
-                asm("v_lshl_add_u32 %0, %1, %3, %2" : "=v"(y) : "v"(b >> LC), "v"(ry0 + py), "n"(4 - LW));
-                if (b < 64 && x >= rx0 && x <= rx1 && y <= ry1) shade_pixel<DEPTH_ONLY, (R3N_PREREAD_BIG != 0) || (!DEPTH_ONLY && (S > 1 ? R3N_PREREAD_MS != 0 : R3N_PREREAD_VIEWPORT != 0)), S, TEX, BLEND, true, SHORTA>(a, w, x, y);
-            }
-        } else {
-            const int cbx = gx0 + lx * 8, cby = ry0 + ly * 8;
-            const bool cand = cbx <= rx1 && cbx + 7 >= rx0 && cby <= ry1 && block_may_cover<8, (S > 1)>(w.ts, cbx, cby, rx1, ry1);
-            unsigned long long blocks = __ballot(cand);
-            if (S == 1 && !BLEND && !w.cutout) {
-                while (blocks) {
-                    int b;
-                    asm("s_ff1_i32_b64 %0, %1\n\ts_bitset0_b64 %1, %0" : "=&s"(b), "+s"(blocks));
-                    const int x = gx0 + (b & 7) * 8 + lx, y = ry0 + (b >> 3) * 8 + ly;
-                    shade_pixel_cmpx<DEPTH_ONLY, false>(a, w, x, y, 0u, rx0, rx1, ry1);
-                }
-            } else
-            while (blocks) {
-                const int b = __builtin_ctzll(blocks);
-                blocks &= blocks - 1ull;
-                const int x = gx0 + (b & 7) * 8 + lx, y = ry0 + (b >> 3) * 8 + ly;
-                if (x >= rx0 && x <= rx1 && y <= ry1) shade_pixel<DEPTH_ONLY, (R3N_PREREAD_BIG != 0) || (!DEPTH_ONLY && (S > 1 ? R3N_PREREAD_MS != 0 : R3N_PREREAD_VIEWPORT != 0)), S, TEX, BLEND, true, SHORTA>(a, w, x, y);
-            }
-        }
+        scan_work_item<DEPTH_ONLY, S, TEX, BLEND, SHORTA>(a, w, bu(14), bu(15), lane);
         asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(na) : : "memory");
         rec = nrec;
         da = na;
     }
 }
 
+// The same stage for the two hot launches -- one sample per pixel, opaque key (shadow views and viewport): R3N_BIG_BATCH records per
+// wait.  A batch is B consecutive entries of one sub-queue; the wave reads all of them with plain scalar loads the compiler tracks,
+// one empty asm statement that takes every record as an input makes it issue them together and wait once, and the items are then
+// scanned one after the other out of SGPRs.  No prefetch: the kernel is bound by instruction issue, the scalar unit first
+// (profiles/work_item_batches.md), and what the other waves of the SIMD do hides a wave's wait; what pays is that the batch is
+// LOCATED once (ballot, readlane, address arithmetic) and that no record is copied from prefetch registers to working registers --
+// about thirty scalar instructions per item less.  (Vector-load batches of 4 / 8 / 16 records broadcast with readlane hide the whole
+// latency and lose: sixteen readlanes per item cost more issue slots than the wait they save.  Same file.)
+//   clamping   a record index past the sub-queue's count reads the last valid record instead (in bounds) and is not scanned
+//   locating   lane q < R3N_BIGQ holds the range of BATCH numbers of sub-queue q, ceil(count_q / B) of them; waves stride over batch
+//              numbers by the wave count; a wave without a batch leaves at once
+#define R3N_BIG_BATCH 3  // records per wait: 2, 3 or 4 (measured: profiles/work_item_batches.md)
+template <bool DEPTH_ONLY>
+R3N_DEV void raster_big_batched_body(const RasterArgs &a) {
+    constexpr uint32_t B = R3N_BIG_BATCH;
+    static_assert(B >= 2u && B <= 4u, "B records of sixteen scalar registers each");
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave_global = __builtin_amdgcn_readfirstlane(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
+    const uint32_t nwaves = gridDim.x * (blockDim.x >> 6);
+    const uint32_t cap = a.big_capacity;
+    const uint32_t qcnt_l = lane < R3N_BIGQ ? min(a.big_count[lane], cap) : 0u;
+    const uint32_t qbat_l = (qcnt_l + (B - 1u)) / B;
+    uint32_t incl = qbat_l;
+#pragma unroll
+    for (uint32_t d = 1; d < R3N_BIGQ; d <<= 1) {
+        const uint32_t t = __shfl_up(incl, d);
+        if (lane >= d) incl += t;
+    }
+    const uint32_t excl = incl - qbat_l;
+    typedef uint32_t u32x16 __attribute__((ext_vector_type(16)));
+    typedef __attribute__((address_space(4))) const u32x16 *sp_t;
+    auto scan = [&](const u32x16 &r) {
+        TriWork w;
+#pragma unroll
+        for (int e = 0; e < 3; ++e) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) w.ts.e[e][c] = __uint_as_float(r[3 * e + c]);
+            w.ts.z[e] = __uint_as_float(r[9 + e]);
+            w.va[e] = 1.0f;
+            w.uv[e][0] = w.uv[e][1] = 0.0f;
+        }
+        w.ts.det = 1.0f;  // (the scan does not use it)
+        w.ts.valid = true;
+        unpack_thresholds(r[13], w.thr);
+        w.slot1 = r[12];
+        w.cutout = false;
+        w.material = r[13] & R3N_BIG_MATERIAL_MASK;
+        w.mat_flags = 0u; w.mat_alpha = 1.0f; w.mat_cutoff = 0.0f;
+        w.alpha_tex = false;
+        scan_work_item<DEPTH_ONLY, 1, false, false, false>(a, w, r[14], r[15], lane);
+    };
+    for (uint32_t batch = wave_global;; batch += nwaves) {
+        const unsigned long long m = __ballot(batch >= excl && batch < incl);  // lanes >= R3N_BIGQ hold an empty range
+        if (!m) break;
+        const uint32_t q = (uint32_t)__builtin_ctzll(m);
+        const uint32_t at = (batch - (uint32_t)__builtin_amdgcn_readlane(excl, q)) * B;          // < count_q
+        const uint32_t n = min(B, (uint32_t)__builtin_amdgcn_readlane(qcnt_l, q) - at);         // 1 .. B valid records
+        const r3n_big_item *first = a.big_items + (size_t)(q * cap + at);                       // (queues hold < 2^32 items: r3n_create)
+        u32x16 r[B];
+#pragma unroll
+        for (uint32_t k = 0; k < B; ++k) r[k] = *(sp_t)(unsigned long long)(first + min(k, n - 1u));
+        asm volatile("" : : "s"(r[0]), "s"(r[1]), "s"(r[B > 2u ? 2u : 0u]), "s"(r[B - 1u]));  // (B < 4 names a record twice)
+#pragma unroll
+        for (uint32_t k = 0; k < B; ++k)
+            if (k < n) scan(r[k]);
+    }
+}
+
 template <bool DEPTH_ONLY, int S = 1, bool TEX = false, bool BLEND = false, bool NOCUT = false, bool SHORTA = false>
 __global__ __launch_bounds__(256) void k_raster_big(RasterArgs a) {
-    raster_big_body<DEPTH_ONLY, S, TEX, BLEND, NOCUT, SHORTA>(a);
+    if constexpr (S == 1 && !TEX && !BLEND && NOCUT && !SHORTA) raster_big_batched_body<DEPTH_ONLY>(a);
+    else raster_big_body<DEPTH_ONLY, S, TEX, BLEND, NOCUT, SHORTA>(a);
 }
 // ------------------------------------------------------------------------------------------------ clears
 __global__ __launch_bounds__(256) void k_fill_u64(unsigned long long *__restrict__ p, unsigned long long v, size_t n) {

@@ -36,7 +36,7 @@ KNOBS = {
     "cull_lds": [0, 16384],
     "vp_cull_lds": [0, 16384],
     "resolve_lds": [0, 36864, 49152],   # four / three workgroups per CU (160 KB): below ~36 KB the cap does not bind
-    "big_grid": [4096, 8192],
+    "big_grid": [1024, 2048, 4096, 8192, 16384],
     "small_grid": [1024, 2048, 4096],
 }
 # (the library's defaults: r3n.hip Tune)
