@@ -83,6 +83,7 @@ pub const R3N_SHARD_OBJECTS: u32 = 0;
 pub const R3N_SHARD_ROWS: u32 = 1;
 pub const R3N_COMM_ID_BYTES: i32 = 128;
 pub const R3N_COMM_IDS: i32 = 3;
+pub const R3N_SUBQ: i32 = 32;
 pub const R3N_STAGE_BAKE: i32 = 0;
 pub const R3N_STAGE_OBJECT_CULL: i32 = 1;
 pub const R3N_STAGE_TRIANGLE_CULL: i32 = 2;
@@ -427,6 +428,13 @@ pub struct r3n_frame_desc {
 
 #[repr(C)]
 #[derive(Clone, Copy)]
+pub struct r3n_tri_ref {
+    pub object: u32,
+    pub triangle: u32,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
 pub struct r3n_host_camera144 {
     pub view: [f32; 16],
     pub projection_kind: u32,
@@ -528,6 +536,7 @@ extern "C" {
     pub fn r3n_output_work_enqueued(ctx: *mut r3n_ctx) -> c_int;
     pub fn r3n_readback_visible_objects(ctx: *mut r3n_ctx, camera: u32, flags: *mut u8, capacity: u32) -> c_int;
     pub fn r3n_readback_triangle_sets(ctx: *mut r3n_ctx, camera: u32, pass: *mut u8, residual: *mut u8, n: u64) -> c_int;
+    pub fn r3n_readback_triangle_lists(ctx: *mut r3n_ctx, camera: u32, list: u32, out: *mut r3n_tri_ref, capacity: u64, counts: *mut u32, subcap: *mut u32) -> c_int;
     pub fn r3n_readback_draw_calls(ctx: *mut r3n_ctx, camera: u32, calls: *mut r3n_indirect_call) -> c_int;
     pub fn r3n_readback_raster_stats(ctx: *mut r3n_ctx, big_items: *mut u32) -> c_int;
     pub fn r3n_readback_blend_order(ctx: *mut r3n_ctx, order: *mut u32, rank_base: *mut u32, capacity: u32) -> c_int;

@@ -759,6 +759,20 @@ int r3n_readback_visible_objects(r3n_ctx *ctx, r3n_camera camera, uint8_t *flags
  * exclusive scan of (enabled ? index_count/3 : 0) over object slots.  pass = execute_culling result
  * (cull.wgsl:264-324); residual = newly visible (cull.wgsl:366-371).  `n` = total triangle count. */
 int r3n_readback_triangle_sets(r3n_ctx *ctx, r3n_camera camera, uint8_t *pass, uint8_t *residual, uint64_t n);
+/* TEST AND DIAGNOSTIC ENTRY: the lists `camera`'s last r3n_cull appended, entry by entry as the device holds them.  The triangle
+ * cull appends every passing triangle to the predicted list (list 0) and -- the viewport only -- every newly visible one to the
+ * residual list (list 1); each list has one region per (material key k, sub-list q), and a region holds counts[k][q] entries of
+ * the *subcap reserved for it.  `out` receives the regions' entries concatenated in (k, q) order, exactly as stored, never
+ * re-sorted: sum(counts) entries.  out == NULL asks for counts and *subcap alone (R3N_OK).  Not culled yet -> R3N_ERR_STATE;
+ * list 1 of a shadow camera (it has no residual list), a list number above 1 or a `capacity` (entries of `out`) below
+ * sum(counts) -> R3N_ERR_INVALID_ARG.  Host-side only: copies, no launch. */
+#define R3N_SUBQ 32
+typedef struct r3n_tri_ref {
+    uint32_t object;
+    uint32_t triangle;
+} r3n_tri_ref;
+int r3n_readback_triangle_lists(r3n_ctx *ctx, r3n_camera camera, uint32_t list, r3n_tri_ref *out, uint64_t capacity,
+                                uint32_t counts[3][R3N_SUBQ], uint32_t *subcap);
 /* per-region IndirectCall as cull.wgsl leaves it: calls[0..3) predicted, calls[3..6) residual (by material key) */
 int r3n_readback_draw_calls(r3n_ctx *ctx, r3n_camera camera, r3n_indirect_call calls[6]);
 /* work-queue occupancy of the rasteriser: big_items[i] = number of >8x8 px work items the i-th r3n_forward call of

@@ -93,6 +93,7 @@ SIGNATURES = {
     "r3n_output_work_enqueued": (cint, [vp]),
     "r3n_readback_visible_objects": (cint, [vp, u32, vp, u32]),
     "r3n_readback_triangle_sets": (cint, [vp, u32, vp, vp, u64]),
+    "r3n_readback_triangle_lists": (cint, [vp, u32, u32, vp, u64, vp, vp]),
     "r3n_readback_draw_calls": (cint, [vp, u32, vp]),
     "r3n_readback_raster_stats": (cint, [vp, vp]),
     "r3n_readback_blend_order": (cint, [vp, vp, vp, u32]),

@@ -778,8 +778,8 @@ struct TriCullArgs {
     const uint32_t *prev_slot_base;       // per object, INVALID when absent last frame; may be null
     const unsigned long long *prev_mask;  // may be null
     unsigned long long *mask;             // one u64 per wave slot
-    r3n_tri_ref *predicted;
-    r3n_tri_ref *residual;                // null for shadow cameras
+    r3n_tri_ref8 *predicted;
+    r3n_tri_ref8 *residual;                // null for shadow cameras
     r3n_sub_counts *sub_counts;           // append counters of this cull
     uint32_t subcap;                      // entries reserved per (material key, sub-list) in each list
     HizView hiz;
@@ -929,7 +929,7 @@ __global__ __launch_bounds__(256) void k_triangle_cull(TriCullArgs a) {
             if (pb == 0ull) continue;
             const unsigned long long rb = s_resid[wave][it];
             const uint32_t key = s_key[wave][it];
-            const r3n_tri_ref ref = {s_obj[wave][it], s_tri0[wave][it] + lane};
+            const r3n_tri_ref8 ref = {s_obj[wave][it], s_tri0[wave][it] + lane};
             const uint32_t np = (uint32_t)__popcll(pb), nr = (uint32_t)__popcll(rb);
             const uint32_t rp = key == 0u ? run_p[0] : (key == 1u ? run_p[1] : run_p[2]);
             const uint32_t rr = key == 0u ? run_r[0] : (key == 1u ? run_r[1] : run_r[2]);

@@ -28,7 +28,7 @@ struct RasterArgs {
     const uint8_t *material_keys;
     uint32_t n_materials;
     const uint32_t *tri_base;              // canonical slot base per object (forward only)
-    const r3n_tri_ref *list;               // compacted triangle list of this camera/source
+    const r3n_tri_ref8 *list;              // compacted triangle list of this camera/source
     const uint32_t *sub_counts;            // [3][R3N_SUBQ] triangles per (material key, sub-list) of that list
     uint32_t subcap;                       // entries reserved per (material key, sub-list)
     uint32_t key;                          // region to draw
@@ -454,7 +454,7 @@ R3N_DEV void raster_small_body(const RasterArgs &a) {
     // block b walks sub-list (b % R3N_SUBQ) of the region, and appends to work sub-queue (b % R3N_BIGQ)
     const uint32_t q = blockIdx.x % R3N_SUBQ;
     const uint32_t n = a.sub_counts[a.key * R3N_SUBQ + q];
-    const r3n_tri_ref *list = a.list + (size_t)(a.key * R3N_SUBQ + q) * a.subcap;
+    const r3n_tri_ref8 *list = a.list + (size_t)(a.key * R3N_SUBQ + q) * a.subcap;
     // producer side of the work queue: the sub-queue is chosen per WAVE.  readfirstlane makes the counter address
     // provably wave-uniform, which is what lets the compiler fold a wave's appends into ONE atomic (with a
     // per-lane address every lane issues its own returning atomic -- measured 4x slower kernels)
@@ -462,7 +462,7 @@ R3N_DEV void raster_small_body(const RasterArgs &a) {
     const bool positive_visible = (a.hdr->flags & R3N_PCU_POSITIVE_AREA_VISIBLE) != 0u;
     const uint32_t stride = (gridDim.x / R3N_SUBQ) * blockDim.x;
     for (uint32_t i = (blockIdx.x / R3N_SUBQ) * blockDim.x + threadIdx.x; i < n; i += stride) {
-        const r3n_tri_ref ref = list[i];
+        const r3n_tri_ref8 ref = list[i];
         TriWork tw;
         if (!prepare_triangle<DEPTH_ONLY, TEX, NOCUT>(a, ref.object, ref.triangle, positive_visible, tw)) continue;
         const int bw = tw.x1 - tw.x0 + 1, bh = tw.y1 - tw.y0 + 1;

@@ -103,10 +103,12 @@ struct r3n_cull_counts {
 
 // One compacted triangle reference (the "index buffer" of this implementation: 8 B instead of the
 // reference's 3 packed u32 because the rasteriser re-fetches indices through the object record).
-struct alignas(8) r3n_tri_ref {  // 8-byte aligned: one dwordx2 load / store per entry
+struct alignas(8) r3n_tri_ref8 {  // 8-byte aligned: one dwordx2 load / store per entry
     uint32_t object;
     uint32_t triangle;
 };
+// include/r3n.h r3n_tri_ref is the same two words without the alignment (r3n_readback_triangle_lists copies entries out as they are)
+static_assert(sizeof(r3n_tri_ref8) == sizeof(r3n_tri_ref) && offsetof(r3n_tri_ref8, triangle) == offsetof(r3n_tri_ref, triangle), "list entry");
 
 // Raster work item for triangles larger than 8x8 px: one wavefront scans a <=64x64 px region.  The item carries
 // the finished triangle setup (the producer computed it to classify the triangle), so the consumer has no
@@ -132,9 +134,9 @@ static_assert(sizeof(r3n_big_uv) == 48, "big item cutout record is 12 dwords");
 // Output lists and work queues are split into sub-queues so that appends do not serialise on one counter: a
 // returning atomic on a single address retires at only ~88 per microsecond on MI355X (MI355X_MICROARCH.md,
 // "dequeue" row), which was the bound of the cull kernel with a single counter per list.
-#define R3N_SUBQ 32   // sub-lists per (list, material key) of the cull output
-#define R3N_BIGQ 32   // sub-queues of the rasteriser's large-triangle work queue; the consumers index their
-                      // concatenation, so the split only spreads the producers' counter traffic
+// R3N_SUBQ (include/r3n.h, 32): sub-lists per (list, material key) of the cull output
+#define R3N_BIGQ 32  // sub-queues of the rasteriser's large-triangle work queue; the consumers index their
+                     // concatenation, so the split only spreads the producers' counter traffic
 struct r3n_sub_counts {
     uint32_t n[2][3][R3N_SUBQ];  // [predicted|residual][material key][sub-list] = triangles appended
 };

@@ -2472,7 +2472,7 @@ int r3n_cull(r3n_ctx *c, r3n_camera cam) {
     const uint32_t chunks = (mw + R3N_CHUNK_WAVES - 1u) / R3N_CHUNK_WAVES;
     // every chunk appends to sub-list (chunk % R3N_SUBQ); worst case all of its slots pass and share one key
     const uint32_t subcap = ((chunks + R3N_SUBQ - 1u) / R3N_SUBQ) * (R3N_CHUNK_WAVES * 64u);
-    const size_t list_bytes = (size_t)3 * R3N_SUBQ * subcap * sizeof(r3n_tri_ref);
+    const size_t list_bytes = (size_t)3 * R3N_SUBQ * subcap * sizeof(r3n_tri_ref8);
     s->subcap[cur] = subcap;
     TRY(ensure(c, s->mask[cur], (size_t)mw * 8u, false, -1));
     TRY(ensure(c, s->predicted[cur], list_bytes, false, -1));
@@ -2493,8 +2493,8 @@ int r3n_cull(r3n_ctx *c, r3n_camera cam) {
     a.prev_slot_base = (viewport && s->has_prev) ? s->slot_base[prev].as<uint32_t>() : nullptr;
     a.prev_mask = (viewport && s->has_prev) ? s->mask[prev].as<unsigned long long>() : nullptr;
     a.mask = s->mask[cur].as<unsigned long long>();
-    a.predicted = s->predicted[cur].as<r3n_tri_ref>();
-    a.residual = viewport ? s->residual.as<r3n_tri_ref>() : nullptr;
+    a.predicted = s->predicted[cur].as<r3n_tri_ref8>();
+    a.residual = viewport ? s->residual.as<r3n_tri_ref8>() : nullptr;
     a.sub_counts = s->sub_counts[cur].as<r3n_sub_counts>();
     a.subcap = subcap;
     a.hiz.data = c->hiz.as<float>();
@@ -2591,19 +2591,19 @@ int r3n_forward(r3n_ctx *c, r3n_camera cam, uint32_t pass, uint32_t source, uint
     }
     HIP_TRY(c, hipSetDevice(c->device));
     int idx;
-    const r3n_tri_ref *list;
+    const r3n_tri_ref8 *list;
     const uint32_t *sub_counts;
     if (source == R3N_SOURCE_PREDICTED) {
         // last frame's predicted triangles, this frame's matrices (forward.rs:224-232, App. D.8)
         if (!s->has_prev) return R3N_OK;
         idx = 1 - s->cur;
-        list = s->predicted[idx].as<r3n_tri_ref>();
+        list = s->predicted[idx].as<r3n_tri_ref8>();
         sub_counts = &s->sub_counts[idx].as<r3n_sub_counts>()->n[0][0][0];
     } else {
         if (!s->culled) return R3N_OK;
         idx = s->cur;
         // residual && viewport -> residual list; otherwise the list written this frame (forward.rs:234,251)
-        list = viewport ? s->residual.as<r3n_tri_ref>() : s->predicted[idx].as<r3n_tri_ref>();
+        list = viewport ? s->residual.as<r3n_tri_ref8>() : s->predicted[idx].as<r3n_tri_ref8>();
         sub_counts = &s->sub_counts[idx].as<r3n_sub_counts>()->n[viewport ? 1 : 0][0][0];
     }
     RasterArgs a{};
@@ -3767,13 +3767,40 @@ int r3n_readback_triangle_sets(r3n_ctx *c, r3n_camera cam, uint8_t *pass, uint8_
                 for (uint32_t q = 0; q < R3N_SUBQ; ++q) {
                     const uint32_t cnt = sc.n[1][k][q];
                     if (!cnt) continue;
-                    std::vector<r3n_tri_ref> refs(cnt);
-                    TRY(copy_d2h(c, refs.data(), s->residual.as<r3n_tri_ref>() + (size_t)(k * R3N_SUBQ + q) * s->subcap[idx],
-                            (size_t)cnt * sizeof(r3n_tri_ref)));
+                    std::vector<r3n_tri_ref8> refs(cnt);
+                    TRY(copy_d2h(c, refs.data(), s->residual.as<r3n_tri_ref8>() + (size_t)(k * R3N_SUBQ + q) * s->subcap[idx],
+                            (size_t)cnt * sizeof(r3n_tri_ref8)));
                     for (const auto &r : refs) residual[(uint64_t)tri_base[r.object] + r.triangle] = 1;
                 }
         }
     }
+    return check_async_status(c);
+}
+
+int r3n_readback_triangle_lists(r3n_ctx *c, r3n_camera cam, uint32_t list, r3n_tri_ref *out, uint64_t capacity,
+                                uint32_t counts[3][R3N_SUBQ], uint32_t *subcap) {
+    CamState *s = c ? find_cam(c, cam, false) : nullptr;
+    if (!s || s->last < 0) return fail(c, R3N_ERR_STATE, "readback_triangle_lists: camera never culled");
+    if (!counts || !subcap) return fail(c, R3N_ERR_INVALID_ARG, "readback_triangle_lists: null");
+    if (list > 1u) return fail(c, R3N_ERR_INVALID_ARG, "readback_triangle_lists: list is 0 (predicted) or 1 (residual)");
+    if (list == 1u && cam != R3N_CAMERA_VIEWPORT) return fail(c, R3N_ERR_INVALID_ARG, "readback_triangle_lists: a shadow camera has no residual list");
+    const int idx = s->last;
+    r3n_sub_counts sc;
+    TRY(copy_d2h(c, &sc, s->sub_counts[idx].p, sizeof sc));
+    uint64_t total = 0;
+    for (uint32_t k = 0; k < 3; ++k)
+        for (uint32_t q = 0; q < R3N_SUBQ; ++q) total += (counts[k][q] = sc.n[list][k][q]);
+    *subcap = s->subcap[idx];
+    if (!out) return check_async_status(c);  // the counts alone
+    if (capacity < total) return fail(c, R3N_ERR_INVALID_ARG, "readback_triangle_lists: buffer too small");
+    const r3n_tri_ref8 *src = list == 0u ? s->predicted[idx].as<r3n_tri_ref8>() : s->residual.as<r3n_tri_ref8>();
+    for (uint32_t k = 0; k < 3; ++k)
+        for (uint32_t q = 0; q < R3N_SUBQ; ++q) {
+            // a count above the region's reservation is the caller's finding: what is copied stays inside the region
+            const uint32_t n = std::min(counts[k][q], s->subcap[idx]);
+            if (n) TRY(copy_d2h(c, out, src + (size_t)(k * R3N_SUBQ + q) * s->subcap[idx], (size_t)n * sizeof(r3n_tri_ref)));
+            out += counts[k][q];
+        }
     return check_async_status(c);
 }
 

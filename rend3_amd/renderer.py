@@ -915,6 +915,23 @@ class Renderer:
                                                _ffi.ptr(recs) if len(slots) else None, len(slots), self.capacity),
                     "r3n_objects_write")
 
+    def write_object_records(self, slots, records, capacity, blend=None):
+        """Bulk edit for tests and tools: r3n_object128 rows (32 u32 words each) written as they are to `slots` with ONE
+        r3n_objects_write, the object buffer then `capacity` slots long (any number).  The per-object mirror is REPLACED, not
+        updated: afterwards it knows only `blend` -- {slot: (material index, sorting location)} of the enabled objects the
+        transparent pass has to order -- so a context written this way is not edited through add_object / remove_object."""
+        if self.dirty_objects or self.pending_free or self.deferred_removals:
+            raise RuntimeError("write_object_records: the context has object edits of its own pending")
+        slots = np.ascontiguousarray(slots, dtype=np.uint32).reshape(-1)
+        records = np.ascontiguousarray(records, dtype=np.uint32).reshape(len(slots), 32)
+        if len(slots):
+            self._check(self.lib.r3n_objects_write(self.ctx, _ffi.ptr(slots), _ffi.ptr(records), len(slots), int(capacity)), "r3n_objects_write")
+        self.capacity = self._capacity_sent = int(capacity)
+        self.object_meta = {int(h): dict(enabled=True, material=int(m), location=np.asarray(loc, dtype=f32).copy())
+                            for h, (m, loc) in (blend or {}).items()}
+        self._blend_cache = None
+        self.world_version += 1
+
     def add_object(self, mesh, material, transform, skeleton=None, morph=None):
         """morph: a morph instance (add_morph_instance) -- the object draws the instance's runs; with skeleton= the skeleton's
         own morph instance (add_skeleton(..., morph=)) applies instead."""
@@ -1304,6 +1321,20 @@ class Renderer:
         self._check(lib.r3n_readback_output(ctx, _ffi.ptr(rgba8), _ffi.ptr(rgba_f)), "readback_output")
         out.update(vis=vis, atlas=atlas, atlas_size=(aw, ah), hdr16=hdr16, rgba8=rgba8, rgba_f32=rgba_f)
         return out
+
+    def readback_triangle_lists(self, cam, which):
+        """r3n_readback_triangle_lists (a test and diagnostic entry): the predicted (`which` 0) or residual (1) list of `cam`'s last
+        cull as the device holds it.  Returns (refs, counts, subcap): refs (n, 2) u32 rows (object, triangle), the regions'
+        entries concatenated in (material key, sub-list) order and never re-sorted; counts (3, R3N_SUBQ) u32; the entries
+        reserved per region.  A count above subcap leaves the rows beyond the region 0xFFFFFFFF."""
+        counts, subcap = np.zeros((3, 32), dtype=np.uint32), ctypes.c_uint32()
+        lib, args = self.lib, (self.ctx, int(cam), int(which))
+        self._check(lib.r3n_readback_triangle_lists(*args, None, 0, _ffi.ptr(counts), ctypes.byref(subcap)), "r3n_readback_triangle_lists")
+        n = int(counts.sum(dtype=np.uint64))
+        refs = np.full((n, 2), 0xFFFFFFFF, dtype=np.uint32)
+        if n:
+            self._check(lib.r3n_readback_triangle_lists(*args, _ffi.ptr(refs), n, _ffi.ptr(counts), ctypes.byref(subcap)), "r3n_readback_triangle_lists")
+        return refs, counts, int(subcap.value)
 
     def raster_stats(self):
         """r3n_readback_raster_stats: work items each r3n_forward call of the last frame queued, [0..16) the viewport's, then 12 per
