@@ -59,6 +59,7 @@ pub const R3N_TEXTURE_FORMAT_COUNT: u32 = 34;
 pub const R3N_MAX_MORPH_TARGETS: u32 = 256;
 pub const R3N_SHADE_EXACT: u32 = 0;
 pub const R3N_SHADE_FAST: u32 = 1;
+pub const R3N_MESH_BLOCK_ZERO: u32 = 1;
 pub const R3N_PROBE_GRAD: i32 = 0;
 pub const R3N_PROBE_GRAD_RGB: i32 = 1;
 pub const R3N_PROBE_SHORT: i32 = 2;
@@ -320,6 +321,61 @@ pub struct r3n_config {
 
 #[repr(C)]
 #[derive(Clone, Copy)]
+pub struct r3n_mesh_block24 {
+    pub payload_offset: u64,
+    pub words: u64,
+    pub flags: u32,
+    pub _pad: u32,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct r3n_mesh_move24 {
+    pub old_byte_offset: u64,
+    pub new_byte_offset: u64,
+    pub padded_words: u64,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct r3n_mesh_compact_opts {
+    pub max_words: u64,
+    pub stage_words: u64,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct r3n_mesh_compact_result {
+    pub blocks_moved: u64,
+    pub words_moved: u64,
+    pub passes: u64,
+    pub kernel_launches: u64,
+    pub full_syncs: u64,
+    pub pool_words_before: u64,
+    pub pool_words_after: u64,
+    pub free_ranges_after: u64,
+    pub relocate_ns: u64,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct r3n_mesh_counters {
+    pub add_calls: u64,
+    pub remove_calls: u64,
+    pub compact_calls: u64,
+    pub bytes_staged: u64,
+    pub launches: u64,
+    pub full_waits: u64,
+    pub growths: u64,
+    pub blocks_live: u64,
+    pub live_words: u64,
+    pub pool_words: u64,
+    pub free_ranges: u64,
+    pub buffer_words: u64,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
 pub struct r3n_texture_compact_opts {
     pub max_words: u64,
     pub stage_words: u64,
@@ -482,6 +538,10 @@ extern "C" {
     pub fn r3n_sync(ctx: *mut r3n_ctx) -> c_int;
     pub fn r3n_stream(ctx: *mut r3n_ctx) -> *mut c_void;
     pub fn r3n_mesh_buffer_write(ctx: *mut r3n_ctx, byte_offset: u64, data: *const c_void, bytes: u64) -> c_int;
+    pub fn r3n_mesh_blocks_add(ctx: *mut r3n_ctx, blocks: *const r3n_mesh_block24, n: u32, payload: *const c_void, payload_bytes: u64, byte_offsets_out: *mut u64) -> c_int;
+    pub fn r3n_mesh_blocks_remove(ctx: *mut r3n_ctx, byte_offsets: *const u64, n: u32) -> c_int;
+    pub fn r3n_mesh_compact(ctx: *mut r3n_ctx, opts: *const r3n_mesh_compact_opts, result: *mut r3n_mesh_compact_result, moves_out: *mut r3n_mesh_move24, moves_capacity: u32) -> c_int;
+    pub fn r3n_mesh_stats(ctx: *mut r3n_ctx, out: *mut r3n_mesh_counters, reset: c_int) -> c_int;
     pub fn r3n_objects_write(ctx: *mut r3n_ctx, slots: *const u32, records: *const r3n_object128, n: u32, capacity: u32) -> c_int;
     pub fn r3n_materials_write(ctx: *mut r3n_ctx, slots: *const u32, records: *const r3n_material208, keys: *const u8, n: u32) -> c_int;
     pub fn r3n_textures_write(ctx: *mut r3n_ctx, descs: *const r3n_texture_desc32, n_textures: u32, texels: *const u32, n_texels: u64) -> c_int;
@@ -542,6 +602,7 @@ extern "C" {
     pub fn r3n_readback_blend_order(ctx: *mut r3n_ctx, order: *mut u32, rank_base: *mut u32, capacity: u32) -> c_int;
     pub fn r3n_readback_baked(ctx: *mut r3n_ctx, camera: u32, model_view_and_mvp: *mut f32, capacity: u32) -> c_int;
     pub fn r3n_readback_mesh(ctx: *mut r3n_ctx, byte_offset: u64, dst: *mut c_void, bytes: u64) -> c_int;
+    pub fn r3n_readback_objects(ctx: *mut r3n_ctx, first_slot: u32, records: *mut r3n_object128, n: u32) -> c_int;
     pub fn r3n_readback_joint_matrices(ctx: *mut r3n_ctx, first_matrix: u32, dst: *mut f32, n_matrices: u32) -> c_int;
     pub fn r3n_readback_texture_descs(ctx: *mut r3n_ctx, descs: *mut r3n_texture_desc32, capacity: u32, n_slots: *mut u32) -> c_int;
     pub fn r3n_readback_texels(ctx: *mut r3n_ctx, first_texel: u64, rgba8: *mut u32, n_texels: u64) -> c_int;

@@ -290,6 +290,78 @@ void *r3n_stream(r3n_ctx *ctx);
 /* ---- world data uploads (the managers' GPU buffers the hot path reads)
  *      MeshManager::add upload, rend3/src/managers/mesh.rs:123-184 (layout: SoA attribute runs + u32 indices) */
 int r3n_mesh_buffer_write(r3n_ctx *ctx, uint64_t byte_offset, const void *data, uint64_t bytes);
+/* ---- pooled mesh blocks: the mesh buffer as a pool that gives words back (MeshManager sub-allocates every attribute and index
+ *      range from a RangeAllocator, rend3/src/managers/mesh.rs:123-184 add, :228-258 allocate_range / free_range, and grows the
+ *      buffer only when no hole fits, :232-308; skeletons take and return their private copies the same way,
+ *      rend3/src/managers/skeleton.rs:105-113 and :139-147).  A BLOCK is one contiguous allocation of mesh-buffer words on a 4-word
+ *      (16-byte) boundary -- a mesh's whole blob (attribute runs, indices, delta block, adjacency), one skeleton's private runs, or
+ *      one morph instance's private runs; its padded length is a multiple of 4 words, so a slide by a multiple of 16 bytes keeps
+ *      every alignment inside it.  The first r3n_mesh_blocks_add puts the context in POOLED mode: r3n_mesh_buffer_write then stays
+ *      legal for ranges inside ONE live block (padding included; in-place edits, with its usual waits) and returns R3N_ERR_STATE
+ *      elsewhere.  A context whose mesh buffer was written by r3n_mesh_buffer_write before refuses r3n_mesh_blocks_add with
+ *      R3N_ERR_STATE.  All four calls below are refused between r3n_frame_begin and r3n_frame_end (R3N_ERR_STATE).
+ *
+ *      r3n_mesh_blocks_add (MeshManager::add / allocate_range, mesh.rs:123-184, :228-247): n blocks; block i takes blocks[i].words
+ *      (>= 1) words from payload + blocks[i].payload_offset (a multiple of 4 bytes, the range inside payload_bytes), or, with
+ *      R3N_MESH_BLOCK_ZERO, no payload: its words are zero-filled on the device (the private runs of skeletons and morph
+ *      instances).  byte_offsets_out[i] = where the block starts.  Placement is first fit at the lowest address over the holes,
+ *      else behind the high-water mark -- deterministic, so every rank that makes the same calls gets the same offsets.  Copies
+ *      and fills run on the update path's own stream and the call waits for that stream alone: words no enqueued frame can name --
+ *      behind the mark, or a hole that was free at the last full wait -- are written without waiting for a frame.  Words freed
+ *      since the last full wait are parked; holes that were free before are preferred, and taking parked words costs ONE wait for
+ *      every frame in flight.  Growth of the device block (x 2) is one device-to-device copy behind such a wait.  A block that
+ *      would end past byte 2^32 -> R3N_ERR_CAPACITY; a bad record (words == 0, unknown flags, a payload range outside the
+ *      payload or not 4-byte aligned) -> R3N_ERR_INVALID_ARG; both with nothing allocated or written.
+ *
+ *      r3n_mesh_blocks_remove (MeshManager::remove / free_range, mesh.rs:197-211, :249-258; SkeletonManager::remove,
+ *      skeleton.rs:139-147): frees whole blocks by their start; the words are parked until the next full wait (a frame in flight
+ *      may still read them).  An offset that is not the start of a live block, or one named twice -> R3N_ERR_INVALID_ARG with
+ *      nothing changed.  Never waits for the GPU.  The caller disables (r3n_objects_write) every object that names the block
+ *      first: the object pass never fetches geometry of a disabled slot.
+ *
+ *      r3n_mesh_compact (no counterpart in the reference, whose allocator never moves a range): slides the live blocks towards
+ *      word 0 in ascending address order, each to the 4-word boundary behind the one before (opts as r3n_texture_compact_opts:
+ *      max_words, stage_words, same meaning, defaults and refusals), and RELOCATES on the device every address the object buffer
+ *      holds: in every record below the object capacity, enabled or not, first_index (words) and the six
+ *      vertex_attribute_start_offsets (bytes) that lie inside a moved block follow it; nothing else of a record is written
+ *      (csrc/mesh_reloc.h states the rule).  The call waits ONCE for every frame in flight (parked words become holes), enqueues
+ *      the moves and the relocation, and waits for its own work; with nothing to move it returns without any wait.  moves_out
+ *      receives the moves in ascending address order so that the caller can fix its own mirrors -- the inputs of r3n_skinning,
+ *      r3n_morph, r3n_vertex_normals and r3n_vertex_tangents are the caller's; moves_capacity smaller than the number of moves ->
+ *      R3N_ERR_INVALID_ARG with nothing changed (blocks_live of r3n_mesh_stats is always enough).  result (may be NULL): as
+ *      r3n_texture_compact_result, kernel_launches counting the relocation launch, plus relocate_ns.  R3N_ERR_HIP: as
+ *      r3n_textures_compact -- the context's allocator is the one from before the call, the words are unspecified.
+ *
+ *      r3n_mesh_stats: counters since creation or the last reset (add_calls, remove_calls, compact_calls, bytes_staged,
+ *      launches = fills, move kernels and relocation kernels, full_waits = waits for every frame in flight the calls above made,
+ *      growths) and the pool's state now (blocks_live, live_words unpadded, pool_words = the high-water mark, free_ranges,
+ *      buffer_words = the device block's size).  `out` may be NULL with reset != 0. */
+#define R3N_MESH_BLOCK_ZERO 1u
+typedef struct r3n_mesh_block24 {
+    uint64_t payload_offset; /* bytes into payload; ignored with R3N_MESH_BLOCK_ZERO */
+    uint64_t words;
+    uint32_t flags, _pad;
+} r3n_mesh_block24;
+typedef struct r3n_mesh_move24 {
+    uint64_t old_byte_offset, new_byte_offset, padded_words;
+} r3n_mesh_move24;
+typedef struct r3n_mesh_compact_opts {
+    uint64_t max_words, stage_words;
+} r3n_mesh_compact_opts;
+typedef struct r3n_mesh_compact_result {
+    uint64_t blocks_moved, words_moved, passes, kernel_launches, full_syncs, pool_words_before, pool_words_after, free_ranges_after;
+    uint64_t relocate_ns; /* the relocation kernel alone, between two device events on the call's stream (0: nothing launched) */
+} r3n_mesh_compact_result;
+typedef struct r3n_mesh_counters {
+    uint64_t add_calls, remove_calls, compact_calls, bytes_staged, launches, full_waits, growths, blocks_live, live_words, pool_words,
+        free_ranges, buffer_words;
+} r3n_mesh_counters;
+int r3n_mesh_blocks_add(r3n_ctx *ctx, const r3n_mesh_block24 *blocks, uint32_t n, const void *payload, uint64_t payload_bytes,
+                        uint64_t *byte_offsets_out);
+int r3n_mesh_blocks_remove(r3n_ctx *ctx, const uint64_t *byte_offsets, uint32_t n);
+int r3n_mesh_compact(r3n_ctx *ctx, const r3n_mesh_compact_opts *opts, r3n_mesh_compact_result *result, r3n_mesh_move24 *moves_out,
+                     uint32_t moves_capacity);
+int r3n_mesh_stats(r3n_ctx *ctx, r3n_mesh_counters *out, int reset);
 /*      ObjectManager::evaluate scatter upload, rend3/src/managers/object.rs:344-364.
  *      `capacity` = object-buffer capacity in records (FreelistDerivedBuffer, util/freelist/buffer.rs:48-52);
  *      growing it preserves existing records, new records are zero (enabled == 0). */
@@ -786,6 +858,10 @@ int r3n_readback_blend_order(r3n_ctx *ctx, uint32_t *order, uint32_t *rank_base,
  * frame are defined (see r3n_uniform_bake); after the per-node r3n_uniform_bake every enabled slot is. */
 int r3n_readback_baked(r3n_ctx *ctx, r3n_camera camera, float *model_view_and_mvp, uint32_t capacity);
 int r3n_readback_mesh(r3n_ctx *ctx, uint64_t byte_offset, void *dst, uint64_t bytes); /* e.g. skinned attribute runs */
+/* The 128-byte object records [first_slot, first_slot + n) as the device holds them (ObjectManager's buffer, rend3/src/managers/
+ * object.rs:344-364; after r3n_mesh_compact: with the relocated offsets, mesh.rs:197-211 being the reason a range ever moves here).
+ * first_slot + n beyond the object capacity -> R3N_ERR_INVALID_ARG.  Waits for every frame in flight. */
+int r3n_readback_objects(r3n_ctx *ctx, uint32_t first_slot, r3n_object128 *records, uint32_t n);
 int r3n_readback_joint_matrices(r3n_ctx *ctx, uint32_t first_matrix, float *dst, uint32_t n_matrices); /* what the last r3n_skinning read */
 /* The texture table as the device holds it (rend3/src/managers/texture.rs keeps one entry per handle): offset in pool words, width,
  * height, mips, format = the pool class (R3N_TEXTURE_RGBA8_UNORM / _SRGB, or 2 = four f32 per texel); removed slots have width =

@@ -38,6 +38,10 @@ SIGNATURES = {
     "r3n_sync": (cint, [vp]),
     "r3n_stream": (vp, [vp]),
     "r3n_mesh_buffer_write": (cint, [vp, u64, vp, u64]),
+    "r3n_mesh_blocks_add": (cint, [vp, vp, u32, vp, u64, vp]),
+    "r3n_mesh_blocks_remove": (cint, [vp, vp, u32]),
+    "r3n_mesh_compact": (cint, [vp, vp, vp, vp, u32]),
+    "r3n_mesh_stats": (cint, [vp, vp, cint]),
     "r3n_objects_write": (cint, [vp, vp, vp, u32, u32]),
     "r3n_materials_write": (cint, [vp, vp, vp, vp, u32]),
     "r3n_textures_write": (cint, [vp, vp, u32, vp, u64]),
@@ -99,6 +103,7 @@ SIGNATURES = {
     "r3n_readback_blend_order": (cint, [vp, vp, vp, u32]),
     "r3n_readback_baked": (cint, [vp, u32, vp, u32]),
     "r3n_readback_mesh": (cint, [vp, u64, vp, u64]),
+    "r3n_readback_objects": (cint, [vp, u32, vp, u32]),
     "r3n_readback_texture_descs": (cint, [vp, vp, u32, vp]),
     "r3n_readback_texels": (cint, [vp, u64, vp, u64]),
     "r3n_readback_joint_matrices": (cint, [vp, u32, vp, u32]),
@@ -185,6 +190,36 @@ class TextureCompactResult(ctypes.Structure):
                                          "pool_words_after", "free_ranges_after")]
 
 
+MESH_BLOCK_ZERO = 1  # R3N_MESH_BLOCK_ZERO
+
+
+class MeshBlock24(ctypes.Structure):
+    """r3n_mesh_block24"""
+    _fields_ = [("payload_offset", u64), ("words", u64), ("flags", u32), ("_pad", u32)]
+
+
+class MeshMove24(ctypes.Structure):
+    """r3n_mesh_move24"""
+    _fields_ = [("old_byte_offset", u64), ("new_byte_offset", u64), ("padded_words", u64)]
+
+
+class MeshCompactOpts(ctypes.Structure):
+    """r3n_mesh_compact_opts"""
+    _fields_ = [("max_words", u64), ("stage_words", u64)]
+
+
+class MeshCompactResult(ctypes.Structure):
+    """r3n_mesh_compact_result"""
+    _fields_ = [(name, u64) for name in ("blocks_moved", "words_moved", "passes", "kernel_launches", "full_syncs", "pool_words_before",
+                                         "pool_words_after", "free_ranges_after", "relocate_ns")]
+
+
+class MeshCounters(ctypes.Structure):
+    """r3n_mesh_counters"""
+    _fields_ = [(name, u64) for name in ("add_calls", "remove_calls", "compact_calls", "bytes_staged", "launches", "full_waits", "growths",
+                                         "blocks_live", "live_words", "pool_words", "free_ranges", "buffer_words")]
+
+
 class TextureTail16(ctypes.Structure):
     """r3n_texture_tail16"""
     _fields_ = [("dst_slot", u32), ("src_slot", u32), ("start_mip", u32), ("mip_count", u32)]
@@ -203,6 +238,7 @@ class Config(ctypes.Structure):
 # sizes the C side pins with static_asserts (rend3_amd/csrc/layouts.h)
 assert ctypes.sizeof(ShadowView272) == 272 and ctypes.sizeof(HostCamera144) == 144 and ctypes.sizeof(FrameDesc) == 152
 assert ctypes.sizeof(HostFrame) == 26712 and ctypes.sizeof(Config) == 32
+assert ctypes.sizeof(MeshBlock24) == 24 and ctypes.sizeof(MeshMove24) == 24 and ctypes.sizeof(MeshCounters) == 96
 
 _LIB = None
 

@@ -22,7 +22,7 @@ COMMON = ["layouts.h", "device_math.h", "../../include/r3n.h"]
 # translation unit -> the headers it includes (besides COMMON)
 UNITS = {
     "r3n.hip": ["texture.h", "kernels_cull.h", "kernels_raster.h", "kernels_shade.h", "comm.h", "skybox.h", "blend_sort.h", "morph.h", "normals.h", "tangents.h",
-                "vertex_block.h", "vertex_gather.h", "exact_math.h", "texel_alloc.h", "texel_compact.h", "texel_tail.h", "texture_jobs.h"],
+                "vertex_block.h", "vertex_gather.h", "exact_math.h", "texel_alloc.h", "texel_compact.h", "texel_tail.h", "texture_jobs.h", "mesh_reloc.h"],
     "shade.hip": ["texture.h", "kernels_shade.h"],
     "shade_cls.hip": ["texture.h", "kernels_shade.h"],
     "shade_ms.hip": ["texture.h", "kernels_shade.h"],
@@ -35,6 +35,7 @@ UNITS = {
     "tangents.hip": ["tangents.h", "vertex_gather.h", "exact_math.h"],
     "texture_decode.hip": ["bc7_tables.h", "bc6h_tables.h", "texture_jobs.h", "vertex_block.h", "vertex_gather.h", "exact_math.h"],
     "texture_compact.hip": ["texel_compact.h", "texel_alloc.h", "vertex_block.h", "vertex_gather.h", "exact_math.h"],
+    "mesh_reloc.hip": ["mesh_reloc.h"],
     "texture_tail.hip": ["texel_tail.h", "texel_alloc.h", "texture_jobs.h", "vertex_block.h", "vertex_gather.h", "exact_math.h"],
     "anim.hip": [],
     "selftest.hip": ["exact_math.h"],

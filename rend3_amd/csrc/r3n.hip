@@ -21,6 +21,7 @@
 #include "kernels_shade.h"
 #include "skybox.h"
 #include "blend_sort.h"
+#include "mesh_reloc.h"
 #include "morph.h"
 #include "normals.h"
 #include "tangents.h"
@@ -246,6 +247,16 @@ struct r3n_ctx {
     // shade stream keep running.  Everything enqueued after the call comes after its work, because the call has waited for it.
     hipStream_t tex_stream = nullptr;
     r3n_texture_counters tex_stats{};
+    // Pooled mesh blocks (r3n_mesh_blocks_add / _remove / r3n_mesh_compact): who owns which mesh-buffer words.  The allocator is the
+    // texel pool's (texel_alloc.h is generic over "a pool of u32 words"); the path shares the texture path's stream, staging and
+    // job-table blocks -- every call of either path ends in a wait for that stream, so neither finds the other's work in flight.
+    texel_alloc::Pool mesh_alloc;
+    std::map<uint64_t, uint64_t> mesh_blocks;  // live blocks: start word -> words (unpadded)
+    bool mesh_pooled = false;                  // the first r3n_mesh_blocks_add
+    bool mesh_appended = false;                // r3n_mesh_buffer_write wrote outside pooled mode
+    uint64_t mesh_sync_seen = 0;               // sync_serial when the mesh path last looked (parked words are clean after a full wait)
+    r3n_mesh_counters mesh_stats{};
+    hipEvent_t mesh_reloc_ev[2] = {nullptr, nullptr};  // around the relocation kernel (r3n_mesh_compact_result::relocate_ns)
     // cube textures + the skybox node (skybox.h): the bordered faces of every cube, where each cube starts, which one is bound
     struct Cube { size_t first_word; uint32_t n, srgb; };
     DevBuf cube_texels;
@@ -1038,6 +1049,8 @@ void r3n_destroy(r3n_ctx *c) {
         if (e) (void)hipEventDestroy(e);
     if (c->tex_stream) (void)hipStreamDestroy(c->tex_stream);
     for (void *p : c->tex_retired) (void)hipFree(p);
+    for (hipEvent_t ev : c->mesh_reloc_ev)
+        if (ev) (void)hipEventDestroy(ev);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
@@ -1055,12 +1068,20 @@ void *r3n_stream(r3n_ctx *c) { return c ? (void *)c->stream : nullptr; }
 // ------------------------------------------------------------------------------------------------ uploads
 int r3n_mesh_buffer_write(r3n_ctx *c, uint64_t byte_offset, const void *data, uint64_t bytes) {
     if (!c || (!data && bytes) || (byte_offset & 3u) || (bytes & 3u)) return fail(c, R3N_ERR_INVALID_ARG, "mesh write: bad args");
+    if (c->mesh_pooled) {  // pooled mode (r3n_mesh_blocks_add): in-place edits of ONE live block only -- the allocator owns the rest
+        if (!bytes) return R3N_OK;
+        const uint64_t first = byte_offset / 4u, end = first + bytes / 4u;
+        auto it = c->mesh_blocks.upper_bound(first);
+        if (it == c->mesh_blocks.begin() || end > texel_alloc::align4((--it)->first + it->second))
+            return fail(c, R3N_ERR_STATE, "mesh write: pooled mode (r3n_mesh_blocks_add) -- the range is not inside one live block");
+    }
     HIP_TRY(c, hipSetDevice(c->device));
     TRY(join_frames(c));  // frames in flight: world buffers are read by the previous frame's resolve and shadow lanes
     TRY(ensure(c, c->mesh, byte_offset + bytes, true, 0));
     if (bytes) {
         HIP_TRY(c, hipMemcpyAsync(static_cast<char *>(c->mesh.p) + byte_offset, data, bytes, hipMemcpyHostToDevice, c->stream));
         HIP_WAIT(c, hipStreamSynchronize(c->stream));  // caller owns `data` only for the duration of the call
+        if (!c->mesh_pooled) c->mesh_appended = true;  // the caller keeps its own cursor: no allocator can own these words
     }
     return R3N_OK;
 }
@@ -1927,6 +1948,226 @@ int r3n_texture_stats(r3n_ctx *c, r3n_texture_counters *out, int reset) {
         out->free_ranges = c->tex_alloc.free_ranges();
     }
     if (reset) c->tex_stats = r3n_texture_counters{};
+    return R3N_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ pooled mesh blocks
+// r3n_mesh_blocks_add / r3n_mesh_blocks_remove / r3n_mesh_compact: the streamed texture path's discipline over the mesh buffer.
+// What a frame in flight may read is never rewritten without waiting for it: FRESH words (behind the high-water mark, or a hole
+// nobody could name since the last full wait) are written on the update stream beside the frames; parked words, growth and
+// compaction go behind sync_all.  The mesh buffer is also WRITTEN by frames (skinning, morph, normals, tangents: private runs of
+// live blocks) -- never fresh words, so the rule covers them.
+
+extern "C" int r3n_internal_relocate_objects(uint32_t *objects, uint32_t capacity, const void *table, uint32_t n, hipStream_t stream);
+
+constexpr uint64_t kMeshLimitWords = 1ull << 30;  // byte offsets are 32-bit: a block ends at or below byte 2^32
+
+// a sync_all since the mesh path last looked: parked ranges are clean
+static void mesh_note_syncs(r3n_ctx *c) {
+    texture_note_syncs(c);  // (the shared scratch blocks' retired allocations are freed there)
+    if (c->mesh_sync_seen == c->sync_serial) return;
+    c->mesh_sync_seen = c->sync_serial;
+    c->mesh_alloc.release();
+}
+
+int r3n_mesh_blocks_add(r3n_ctx *c, const r3n_mesh_block24 *blocks, uint32_t n, const void *payload, uint64_t payload_bytes,
+                        uint64_t *byte_offsets_out) {
+    if (!c || (n && (!blocks || !byte_offsets_out))) return fail(c, R3N_ERR_INVALID_ARG, "mesh blocks add: null");
+    if (c->in_frame) return fail(c, R3N_ERR_STATE, "mesh blocks add: inside a frame");
+    if (c->mesh_appended) return fail(c, R3N_ERR_STATE, "mesh blocks add: the mesh buffer was written by r3n_mesh_buffer_write (the caller's own cursor owns its words)");
+    // ---- validation and planning: nothing of the context changes before both are through
+    for (uint32_t i = 0; i < n; ++i) {
+        const r3n_mesh_block24 &b = blocks[i];
+        if (b.words == 0 || b.words > kMeshLimitWords || (b.flags & ~R3N_MESH_BLOCK_ZERO))
+            return fail(c, b.words > kMeshLimitWords ? R3N_ERR_CAPACITY : R3N_ERR_INVALID_ARG, "mesh blocks add: block " + std::to_string(i) + ": words == 0, more than 2^30 words, or unknown flags");
+        if (!(b.flags & R3N_MESH_BLOCK_ZERO) &&
+            (!payload || (b.payload_offset & 3u) || b.payload_offset > payload_bytes || b.words * 4u > payload_bytes - b.payload_offset))
+            return fail(c, R3N_ERR_INVALID_ARG, "mesh blocks add: block " + std::to_string(i) + ": payload range outside the payload or not 4-byte aligned");
+    }
+    if (!n) return R3N_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (!c->tex_stream) HIP_TRY(c, hipStreamCreateWithFlags(&c->tex_stream, hipStreamNonBlocking));
+    mesh_note_syncs(c);
+    const uint64_t syncs_before = c->sync_serial;
+    texel_alloc::Pool plan = c->mesh_alloc;
+    std::vector<uint64_t> at(n);
+    bool wait = false;
+    for (uint32_t i = 0; i < n; ++i) {
+        bool merged = false;
+        at[i] = plan.alloc(blocks[i].words, &merged);
+        if (at[i] == texel_alloc::NONE || at[i] + blocks[i].words > kMeshLimitWords)
+            return fail(c, R3N_ERR_CAPACITY, "mesh blocks add: the mesh buffer would exceed 2^32 bytes");
+        wait = wait || merged;  // the words were freed since the last full wait
+    }
+    const size_t need = (size_t)plan.end() * 4u + 16u;  // (+16: the last block's padding lies inside the allocation -- compaction moves padded words)
+    const bool grow = need > c->mesh.bytes || !c->mesh.p;
+    // ---- device side
+    if (wait || grow) {
+        TRY(sync_all(c));
+        mesh_note_syncs(c);
+        plan.release();
+    }
+    if (grow) {
+        TRY(grow_texture_resident(c, c->mesh, need, (size_t)kMeshLimitWords * 4u + 16u));
+        ++c->mesh_stats.growths;
+    }
+    // ---- the host mirror follows; then copies and fills on the update stream, beside the frames
+    c->mesh_alloc = plan;
+    c->mesh_pooled = true;
+    uint64_t staged = 0, fills = 0;
+    hipError_t e = hipSuccess;
+    for (uint32_t i = 0; i < n; ++i) {
+        c->mesh_blocks[at[i]] = blocks[i].words;
+        byte_offsets_out[i] = at[i] * 4u;
+        char *dst = static_cast<char *>(c->mesh.p) + at[i] * 4u;
+        if (e != hipSuccess) continue;
+        if (blocks[i].flags & R3N_MESH_BLOCK_ZERO) {
+            e = hipMemsetAsync(dst, 0, blocks[i].words * 4u, c->tex_stream);
+            ++fills;
+        } else {
+            e = hipMemcpyAsync(dst, static_cast<const char *>(payload) + blocks[i].payload_offset, blocks[i].words * 4u, hipMemcpyHostToDevice, c->tex_stream);
+            staged += blocks[i].words * 4u;
+        }
+    }
+    const hipError_t e2 = hipStreamSynchronize(c->tex_stream);  // its own work alone; the caller owns the payload only for the duration of the call
+    ++c->main_epoch;  // the shadow lanes read the mesh buffer
+    if (e != hipSuccess) return fail(c, R3N_ERR_HIP, std::string("mesh blocks add: ") + hipGetErrorString(e));
+    if (e2 != hipSuccess) return fail(c, R3N_ERR_HIP, std::string("mesh blocks add: ") + hipGetErrorString(e2));
+    ++c->mesh_stats.add_calls;
+    c->mesh_stats.bytes_staged += staged;
+    c->mesh_stats.launches += fills;
+    c->mesh_stats.full_waits += c->sync_serial - syncs_before;
+    return R3N_OK;
+}
+
+int r3n_mesh_blocks_remove(r3n_ctx *c, const uint64_t *byte_offsets, uint32_t n) {
+    if (!c || (n && !byte_offsets)) return fail(c, R3N_ERR_INVALID_ARG, "mesh blocks remove: null");
+    if (c->in_frame) return fail(c, R3N_ERR_STATE, "mesh blocks remove: inside a frame");
+    if (!n) return R3N_OK;
+    std::vector<uint64_t> sorted(byte_offsets, byte_offsets + n);
+    std::sort(sorted.begin(), sorted.end());
+    if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) return fail(c, R3N_ERR_INVALID_ARG, "mesh blocks remove: one block named twice");
+    for (uint64_t b : sorted)
+        if ((b & 15u) || !c->mesh_blocks.count(b / 4u)) return fail(c, R3N_ERR_INVALID_ARG, "mesh blocks remove: byte offset " + std::to_string(b) + " is not the start of a live block");
+    mesh_note_syncs(c);
+    for (uint64_t b : sorted) {
+        auto it = c->mesh_blocks.find(b / 4u);
+        c->mesh_alloc.free(it->first, it->second, true);  // a frame in flight may still read the words: parked until the next full wait
+        c->mesh_blocks.erase(it);
+    }
+    ++c->mesh_stats.remove_calls;
+    return R3N_OK;
+}
+
+// Slides the live blocks towards word 0 (texel_compact.h plans, texture_compact.hip moves) and relocates the object records on the
+// device (mesh_reloc.h / mesh_reloc.hip).  The plan follows from the live blocks alone -- a wait changes none of them -- so it is
+// made first, and a call with nothing to move returns without a wait.
+int r3n_mesh_compact(r3n_ctx *c, const r3n_mesh_compact_opts *opts, r3n_mesh_compact_result *out, r3n_mesh_move24 *moves_out,
+                     uint32_t moves_capacity) {
+    if (!c) return R3N_ERR_INVALID_ARG;
+    const uint64_t max_words = opts ? opts->max_words : 0;
+    const uint64_t stage_words = opts && opts->stage_words ? opts->stage_words : texel_compact::DEFAULT_STAGE_WORDS;
+    if ((stage_words & 3u) != 0u || stage_words < texel_compact::MIN_STAGE_WORDS)
+        return fail(c, R3N_ERR_INVALID_ARG, "mesh compact: stage_words must be a multiple of 4 and at least 256");
+    if (c->in_frame) return fail(c, R3N_ERR_STATE, "mesh compact: inside a frame");
+    std::vector<texel_compact::Live> live;
+    live.reserve(c->mesh_blocks.size());
+    for (const auto &kv : c->mesh_blocks) live.push_back(texel_compact::Live{kv.first, kv.second, 0u});
+    const texel_compact::Plan plan = texel_compact::plan(live, max_words, stage_words);
+    r3n_mesh_compact_result res{};
+    res.pool_words_before = res.pool_words_after = c->mesh_alloc.end();
+    res.free_ranges_after = c->mesh_alloc.free_ranges();
+    if (plan.moves.empty()) {  // no wait, no launch; parked ranges stay parked
+        if (out) *out = res;
+        return R3N_OK;
+    }
+    if (plan.moves.size() > moves_capacity || !moves_out)
+        return fail(c, R3N_ERR_INVALID_ARG, "mesh compact: moves_capacity is smaller than the number of moves (blocks_live of r3n_mesh_stats is always enough)");
+    std::vector<uint32_t> block;
+    vertex_block::layout layout{};
+    if (!texel_compact::lay_out(plan, block, layout)) return fail(c, R3N_ERR_CAPACITY, "mesh compact: more than 2^31 wave slots of copy work in one call");
+    const texel_compact::Move &last = plan.moves.back();
+    if ((last.src + last.words) * 4u > c->mesh.bytes) return fail(c, R3N_ERR_STATE, "mesh compact: a live block ends outside the mesh buffer");
+    // the relocation table rides behind the plan's table in the same device block (16-byte aligned), one copy for both
+    std::vector<mesh_reloc::Move> rmoves;
+    rmoves.reserve(plan.moves.size());
+    for (const texel_compact::Move &m : plan.moves) rmoves.push_back(mesh_reloc::Move{m.src, m.dst, m.words});
+    std::vector<mesh_reloc::Entry> table;
+    if (!mesh_reloc::build_table(rmoves, table)) return fail(c, R3N_ERR_STATE, "mesh compact: a move outside 32-bit word addresses");
+    block.resize((block.size() + 3u) & ~(size_t)3u, 0u);
+    const size_t table_at = block.size();
+    block.resize(table_at + table.size() * 4u);
+    std::memcpy(block.data() + table_at, table.data(), table.size() * sizeof(mesh_reloc::Entry));
+
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (!c->tex_stream) HIP_TRY(c, hipStreamCreateWithFlags(&c->tex_stream, hipStreamNonBlocking));
+    const uint64_t syncs_before = c->sync_serial;
+    TRY(sync_all(c));  // a frame in flight may read every word that moves, every word moved over, and every record that is patched
+    mesh_note_syncs(c);
+    TRY(grow_texture_scratch(c, c->tex_stage, (size_t)std::max<uint64_t>(plan.scratch_words, 1) * 4u));
+    TRY(grow_texture_scratch(c, c->tex_jobs, block.size() * 4u));
+
+    // ---- the passes, then the relocation, in stream order on the update stream
+    uint32_t *pool = c->mesh.as<uint32_t>(), *scratch = c->tex_stage.as<uint32_t>();
+    const uint32_t *jobs = c->tex_jobs.as<uint32_t>();
+    hipError_t e = hipMemcpyAsync(c->tex_jobs.p, block.data(), block.size() * 4u, hipMemcpyHostToDevice, c->tex_stream);
+    for (size_t i = 0; i < plan.launches.size() && e == hipSuccess; ++i) {
+        const texel_compact::Launch &l = plan.launches[i];
+        e = (hipError_t)r3n_internal_move_segments(jobs, layout.o_first, layout.o_inst, (uint32_t)l.first_wave, (uint32_t)l.waves,
+                                                   l.kind == texel_compact::SCATTER ? scratch : pool, l.kind == texel_compact::GATHER ? scratch : pool,
+                                                   c->tex_stream);
+    }
+    uint64_t launches = plan.launches.size();
+    bool relocated = false;
+    if (e == hipSuccess && c->capacity && c->objects.p) {
+        for (hipEvent_t &ev : c->mesh_reloc_ev)
+            if (!ev && e == hipSuccess) e = hipEventCreate(&ev);
+        if (e == hipSuccess) e = hipEventRecord(c->mesh_reloc_ev[0], c->tex_stream);
+        if (e == hipSuccess) e = (hipError_t)r3n_internal_relocate_objects(c->objects.as<uint32_t>(), c->capacity, jobs + table_at, (uint32_t)table.size(), c->tex_stream);
+        if (e == hipSuccess) e = hipEventRecord(c->mesh_reloc_ev[1], c->tex_stream);
+        relocated = e == hipSuccess;
+        ++launches;
+    }
+    const hipError_t e2 = hipStreamSynchronize(c->tex_stream);  // the add path relies on it: everything that rewrote the buffer ended in a wait
+    if (relocated && e2 == hipSuccess) {
+        float ms = 0.0f;
+        if (hipEventElapsedTime(&ms, c->mesh_reloc_ev[0], c->mesh_reloc_ev[1]) == hipSuccess) res.relocate_ns = (uint64_t)((double)ms * 1e6);
+    }
+    if (e != hipSuccess) return fail(c, R3N_ERR_HIP, std::string("mesh compact: ") + hipGetErrorString(e));
+    if (e2 != hipSuccess) return fail(c, R3N_ERR_HIP, std::string("mesh compact: ") + hipGetErrorString(e2));
+    texel_compact::rebuild(c->mesh_alloc, plan);
+    c->mesh_blocks.clear();
+    for (const texel_compact::Live &t : plan.live) c->mesh_blocks[t.start] = t.words;
+    c->h_skin_inputs.clear();  // cached skeleton records name runs that moved: the next r3n_skinning uploads the caller's again
+    ++c->main_epoch;           // the shadow lanes read the mesh buffer and the records
+    for (size_t i = 0; i < plan.moves.size(); ++i)
+        moves_out[i] = r3n_mesh_move24{plan.moves[i].src * 4u, plan.moves[i].dst * 4u, plan.moves[i].words};
+    res.blocks_moved = plan.moves.size();
+    res.words_moved = plan.words_moved;
+    res.passes = plan.passes.size();
+    res.kernel_launches = launches;
+    res.full_syncs = c->sync_serial - syncs_before;
+    res.pool_words_after = c->mesh_alloc.end();
+    res.free_ranges_after = c->mesh_alloc.free_ranges();
+    if (out) *out = res;
+    ++c->mesh_stats.compact_calls;
+    c->mesh_stats.launches += launches;
+    c->mesh_stats.full_waits += res.full_syncs;
+    return R3N_OK;
+}
+
+int r3n_mesh_stats(r3n_ctx *c, r3n_mesh_counters *out, int reset) {
+    if (!c || (!out && !reset)) return fail(c, R3N_ERR_INVALID_ARG, "mesh stats: null");
+    if (out) {
+        *out = c->mesh_stats;
+        out->blocks_live = c->mesh_blocks.size();
+        out->live_words = 0;
+        for (const auto &kv : c->mesh_blocks) out->live_words += kv.second;
+        out->pool_words = c->mesh_alloc.end();
+        out->free_ranges = c->mesh_alloc.free_ranges();
+        out->buffer_words = c->mesh.bytes / 4u;
+    }
+    if (reset) c->mesh_stats = r3n_mesh_counters{};
     return R3N_OK;
 }
 
@@ -3838,6 +4079,13 @@ int r3n_readback_baked(r3n_ctx *c, r3n_camera cam, float *out, uint32_t capacity
 int r3n_readback_mesh(r3n_ctx *c, uint64_t byte_offset, void *dst, uint64_t bytes) {
     if (!c || !dst || byte_offset + bytes > c->mesh.bytes) return fail(c, R3N_ERR_INVALID_ARG, "readback_mesh: range outside the mesh buffer");
     return d2h(c, dst, static_cast<char *>(c->mesh.p) + byte_offset, bytes);
+}
+
+int r3n_readback_objects(r3n_ctx *c, uint32_t first_slot, r3n_object128 *records, uint32_t n) {
+    if (!c || (n && !records) || (uint64_t)first_slot + n > c->capacity || (uint64_t)c->capacity * sizeof(r3n_object128) > c->objects.bytes)
+        return fail(c, R3N_ERR_INVALID_ARG, "readback_objects: range outside the object buffer");
+    if (!n) return R3N_OK;
+    return d2h(c, records, c->objects.as<r3n_object128>() + first_slot, (size_t)n * sizeof(r3n_object128));
 }
 
 int r3n_readback_joint_matrices(r3n_ctx *c, uint32_t first, float *dst, uint32_t n) {

@@ -186,7 +186,41 @@ class CameraSpecifier:
 
 class _Mesh:
     __slots__ = ("attr_off", "first_index", "index_count", "centre", "radius", "vertex_count", "joint_off", "weight_off",
-                 "n_targets", "delta_off", "reach", "morph_weights", "adjacency_off", "left_handed", "morph_normals", "morph_tangents")
+                 "n_targets", "delta_off", "reach", "morph_weights", "adjacency_off", "left_handed", "morph_normals", "morph_tangents",
+                 "block")  # block: mesh_upload="stream": byte offset of the mesh's pooled block (None in "append" mode)
+
+
+def relocate_offsets(values, moves, words=False):
+    """The rule of rend3_amd/csrc/mesh_reloc.h, restated for the host's mirrors after r3n_mesh_compact.  values: mesh-buffer
+    addresses (byte offsets; words=True: word addresses), any shape; moves: rows (old byte offset, new byte offset, padded
+    words).  An address whose word lies in [old, old + padded words) of a move follows it by old - new; every other address,
+    INVALID always, is unchanged; a byte offset keeps its low two bits.  Returns a uint32 array of the same shape."""
+    v = np.asarray(values, dtype=np.uint32)
+    moves = np.asarray(moves, dtype=np.uint64).reshape(-1, 3)
+    if not len(moves) or not v.size:
+        return v.copy()
+    moves = moves[np.argsort(moves[:, 0])]
+    src = moves[:, 0] // 4
+    end, shift = src + moves[:, 2], src - moves[:, 1] // 4
+    word = v.astype(np.uint64) if words else v.astype(np.uint64) >> np.uint64(2)
+    low = np.zeros_like(word) if words else v.astype(np.uint64) & np.uint64(3)
+    e = np.searchsorted(src, word, side="right").astype(np.int64) - 1  # the last move that starts at or below the word
+    k = np.maximum(e, 0)
+    hit = (e >= 0) & (word < end[k]) & (v != INVALID)
+    moved = word - np.where(hit, shift[k], np.uint64(0))
+    out = moved if words else (moved << np.uint64(2)) | low
+    return np.where(hit, out, v.astype(np.uint64)).astype(np.uint32)
+
+
+def _shift_mesh(m, fn):
+    """Every mesh-buffer address a _Mesh holds through fn(byte offset) -> byte offset: the block's start at add_mesh, the moves of
+    a compaction afterwards.  INVALID stays."""
+    def f(off):
+        return INVALID if off == INVALID else int(fn(int(off)))
+    m.attr_off = [f(o) for o in m.attr_off]
+    m.joint_off, m.weight_off, m.adjacency_off = f(m.joint_off), f(m.weight_off), f(m.adjacency_off)
+    m.delta_off = [f(o) for o in m.delta_off]
+    m.first_index = f(4 * m.first_index) // 4
 
 
 class EvalOutput:
@@ -201,7 +235,7 @@ class Renderer:
     """World bookkeeping feeding the object/mesh/material/light buffers of the C ABI."""
 
     def __init__(self, handedness=host.LEFT, aspect_ratio=None, device=0, max_big_items=None, blend_sort="host", texture_upload="whole",
-                 texture_compact=None):
+                 texture_compact=None, mesh_upload="append", mesh_compact=None):
         self.lib = _ffi.lib()
         if blend_sort not in ("host", "gpu"):
             raise ValueError("blend_sort: 'host' or 'gpu'")
@@ -221,6 +255,19 @@ class Renderer:
         if texture_compact is not None and not (0.0 < float(texture_compact) <= 1.0):
             raise ValueError("texture_compact: None or a fraction in (0, 1]")
         self._texture_compact = None if texture_compact is None else float(texture_compact)
+        # how mesh words reach the device: "append" = behind one cursor through r3n_mesh_buffer_write, nothing is ever given back;
+        # "stream" = every mesh, skeleton and morph instance is ONE pooled block (r3n_mesh_blocks_add / _remove, MeshManager::add /
+        # remove), removable one by one, and compact_meshes slides the live blocks together on the GPU
+        if mesh_upload not in ("append", "stream"):
+            raise ValueError("mesh_upload: 'append' or 'stream'")
+        self._mesh_upload = mesh_upload
+        # "stream": None = the mesh buffer is never compacted by itself; a fraction f in (0, 1] = r3n_mesh_compact in
+        # evaluate_instructions when more than f of the buffer below its high-water mark is holes (the rule of texture_compact)
+        if mesh_compact is not None and not (0.0 < float(mesh_compact) <= 1.0):
+            raise ValueError("mesh_compact: None or a fraction in (0, 1]")
+        self._mesh_compact = None if mesh_compact is None else float(mesh_compact)
+        self._mesh_edits = False  # "stream": a block was added or removed since the last look at the holes
+        self.object_writes = 0    # r3n_objects_write calls that carried records (the tests' "no resend" counts them)
         # where the transparent pass's back-to-front order is sorted: "host" = host.blend_draw_order + r3n_blend_order_write every
         # frame; "gpu" = the blend set goes up when the world changes (r3n_blend_objects_write), r3n_blend_sort orders it per frame
         self.blend_sort = blend_sort
@@ -350,7 +397,8 @@ class Renderer:
         m = _Mesh()
         m.attr_off = [INVALID] * 6
         chunks = []
-        cursor = self.mesh_cursor
+        stream = self._mesh_upload == "stream"
+        cursor = 0 if stream else self.mesh_cursor  # "stream": offsets inside the blob first; the block's start is added below
 
         def push(words):
             nonlocal cursor
@@ -404,9 +452,14 @@ class Renderer:
                     push(np.zeros(4 - cursor % 4, dtype=np.uint32))
                 m.adjacency_off = 4 * push(adjacency)
         blob = np.concatenate(chunks)
-        self._check(self.lib.r3n_mesh_buffer_write(self.ctx, 4 * self.mesh_cursor, _ffi.ptr(blob), blob.nbytes),
-                    "r3n_mesh_buffer_write")
-        self.mesh_cursor = cursor
+        m.block = None
+        if stream:  # one block for the whole blob: its start is a multiple of 16 bytes, so every alignment inside is kept
+            m.block = self._add_mesh_blocks([blob])[0]
+            _shift_mesh(m, lambda off: off + m.block)
+        else:
+            self._check(self.lib.r3n_mesh_buffer_write(self.ctx, 4 * self.mesh_cursor, _ffi.ptr(blob), blob.nbytes),
+                        "r3n_mesh_buffer_write")
+            self.mesh_cursor = cursor
         m.centre, m.radius = host.bounding_sphere_from_mesh(positions)
         self.meshes.append(m)
         return len(self.meshes) - 1
@@ -421,6 +474,8 @@ class Renderer:
         if morph is not None and self.morphs[morph]["mesh"] != mesh:
             raise ValueError("add_skeleton: the morph instance belongs to another mesh")
         out_off = [INVALID] * 3
+        if self._mesh_upload == "stream":
+            return self._add_skeletons_stream(mesh, [joint_matrices], morph)[0]
         for a in range(3):  # private position / normal / tangent copies (skeleton.rs:110-113)
             if m.attr_off[a] != INVALID:
                 out_off[a] = 4 * self.mesh_cursor
@@ -428,13 +483,15 @@ class Renderer:
                 self._check(self.lib.r3n_mesh_buffer_write(self.ctx, out_off[a], _ffi.ptr(zeros), zeros.nbytes), "r3n_mesh_buffer_write")
                 self.mesh_cursor += len(zeros)
         self.skeletons.append(dict(mesh=mesh, out_off=out_off, matrices=np.ascontiguousarray(joint_matrices, dtype=f32).reshape(-1, 16),
-                                   morph=morph))
+                                   morph=morph, block=None))
         self._skin_inputs = None
         return len(self.skeletons) - 1
 
     def add_skeletons_bulk(self, mesh, joint_matrices_per_skeleton):
         """Many skeletons of one mesh (config 5): one zero-fill upload for all private output ranges."""
         m = self.meshes[mesh]
+        if self._mesh_upload == "stream":
+            return self._add_skeletons_stream(mesh, joint_matrices_per_skeleton, None)
         n = len(joint_matrices_per_skeleton)
         n_attr = sum(1 for a in range(3) if m.attr_off[a] != INVALID)
         words = 3 * m.vertex_count
@@ -449,10 +506,27 @@ class Renderer:
                 if m.attr_off[a] != INVALID:
                     out_off[a] = 4 * (base + (i * n_attr + k) * words)
                     k += 1
-            self.skeletons.append(dict(mesh=mesh, out_off=out_off, morph=None,
+            self.skeletons.append(dict(mesh=mesh, out_off=out_off, morph=None, block=None,
                                        matrices=np.ascontiguousarray(joint_matrices_per_skeleton[i], dtype=f32).reshape(-1, 16)))
         self._skin_inputs = None
         return list(range(first, first + n))
+
+    def _add_skeletons_stream(self, mesh, joint_matrices_per_skeleton, morph):
+        """mesh_upload="stream": ONE r3n_mesh_blocks_add with one zero-filled block per skeleton (its private runs back to back), so
+        that each can be retired on its own (SkeletonManager::remove, skeleton.rs:139-147)."""
+        m = self.meshes[mesh]
+        attrs = [a for a in range(3) if m.attr_off[a] != INVALID]
+        words = 3 * m.vertex_count
+        blocks = self._add_mesh_blocks([len(attrs) * words] * len(joint_matrices_per_skeleton))
+        first = len(self.skeletons)
+        for block, mats in zip(blocks, joint_matrices_per_skeleton):
+            out_off = [INVALID] * 3
+            for k, a in enumerate(attrs):
+                out_off[a] = block + 4 * k * words
+            self.skeletons.append(dict(mesh=mesh, out_off=out_off, morph=morph, block=block,
+                                       matrices=np.ascontiguousarray(mats, dtype=f32).reshape(-1, 16)))
+        self._skin_inputs = None
+        return list(range(first, first + len(blocks)))
 
     # ---- morph targets (glTF 2.0 section 3.7.2.2; DESIGN.md section 2 "Morph targets")
     def add_morph_instance(self, mesh, weights=None):
@@ -471,16 +545,22 @@ class Renderer:
         # morph_tangents="recompute" one
         attrs = [a for a in range(3) if m.delta_off[a] != INVALID or (a == 1 and m.morph_normals) or (a == 2 and m.morph_tangents)]
         words = (3 * m.vertex_count + 3) & ~3  # a run, padded to 16 bytes
-        base = (self.mesh_cursor + 3) & ~3
-        zeros = np.zeros(max(n * len(attrs) * words, 4), dtype=np.uint32)
-        self._check(self.lib.r3n_mesh_buffer_write(self.ctx, 4 * base, _ffi.ptr(zeros), zeros.nbytes), "r3n_mesh_buffer_write")
-        self.mesh_cursor = base + len(zeros)
+        if self._mesh_upload == "stream":  # ONE call, one zero-filled block per instance: each can be retired on its own
+            blocks = self._add_mesh_blocks([max(len(attrs) * words, 4)] * n)
+            starts = [b // 4 for b in blocks]
+        else:
+            base = (self.mesh_cursor + 3) & ~3
+            zeros = np.zeros(max(n * len(attrs) * words, 4), dtype=np.uint32)
+            self._check(self.lib.r3n_mesh_buffer_write(self.ctx, 4 * base, _ffi.ptr(zeros), zeros.nbytes), "r3n_mesh_buffer_write")
+            self.mesh_cursor = base + len(zeros)
+            blocks, starts = [None] * n, [base + i * len(attrs) * words for i in range(n)]
         first = len(self.morphs)
         for i, w in enumerate(weights_per_instance):
             out_off = [INVALID] * 3
             for k, a in enumerate(attrs):
-                out_off[a] = 4 * (base + (i * len(attrs) + k) * words)
-            self.morphs.append(dict(mesh=mesh, out_off=out_off, weights=self._morph_weights(m, m.morph_weights if w is None else w), objects=[]))
+                out_off[a] = 4 * (starts[i] + k * words)
+            self.morphs.append(dict(mesh=mesh, out_off=out_off, weights=self._morph_weights(m, m.morph_weights if w is None else w), objects=[],
+                                    block=blocks[i]))
             self._morph_dirty.add(first + i)
         return list(range(first, first + n))
 
@@ -596,15 +676,17 @@ class Renderer:
         state = self._pose_state
         rq = np.zeros(len(state), dtype=[("clip", np.uint32), ("time", np.float32), ("base", np.uint32), ("pad", np.uint32)])
         for i, (sk, (clip, time)) in enumerate(sorted(state.items())):
-            rq[i] = (clip, time, int(self._skin_inputs[sk][8]), 0)
+            rq[i] = (clip, time, int(self._skin_inputs[self._skin_row[sk]][8]), 0)
         return rq
 
     def skinning_buffers(self):
         """build_gpu_skinning_input_buffers (rend3-routine/src/skinning.rs:54-139)"""
         if getattr(self, "_skin_inputs", None) is None:
-            inputs = np.zeros((len(self.skeletons), 10), dtype=np.uint32)
+            live = [(h, sk) for h, sk in enumerate(self.skeletons) if sk is not None]  # (remove_skeleton leaves None: handles are not reused)
+            inputs = np.zeros((len(live), 10), dtype=np.uint32)
+            self._skin_row = {h: i for i, (h, _) in enumerate(live)}
             base = 0
-            for i, sk in enumerate(self.skeletons):
+            for i, (_, sk) in enumerate(live):
                 m = self.meshes[sk["mesh"]]
                 src = list(m.attr_off[:3])
                 if sk["morph"] is not None:  # morph, then skin: the base runs are the morph instance's outputs where it has some
@@ -613,8 +695,159 @@ class Renderer:
                              sk["out_off"][1], sk["out_off"][2], base, m.vertex_count]
                 base += len(sk["matrices"])
             self._skin_inputs = inputs
-        mats = np.ascontiguousarray(np.concatenate([sk["matrices"] for sk in self.skeletons]))
+        mats = np.ascontiguousarray(np.concatenate([sk["matrices"] for sk in self.skeletons if sk is not None]))
         return self._skin_inputs, mats
+
+    def _has_skeletons(self):
+        return any(sk is not None for sk in self.skeletons)
+
+    # ---- pooled mesh blocks (mesh_upload="stream"; MeshManager::add / remove, rend3/src/managers/mesh.rs:123-211)
+    @property
+    def mesh_upload(self):
+        return self._mesh_upload
+
+    @mesh_upload.setter
+    def mesh_upload(self, mode):
+        if mode not in ("append", "stream"):
+            raise ValueError("mesh_upload: 'append' or 'stream'")
+        if mode != self._mesh_upload and (self.meshes or self.skeletons or self.morphs):
+            raise ValueError("mesh_upload cannot change once meshes exist")
+        self._mesh_upload = mode
+
+    @property
+    def mesh_compact(self):
+        return self._mesh_compact
+
+    @mesh_compact.setter
+    def mesh_compact(self, fraction):
+        if fraction is not None and not (0.0 < float(fraction) <= 1.0):
+            raise ValueError("mesh_compact: None or a fraction in (0, 1]")
+        self._mesh_compact = None if fraction is None else float(fraction)
+
+    def _add_mesh_blocks(self, items):
+        """ONE r3n_mesh_blocks_add: items are uint32 arrays (uploaded) or word counts (zero-filled on the device).  Returns the
+        blocks' byte offsets."""
+        recs = (_ffi.MeshBlock24 * len(items))()
+        chunks, at = [], 0
+        for i, it in enumerate(items):
+            if isinstance(it, np.ndarray):
+                recs[i].payload_offset, recs[i].words, recs[i].flags = at, len(it), 0
+                chunks.append(np.ascontiguousarray(it, dtype=np.uint32))
+                at += 4 * len(it)
+            else:
+                recs[i].payload_offset, recs[i].words, recs[i].flags = 0, int(it), _ffi.MESH_BLOCK_ZERO
+        payload = np.concatenate(chunks) if chunks else None
+        out = np.zeros(len(items), dtype=np.uint64)
+        self._check(self.lib.r3n_mesh_blocks_add(self.ctx, recs, len(items), _ffi.ptr(payload), at, _ffi.ptr(out)), "r3n_mesh_blocks_add")
+        self._mesh_edits = True
+        return [int(b) for b in out]
+
+    def _remove_mesh_block(self, what, block):
+        if self._mesh_upload != "stream":
+            raise ValueError(f"{what} needs Renderer(mesh_upload='stream'): the append path gives no words back")
+        offs = np.array([block], dtype=np.uint64)
+        self._check(self.lib.r3n_mesh_blocks_remove(self.ctx, _ffi.ptr(offs), 1), "r3n_mesh_blocks_remove")
+        self._mesh_edits = True
+
+    def _enabled_objects(self):
+        return [meta for meta in self.object_meta.values() if meta.get("enabled")]
+
+    def remove_mesh(self, h):
+        """MeshManager::remove (mesh.rs:197-211): the mesh's words are given back and may be reused.  ValueError while an enabled
+        object, a skeleton or a morph instance still names the handle (the reference keeps a mesh alive while anything holds its
+        handle).  Handles are not reused.  mesh_upload="stream" only."""
+        if self._mesh_upload != "stream":
+            raise ValueError("remove_mesh needs Renderer(mesh_upload='stream'): the append path gives no words back")
+        if self.meshes[h] is None:
+            raise ValueError("remove_mesh: the mesh was removed already")
+        if (any(meta.get("mesh") == h for meta in self._enabled_objects()) or any(sk is not None and sk["mesh"] == h for sk in self.skeletons)
+                or any(inst is not None and inst["mesh"] == h for inst in self.morphs)):
+            raise ValueError("remove_mesh: an enabled object, a skeleton or a morph instance still names the mesh")
+        self._remove_mesh_block("remove_mesh", self.meshes[h].block)
+        self.meshes[h] = None
+
+    def remove_skeleton(self, h):
+        """SkeletonManager::remove (skeleton.rs:139-147): the skeleton's private runs are given back.  ValueError while an enabled
+        object is bound to it.  mesh_upload="stream" only."""
+        if self._mesh_upload != "stream":
+            raise ValueError("remove_skeleton needs Renderer(mesh_upload='stream'): the append path gives no words back")
+        if self.skeletons[h] is None:
+            raise ValueError("remove_skeleton: the skeleton was removed already")
+        if any(meta.get("skeleton") == h for meta in self._enabled_objects()):
+            raise ValueError("remove_skeleton: an enabled object is still bound to the skeleton")
+        self._remove_mesh_block("remove_skeleton", self.skeletons[h]["block"])
+        self.skeletons[h] = None
+        self._pose_state.pop(h, None)
+        self._skin_inputs = None
+        self.world_version += 1
+
+    def remove_morph_instance(self, h):
+        """The instance's private runs are given back.  ValueError while an enabled object or a skeleton is bound to it.
+        mesh_upload="stream" only."""
+        if self._mesh_upload != "stream":
+            raise ValueError("remove_morph_instance needs Renderer(mesh_upload='stream'): the append path gives no words back")
+        if self.morphs[h] is None:
+            raise ValueError("remove_morph_instance: the instance was removed already")
+        if (any(h in (meta.get("morph"), meta.get("morph_instance")) for meta in self._enabled_objects())
+                or any(sk is not None and sk["morph"] == h for sk in self.skeletons)):
+            raise ValueError("remove_morph_instance: an enabled object or a skeleton is still bound to the instance")
+        self._remove_mesh_block("remove_morph_instance", self.morphs[h]["block"])
+        self.morphs[h] = None
+        self._morph_dirty.discard(h)
+        self.world_version += 1
+
+    def compact_meshes(self, max_words=0, stage_words=0):
+        """Slides the live mesh blocks towards word 0 on the GPU and patches the object records there (r3n_mesh_compact): no record
+        is re-sent.  Afterwards every mirror of a mesh-buffer address the renderer holds follows the returned moves through
+        relocate_offsets -- the meshes, the skeletons' and morph instances' private runs, the cached skinning inputs (the morph,
+        normals and tangents inputs are built from those per call) and the records still waiting in the dirty-object mirror.
+        max_words / stage_words: as compact_textures.  mesh_upload="stream" only.  Returns r3n_mesh_compact_result as a dict,
+        plus moves = uint64[n, 3] rows (old byte offset, new byte offset, padded words)."""
+        if self._mesh_upload != "stream":
+            raise ValueError("compact_meshes needs Renderer(mesh_upload='stream'): the append path lays its buffer out densely")
+        capacity = max(self.mesh_stats()["blocks_live"], 1)
+        moves = (_ffi.MeshMove24 * capacity)()
+        opts = _ffi.MeshCompactOpts(max_words=int(max_words), stage_words=int(stage_words))
+        out = _ffi.MeshCompactResult()
+        self._check(self.lib.r3n_mesh_compact(self.ctx, ctypes.byref(opts), ctypes.byref(out), moves, capacity), "r3n_mesh_compact")
+        res = {name: int(getattr(out, name)) for name, _ in _ffi.MeshCompactResult._fields_}
+        res["moves"] = np.array([(mv.old_byte_offset, mv.new_byte_offset, mv.padded_words) for mv in moves[:res["blocks_moved"]]],
+                                dtype=np.uint64).reshape(-1, 3)
+        if res["blocks_moved"]:
+            self._apply_mesh_moves(res["moves"])
+        return res
+
+    def _apply_mesh_moves(self, moves):
+        def one(off):
+            return int(relocate_offsets(np.uint32(off), moves))
+        for m in self.meshes:
+            if m is not None:
+                _shift_mesh(m, one)
+                m.block = one(m.block)
+        for entry in list(self.skeletons) + list(self.morphs):
+            if entry is not None:
+                entry["out_off"] = [int(o) for o in relocate_offsets(entry["out_off"], moves)]
+                entry["block"] = one(entry["block"])
+        if getattr(self, "_skin_inputs", None) is not None:  # columns 0..7 are byte offsets (r3n_skinning_input40)
+            self._skin_inputs[:, :8] = relocate_offsets(self._skin_inputs[:, :8], moves)
+        # records not sent yet go up with the new addresses; the device has patched the ones it holds
+        for rec in self.dirty_objects.values():
+            rec[20] = relocate_offsets(rec[20], moves, words=True)
+            rec[23:29] = relocate_offsets(rec[23:29], moves)
+
+    def mesh_stats(self, reset=False):
+        """Counters of the pooled mesh path (r3n_mesh_stats) as a dict; reset=True zeroes them after the read."""
+        out = _ffi.MeshCounters()
+        self._check(self.lib.r3n_mesh_stats(self.ctx, ctypes.byref(out), 1 if reset else 0), "r3n_mesh_stats")
+        return {name: int(getattr(out, name)) for name, _ in _ffi.MeshCounters._fields_}
+
+    def readback_objects(self, first_slot=0, n=None):
+        """r3n_readback_objects: the 128-byte records as the device holds them, uint32[n, 32]."""
+        n = self.capacity - first_slot if n is None else int(n)
+        out = np.zeros((max(n, 1), 32), dtype=np.uint32)
+        if n:
+            self._check(self.lib.r3n_readback_objects(self.ctx, int(first_slot), _ffi.ptr(out), n), "r3n_readback_objects")
+        return out[:n]
 
     @property
     def texture_upload(self):
@@ -911,6 +1144,7 @@ class Renderer:
             return
         slots = np.array([h for h, _ in items], dtype=np.uint32)
         recs = np.ascontiguousarray(np.stack([r for _, r in items]) if items else np.zeros((0, 32), dtype=np.uint32))
+        self.object_writes += 1 if len(slots) else 0
         self._check(self.lib.r3n_objects_write(self.ctx, _ffi.ptr(slots) if len(slots) else None,
                                                _ffi.ptr(recs) if len(slots) else None, len(slots), self.capacity),
                     "r3n_objects_write")
@@ -925,6 +1159,7 @@ class Renderer:
         slots = np.ascontiguousarray(slots, dtype=np.uint32).reshape(-1)
         records = np.ascontiguousarray(records, dtype=np.uint32).reshape(len(slots), 32)
         if len(slots):
+            self.object_writes += 1
             self._check(self.lib.r3n_objects_write(self.ctx, _ffi.ptr(slots), _ffi.ptr(records), len(slots), int(capacity)), "r3n_objects_write")
         self.capacity = self._capacity_sent = int(capacity)
         self.object_meta = {int(h): dict(enabled=True, material=int(m), location=np.asarray(loc, dtype=f32).copy())
@@ -1076,7 +1311,17 @@ class Renderer:
     def evaluate_instructions(self):
         self._flush_textures(before_frame=True)
         self._flush_cubes()
+        self._compact_meshes_before_frame()
         return self._evaluate_instructions()
+
+    def _compact_meshes_before_frame(self):
+        """mesh_compact=f: after a block was added or removed, r3n_mesh_compact when more than f of the buffer below its mark is holes"""
+        if self._mesh_compact is None or not self._mesh_edits:
+            return
+        self._mesh_edits = False
+        st = self.mesh_stats()
+        if st["pool_words"] - st["live_words"] > self._mesh_compact * st["pool_words"]:
+            self.compact_meshes()
 
     def _flush_objects(self):
         """ObjectManager::evaluate (object.rs:344-364): last frame's removals become real, dirty records are scattered."""
@@ -1201,6 +1446,7 @@ class Renderer:
             d.directional_buffer = base + _ffi.HostFrame.directional_buffer.offset
         self._flush_textures(before_frame=True)
         self._flush_cubes()
+        self._compact_meshes_before_frame()
         self._flush_objects()
         self._flush_morphs()  # morph, then skin (the skinning node is inside r3n_render_frame)
         cam, fr, d = fc["cam"], fc["frame"], fc["desc"]
@@ -1253,7 +1499,7 @@ class Renderer:
             d.flags |= _ffi.FRAME_SHADOW_MASK
             d.shadow_view_mask = sum(1 << v for v in range(n_views) if exchange.owns_shadow_view(v))
         keep = None
-        if self.skeletons:  # skinning (base.rs:145, skinning.rs:211-226)
+        if self._has_skeletons():  # skinning (base.rs:145, skinning.rs:211-226)
             sk_in, sk_m = self.skinning_buffers()
             poses = self._pose_requests()
             if len(poses):
@@ -1364,7 +1610,7 @@ class Renderer:
 
     def readback_joint_matrices(self):
         """The joint matrices the last skinning pass read (host-provided and GPU-posed), (n, 16) f32."""
-        n = sum(len(sk["matrices"]) for sk in self.skeletons)
+        n = sum(len(sk["matrices"]) for sk in self.skeletons if sk is not None)
         out = np.zeros((max(n, 1), 16), dtype=f32)
         if n:
             self._check(self.lib.r3n_readback_joint_matrices(self.ctx, 0, _ffi.ptr(out), n), "r3n_readback_joint_matrices")
@@ -1613,7 +1859,7 @@ class BaseRenderGraph:
         graph.add_node("Morph", lambda r, _ev: r._flush_morphs())
         # skinning (base.rs:145, skinning.rs:211-226)
         def skin(r, _ev):
-            if r.skeletons:
+            if r._has_skeletons():
                 sk_in, sk_m = r.skinning_buffers()
                 poses = r._pose_requests()
                 if len(poses):

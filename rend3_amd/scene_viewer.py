@@ -93,6 +93,12 @@ def add_arguments(ap):
     ap.add_argument("--texture-upload", choices=("whole", "stream"), default="whole",
                     help="how 2D textures reach the device: whole = the bindless array is re-sent when it changed, stream = single "
                          "entries are added and removed in place (r3n_textures_update), as the reference's TextureManager does")
+    ap.add_argument("--mesh-upload", choices=("append", "stream"), default="append",
+                    help="how mesh words reach the device: append = behind one cursor, nothing is given back; stream = pooled blocks "
+                         "(r3n_mesh_blocks_add / _remove), as the reference's MeshManager sub-allocates and frees ranges")
+    ap.add_argument("--mesh-compact", type=float, default=None, metavar="F",
+                    help="with --mesh-upload stream: compact the mesh buffer on the GPU (r3n_mesh_compact) in front of a frame when more "
+                         "than the fraction F in (0, 1] of it is holes; default: never")
     ap.add_argument("--morph-normals", choices=("base", "recompute"), default="base",
                     help="normals of morphed primitives without NORMAL: base = those of the bind shape under any weights, "
                          "recompute = recomputed from the morphed positions on the GPU (r3n_vertex_normals)")
@@ -121,7 +127,8 @@ def settings_from(args):
                 blend_sort=getattr(args, "blend_sort", "host"), morph_normals=getattr(args, "morph_normals", "base"),
                 build_tangents=getattr(args, "build_tangents", False), morph_tangents=getattr(args, "morph_tangents", "base"),
                 texture_upload=getattr(args, "texture_upload", "whole"), texture_compact=getattr(args, "texture_compact", None),
-                texture_skip_mips=getattr(args, "texture_skip_mips", 0))
+                texture_skip_mips=getattr(args, "texture_skip_mips", 0),
+                mesh_upload=getattr(args, "mesh_upload", "append"), mesh_compact=getattr(args, "mesh_compact", None))
 
 
 def default_settings(**over):
@@ -184,6 +191,14 @@ def build(r, hm, mk, settings):
             raise ValueError("--texture-skip-mips: a level count >= 0")
         if settings.get("texture_upload", "whole") != "stream":
             raise ValueError("--texture-skip-mips needs --texture-upload stream: the whole-array path keeps no resident pool to copy from")
+    if settings.get("mesh_upload", "append") != "append":  # (a renderer without pooled mesh blocks fails here)
+        if not hasattr(r, "mesh_upload"):
+            raise ValueError("--mesh-upload stream: this renderer appends behind one cursor")
+        r.mesh_upload = settings["mesh_upload"]
+    if settings.get("mesh_compact") is not None:
+        if settings.get("mesh_upload", "append") != "stream":
+            raise ValueError("--mesh-compact needs --mesh-upload stream: the append path lays its buffer out densely")
+        r.mesh_compact = settings["mesh_compact"]
     light = None
     if settings["directional_light"] is not None:  # setup (mod.rs:463-472)
         light = r.add_directional_light(color=(1.0, 1.0, 1.0), intensity=settings["directional_light_intensity"],
