@@ -577,7 +577,9 @@ int r3n_set_output_format(r3n_ctx *ctx, uint32_t format);
  * restatement of skinning.wgsl:37-94.  MFMA (opt-in): the joint-matrix x vertex-block contraction on the matrix cores
  * (v_mfma_f32_16x16x4_f32: four joint matrices x 16 vertices per instruction), for rigs of at most FOUR joints
  * (R3N_ERR_UNSUPPORTED otherwise); its f32 results follow the fused-multiply-add order of the instruction, bit-identical to
- * oracle/r3o.c::r3o_skinning_mfma_order, within 1e-6 relative of EXACT. */
+ * oracle/r3o.c::r3o_skinning_mfma_order, within 1e-6 relative of EXACT.  It weights joint slots, not influences; a slot that
+ * no taken influence of a vertex names adds +0 to that vertex whatever its matrix holds, so a degenerate joint matrix (zero
+ * column, NaN, inf) reaches exactly the vertices it reaches in EXACT. */
 #define R3N_SKIN_EXACT 0u
 #define R3N_SKIN_MFMA 1u
 int r3n_set_skinning_mode(r3n_ctx *ctx, uint32_t mode);
@@ -599,13 +601,23 @@ int r3n_frame_begin(r3n_ctx *ctx, const r3n_frame_uniforms496 *uniforms, uint32_
 /* skinning::add_skinning_to_graph (rend3-routine/src/skinning.rs:211-226): build_gpu_skinning_input_buffers (:54-139) +
  * GpuSkinner::execute_pass (:142-199) + skinning.wgsl.  `inputs`: one record per skeleton, `joint_matrices`: all
  * skeletons' joint matrices back to back (column-major mat4).  ONE launch covers every skeleton (the reference issues
- * one dispatch + one dynamic-offset bind per skeleton).  Must precede the frame's bakes (base.rs:145). */
+ * one dispatch + one dynamic-offset bind per skeleton).  Must precede the frame's bakes (base.rs:145).
+ * PRECONDITION, not checked here (the indices live in device memory): every joint index a skeleton's mesh holds, in any of the
+ * four slots and whatever its weight, is below that skeleton's matrix count -- the distance from its joint_matrix_base_offset
+ * to the next skeleton's, or to n_joint_matrices for the last.  A larger index reads another skeleton's matrices or past the
+ * buffer.  The host mirror enforces it where skeletons are made (SkeletonManager::validate_skeleton's NotEnoughJoints,
+ * rend3/src/managers/skeleton.rs:73-89: Renderer.add_skeleton / add_skeletons_bulk refuse a shorter list) and keeps a
+ * skeleton's count fixed afterwards, so the bases of cached records stay the running sums of the counts.  R3N_SKIN_MFMA reads a
+ * skeleton's joint count from the same distance. */
 int r3n_skinning(r3n_ctx *ctx, const r3n_skinning_input40 *inputs, uint32_t n_skeletons, const float *joint_matrices,
                  uint32_t n_joint_matrices);
 /* rend3-anim on the GPU.  r3n_animation_write replaces the rig / clip tables.  r3n_pose_skeletons queues
  * pose_animation_frame's per-skin work (rend3-anim/src/lib.rs:213-262) for `n` skeleton instances: the NEXT r3n_skinning
  * evaluates them on the GPU -- after copying its host `joint_matrices` (which may be NULL when every skeleton is posed
- * this way) -- and writes each skeleton's joint matrices (global * inverse bind) at its matrix_base. */
+ * this way) -- and writes each skeleton's joint matrices (global * inverse bind) at its matrix_base: the clip's WHOLE rig,
+ * rig.n_joints matrices.  Only the largest end is checked against n_joint_matrices; that the skeleton at matrix_base stores at
+ * least rig.n_joints matrices is the caller's part (Renderer.pose_skeletons refuses a larger rig: it would overwrite the next
+ * skeleton's matrices). */
 int r3n_animation_write(r3n_ctx *ctx, const r3n_anim_rig16 *rigs, uint32_t n_rigs, const r3n_anim_joint80 *joints,
                         uint32_t n_joints, const r3n_anim_clip16 *clips, uint32_t n_clips, const r3n_anim_track80 *tracks,
                         uint32_t n_tracks, const float *times, uint32_t n_times, const float *values, uint32_t n_values);

@@ -1608,7 +1608,8 @@ void r3o_skinning(uint32_t *mesh, const r3o_skinning_input *inputs, uint32_t n_s
 
 /* The same skinning in the operation order of the matrix-core variant (rend3_amd/csrc/skin_mfma.hip, R3N_SKIN_MFMA): the f32
  * MFMA is a fused-multiply-add chain over k = 0..3, the blend weights are applied per JOINT SLOT j < 4 of the rig (not per
- * influence) and the four slots are summed in slot order.  njoints[s] <= 4.  Not the arithmetic contract of r3o_skinning: a
+ * influence) and the four slots are summed in slot order; a slot whose weight sum is 0 (no taken influence names it) adds +0
+ * without looking at its matrix.  njoints[s] <= 4.  Not the arithmetic contract of r3o_skinning: a
  * second, equally explicit order that the opt-in kernel is bit-identical to. */
 void r3o_skinning_mfma_order(uint32_t *mesh, const r3o_skinning_input *inputs, uint32_t n_skeletons, const float *joint_matrices,
                              const uint32_t *njoints) {
@@ -1641,7 +1642,11 @@ void r3o_skinning_mfma_order(uint32_t *mesh, const r3o_skinning_input *inputs, u
                         qn = fmaf(0.0f, 0.0f, qn);  /* k = 3 of the instruction: a = 0, b = 0 */
                         qt = fmaf(0.0f, 0.0f, qt);
                     }
-                    tp[j][r] = qp * W; tn[j][r] = qn * W; tt[j][r] = qt * W;
+                    /* a slot no taken influence names contributes +0, whatever its matrix holds: skinning.wgsl:69 never reads
+                     * that matrix, so a zero-scale column (0 * inf), a NaN entry or an inf translation of joint j must not
+                     * reach a vertex that gives joint j no weight */
+                    if (W > 0.0f) { tp[j][r] = qp * W; tn[j][r] = qn * W; tt[j][r] = qt * W; }
+                    else { tp[j][r] = 0.0f; tn[j][r] = 0.0f; tt[j][r] = 0.0f; }
                 }
             }
             float pa[3], na[3], ta[3];

@@ -155,7 +155,8 @@ def material_record(albedo=(0, 0, 0, 1), albedo_mode="value", unlit=False, rough
 
 
 class _Mesh:
-    __slots__ = ("attr_off", "first_index", "index_count", "centre", "radius", "vertex_count", "joint_off", "weight_off")
+    __slots__ = ("attr_off", "first_index", "index_count", "centre", "radius", "vertex_count", "joint_off", "weight_off",
+                 "required_joint_count")  # highest joint index of any slot + 1 (mesh.rs:135-139); None without joint indices
 
 
 class OracleRenderer:
@@ -189,18 +190,32 @@ class OracleRenderer:
 
     # ------------------------------------------------------------------ skeletons (rend3/src/managers/skeleton.rs:67-163)
     def add_skeleton(self, mesh, joint_matrices):
+        """validate_skeleton (skeleton.rs:67-126).  NotEnoughJoints (:83-89) is a ValueError with both counts, raised before
+        anything is allocated.  The skeleton stores exactly the matrices given, for good: the reference truncates to the mesh's
+        count (:115-117); the surplus is never read by the skinning shader (the product's rule)."""
         m = self.meshes[mesh]
         assert m.joint_off != INVALID, "Mesh must have joint indices to be used in a skeleton"
+        matrices = np.ascontiguousarray(joint_matrices, dtype=f32).reshape(-1, 16)
+        if m.required_joint_count > len(matrices):
+            raise ValueError(f"NotEnoughJoints: the mesh names {m.required_joint_count} joints, but only {len(matrices)} "
+                             "joint matrices were provided")
         out_off = [INVALID] * 3
         for a in range(3):  # position, normal, tangent copies private to the skeleton (skeleton.rs:110-113)
             if m.attr_off[a] != INVALID:
                 out_off[a] = 4 * len(self.mesh_words)
                 self._mesh_append([np.zeros(3 * m.vertex_count, dtype=np.uint32)])
-        self.skeletons.append(dict(mesh=mesh, out_off=out_off, matrices=np.ascontiguousarray(joint_matrices, dtype=f32).reshape(-1, 16)))
+        self.skeletons.append(dict(mesh=mesh, out_off=out_off, matrices=matrices))
         return len(self.skeletons) - 1
 
     def set_skeleton_joint_matrices(self, sk, joint_matrices):
-        self.skeletons[sk]["matrices"] = np.ascontiguousarray(joint_matrices, dtype=f32).reshape(-1, 16)
+        """set_joint_matrices (skeleton.rs:151-163) against the stored count: fewer raise (the reference's assert), more are
+        truncated to it."""
+        stored = len(self.skeletons[sk]["matrices"])
+        mats = np.ascontiguousarray(joint_matrices, dtype=f32).reshape(-1, 16)
+        if len(mats) < stored:
+            raise ValueError(f"Not enough joints to update this skeleton. The skeleton stores {stored} joint matrices, "
+                             f"but only {len(mats)} joint matrices were provided.")
+        self.skeletons[sk]["matrices"] = np.ascontiguousarray(mats[:stored])
 
     def skinning_buffers(self):
         """build_gpu_skinning_input_buffers, rend3-routine/src/skinning.rs:54-139"""
@@ -299,6 +314,8 @@ class OracleRenderer:
 
     def add_mesh(self, positions, indices=None, normals=None, colors=None, mesh_handedness=host.LEFT, tangents=None,
                  joint_indices=None, joint_weights=None, uv0=None):
+        if joint_indices is not None and joint_weights is None:  # SkeletonCreationError::MissingAttributesJointWeights, refused here
+            raise ValueError("MissingAttributesJointWeights: a mesh with joint indices needs joint weights")
         positions = np.ascontiguousarray(positions, dtype=f32).reshape(-1, 3)
         if indices is None:
             indices = np.arange(len(positions), dtype=np.uint32)
@@ -329,7 +346,10 @@ class OracleRenderer:
             m.attr_off[5] = 4 * push(colors.view(np.uint32).reshape(-1))
         m.vertex_count = len(positions)
         m.joint_off = m.weight_off = INVALID
+        m.required_joint_count = None
         if joint_indices is not None:  # [u16; 4] per vertex, 8 bytes (rend3-types/src/attribute.rs:97-135)
+            ji = np.asarray(joint_indices, dtype=np.uint16).reshape(-1)
+            m.required_joint_count = int(ji.max()) + 1 if ji.size else 0  # every slot counts, whatever its weight (mesh.rs:135-139)
             m.joint_off = 4 * push(np.ascontiguousarray(joint_indices, dtype=np.uint16).reshape(-1, 4).view(np.uint32).reshape(-1))
             m.weight_off = 4 * push(np.ascontiguousarray(joint_weights, dtype=f32).reshape(-1, 4).view(np.uint32).reshape(-1))
         m.first_index = push(indices)

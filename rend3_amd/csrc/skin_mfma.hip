@@ -14,7 +14,7 @@
 // oracle/r3o.c::r3o_skinning_mfma_order, which is what tests/test_skinning.py holds it to:
 //   q_j   = fma(m_j[.][3], 1, fma(m_j[.][2], z, fma(m_j[.][1], y, fma(m_j[.][0], x, 0))))          (per joint slot j < 4)
 //   W_j   = sum over the vertex's influences i (in order) with joint index j and weight > 0 of weight_i
-//   p'    = ((q_0 W_0 + q_1 W_1) + q_2 W_2) + q_3 W_3                                                 (unfused)
+//   p'    = ((q_0 W_0 + q_1 W_1) + q_2 W_2) + q_3 W_3                 (unfused; a term with W_j = 0 is +0, q_j is not looked at)
 //   normals / tangents: the same with the columns of m_j scaled by 1 / |column|^2 (folded into the A operand) and w = 0,
 //   normalised afterwards (v * (1 / sqrt(v.v)), IEEE) like skinning.wgsl:89-90.
 // It is HBM-bound like the vector kernel (96 B per vertex against 384 matrix-core flops): the A/B of the two is what
@@ -60,9 +60,11 @@ __global__ __launch_bounds__(256) void k_skinning_mfma(uint32_t *__restrict__ me
         const uint32_t v = vb + (lane & 15u);          // this lane's column: vertex v, K index k = lane >> 4
         const bool live = v < in.vertex_count;
         // B operands: lane l holds B[k = l >> 4][n = l & 15] = component k of vertex n (1 / 0 for k = 3)
+        // (an attribute without a base run reads as zeros, its fourth component is still w3: vec4(vec3(0), 1), skinning.wgsl:53-73)
         auto comp = [&](uint32_t off, float w3) {
-            if (off == R3N_INVALID || !live) return 0.0f;
-            return k < 3u ? __uint_as_float(mesh[off / 4u + v * 3u + k]) : w3;
+            if (!live) return 0.0f;
+            if (k == 3u) return w3;
+            return off == R3N_INVALID ? 0.0f : __uint_as_float(mesh[off / 4u + v * 3u + k]);
         };
         const float b_pos = comp(in.base_position_offset, 1.0f), b_nrm = comp(in.base_normal_offset, 0.0f), b_tan = comp(in.base_tangent_offset, 0.0f);
         const f32x4 zero = {0.0f, 0.0f, 0.0f, 0.0f};
@@ -80,12 +82,15 @@ __global__ __launch_bounds__(256) void k_skinning_mfma(uint32_t *__restrict__ me
 #pragma unroll
             for (int i = 0; i < 4; ++i) W += (ji[i] == k && wt[i] > 0.0f) ? wt[i] : 0.0f;  // k == lane >> 4 == the joint slot
         }
+        // a slot no taken influence names adds +0 whatever its matrix holds (skinning.wgsl:69 never reads that matrix: a zero
+        // column, a NaN entry or an inf translation of a joint must not reach the vertices that give it no weight)
+        const bool named = W > 0.0f;
         float pa[3], na[3], ta[3];
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
-            pa[c] = sum_groups(qp[c] * W, lane);
-            na[c] = sum_groups(qn[c] * W, lane);
-            ta[c] = sum_groups(qt[c] * W, lane);
+            pa[c] = sum_groups(named ? qp[c] * W : 0.0f, lane);
+            na[c] = sum_groups(named ? qn[c] * W : 0.0f, lane);
+            ta[c] = sum_groups(named ? qt[c] * W : 0.0f, lane);
         }
         if (lane < 16u && live) {
             normalize3(na);

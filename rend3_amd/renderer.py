@@ -187,7 +187,26 @@ class CameraSpecifier:
 class _Mesh:
     __slots__ = ("attr_off", "first_index", "index_count", "centre", "radius", "vertex_count", "joint_off", "weight_off",
                  "n_targets", "delta_off", "reach", "morph_weights", "adjacency_off", "left_handed", "morph_normals", "morph_tangents",
-                 "block")  # block: mesh_upload="stream": byte offset of the mesh's pooled block (None in "append" mode)
+                 "block",  # block: mesh_upload="stream": byte offset of the mesh's pooled block (None in "append" mode)
+                 "required_joint_count")  # highest joint index of any slot + 1 (mesh.rs:135-139); None without joint indices
+
+
+def required_joint_count(joint_indices):
+    """InternalMesh::required_joint_count (rend3/src/managers/mesh.rs:135-139): the highest joint index over all four slots of
+    every vertex, plus one.  The weights play no part, as in the reference: a slot whose weight is zero counts too."""
+    ji = np.asarray(joint_indices, dtype=np.uint16).reshape(-1)
+    return int(ji.max()) + 1 if ji.size else 0
+
+
+def checked_joint_matrices(required, joint_matrices):
+    """SkeletonManager::validate_skeleton (rend3/src/managers/skeleton.rs:73-89): the matrices as (n, 16) f32; ValueError when
+    the mesh has no joint indices or names more joints than there are matrices (NotEnoughJoints, with both counts)."""
+    if required is None:
+        raise ValueError("Mesh must have joint indices to be used in a skeleton")  # SkeletonCreationError
+    mats = np.ascontiguousarray(joint_matrices, dtype=f32).reshape(-1, 16)
+    if required > len(mats):
+        raise ValueError(f"NotEnoughJoints: the mesh names {required} joints, but only {len(mats)} joint matrices were provided")
+    return mats
 
 
 def relocate_offsets(values, moves, words=False):
@@ -383,6 +402,8 @@ class Renderer:
                 raise ValueError("morph_tangents='recompute': the mesh needs morph targets with position deltas")
             if morph_targets.get("tangents") is not None:
                 raise ValueError("morph_tangents='recompute': the targets carry tangent deltas")
+        if joint_indices is not None and joint_weights is None:  # SkeletonCreationError::MissingAttributesJointWeights, refused here
+            raise ValueError("MissingAttributesJointWeights: a mesh with joint indices needs joint weights")
         positions = np.ascontiguousarray(positions, dtype=f32).reshape(-1, 3)
         if indices is None:
             indices = np.arange(len(positions), dtype=np.uint32)
@@ -418,7 +439,9 @@ class Renderer:
             m.attr_off[5] = 4 * push(colors.view(np.uint32).reshape(-1))
         m.vertex_count = len(positions)
         m.joint_off = m.weight_off = INVALID
+        m.required_joint_count = None
         if joint_indices is not None:  # [u16; 4] per vertex + vec4<f32> weights (rend3-types/src/attribute.rs:97-135)
+            m.required_joint_count = required_joint_count(joint_indices)
             m.joint_off = 4 * push(np.ascontiguousarray(joint_indices, dtype=np.uint16).reshape(-1, 4).view(np.uint32).reshape(-1))
             m.weight_off = 4 * push(np.ascontiguousarray(joint_weights, dtype=f32).reshape(-1, 4).view(np.uint32).reshape(-1))
         m.first_index = push(indices)
@@ -467,32 +490,35 @@ class Renderer:
     # ---- skeletons (rend3/src/managers/skeleton.rs:67-163)
     def add_skeleton(self, mesh, joint_matrices, morph=None):
         """morph: a morph instance of the same mesh -- the skeleton then skins from the instance's morphed runs (glTF: morph
-        first, then skin) and its objects take the instance's widened bounding sphere."""
+        first, then skin) and its objects take the instance's widened bounding sphere.  ValueError, before anything is allocated,
+        when the mesh names more joints than there are matrices (NotEnoughJoints, skeleton.rs:83-89).  The skeleton stores
+        exactly the matrices given, for good: the reference truncates to the mesh's count (skeleton.rs:115-117), this mirror
+        keeps the surplus -- never read by the skinning kernel -- so that a pose can write a whole rig."""
         m = self.meshes[mesh]
-        if m.joint_off == INVALID:
-            raise ValueError("Mesh must have joint indices to be used in a skeleton")  # SkeletonCreationError
+        matrices = checked_joint_matrices(m.required_joint_count, joint_matrices)
         if morph is not None and self.morphs[morph]["mesh"] != mesh:
             raise ValueError("add_skeleton: the morph instance belongs to another mesh")
         out_off = [INVALID] * 3
         if self._mesh_upload == "stream":
-            return self._add_skeletons_stream(mesh, [joint_matrices], morph)[0]
+            return self._add_skeletons_stream(mesh, [matrices], morph)[0]
         for a in range(3):  # private position / normal / tangent copies (skeleton.rs:110-113)
             if m.attr_off[a] != INVALID:
                 out_off[a] = 4 * self.mesh_cursor
                 zeros = np.zeros(3 * m.vertex_count, dtype=np.uint32)
                 self._check(self.lib.r3n_mesh_buffer_write(self.ctx, out_off[a], _ffi.ptr(zeros), zeros.nbytes), "r3n_mesh_buffer_write")
                 self.mesh_cursor += len(zeros)
-        self.skeletons.append(dict(mesh=mesh, out_off=out_off, matrices=np.ascontiguousarray(joint_matrices, dtype=f32).reshape(-1, 16),
-                                   morph=morph, block=None))
+        self.skeletons.append(dict(mesh=mesh, out_off=out_off, matrices=matrices, morph=morph, block=None))
         self._skin_inputs = None
         return len(self.skeletons) - 1
 
     def add_skeletons_bulk(self, mesh, joint_matrices_per_skeleton):
-        """Many skeletons of one mesh (config 5): one zero-fill upload for all private output ranges."""
+        """Many skeletons of one mesh (config 5): one zero-fill upload for all private output ranges.  Every matrix list is
+        checked as in add_skeleton before anything is allocated: one short list refuses the whole call."""
         m = self.meshes[mesh]
+        matrices = [checked_joint_matrices(m.required_joint_count, mats) for mats in joint_matrices_per_skeleton]
         if self._mesh_upload == "stream":
-            return self._add_skeletons_stream(mesh, joint_matrices_per_skeleton, None)
-        n = len(joint_matrices_per_skeleton)
+            return self._add_skeletons_stream(mesh, matrices, None)
+        n = len(matrices)
         n_attr = sum(1 for a in range(3) if m.attr_off[a] != INVALID)
         words = 3 * m.vertex_count
         zeros = np.zeros(n * n_attr * words, dtype=np.uint32)
@@ -506,14 +532,14 @@ class Renderer:
                 if m.attr_off[a] != INVALID:
                     out_off[a] = 4 * (base + (i * n_attr + k) * words)
                     k += 1
-            self.skeletons.append(dict(mesh=mesh, out_off=out_off, morph=None, block=None,
-                                       matrices=np.ascontiguousarray(joint_matrices_per_skeleton[i], dtype=f32).reshape(-1, 16)))
+            self.skeletons.append(dict(mesh=mesh, out_off=out_off, morph=None, block=None, matrices=matrices[i]))
         self._skin_inputs = None
         return list(range(first, first + n))
 
     def _add_skeletons_stream(self, mesh, joint_matrices_per_skeleton, morph):
         """mesh_upload="stream": ONE r3n_mesh_blocks_add with one zero-filled block per skeleton (its private runs back to back), so
-        that each can be retired on its own (SkeletonManager::remove, skeleton.rs:139-147)."""
+        that each can be retired on its own (SkeletonManager::remove, skeleton.rs:139-147).  The matrix lists come checked
+        (checked_joint_matrices) from add_skeleton / add_skeletons_bulk."""
         m = self.meshes[mesh]
         attrs = [a for a in range(3) if m.attr_off[a] != INVALID]
         words = 3 * m.vertex_count
@@ -523,8 +549,7 @@ class Renderer:
             out_off = [INVALID] * 3
             for k, a in enumerate(attrs):
                 out_off[a] = block + 4 * k * words
-            self.skeletons.append(dict(mesh=mesh, out_off=out_off, morph=morph, block=block,
-                                       matrices=np.ascontiguousarray(mats, dtype=f32).reshape(-1, 16)))
+            self.skeletons.append(dict(mesh=mesh, out_off=out_off, morph=morph, block=block, matrices=mats))
         self._skin_inputs = None
         return list(range(first, first + len(blocks)))
 
@@ -636,9 +661,17 @@ class Renderer:
         self._morph_dirty.clear()
 
     def set_skeleton_joint_matrices(self, sk, joint_matrices):
+        """SkeletonManager::set_joint_matrices (skeleton.rs:151-163) against the count the skeleton stores, which is fixed at its
+        creation: fewer matrices raise ValueError (the reference's assert), more are truncated to it.  So the matrix bases in
+        the cached skinning records, the running sums of the stored counts, cannot go stale."""
+        stored = len(self.skeletons[sk]["matrices"])
+        mats = np.ascontiguousarray(joint_matrices, dtype=f32).reshape(-1, 16)
+        if len(mats) < stored:
+            raise ValueError(f"Not enough joints to update this skeleton. The skeleton stores {stored} joint matrices, "
+                             f"but only {len(mats)} joint matrices were provided.")
         self.world_version += 1  # skinned vertices may leave the bounds the partition was built from
         self._pose_state.pop(sk, None)
-        self.skeletons[sk]["matrices"] = np.ascontiguousarray(joint_matrices, dtype=f32).reshape(-1, 16)
+        self.skeletons[sk]["matrices"] = np.ascontiguousarray(mats[:stored])
 
     def animation_add(self, rigs, joints, clips, tracks, times, values):
         """Register one AnimationData's tables (anim.AnimationData builds them; record layouts in include/r3n.h).  The
@@ -667,7 +700,20 @@ class Renderer:
         """rend3-anim poses: requests = [(clip, time, skeleton handle)].  The joint matrices are evaluated on the GPU
         (csrc/anim.hip) in front of every skinning pass, straight into the buffer the skinning kernel reads, until the
         skeleton gets another pose or explicit matrices (Renderer::set_skeleton_joint_matrices semantics: the last
-        value set stays)."""
+        value set stays).  The pose kernel writes the clip's whole rig at the skeleton's matrix base: ValueError, before any
+        request is taken, when a clip's rig has more joints than its skeleton stores (it would overwrite the next skeleton's)."""
+        requests = list(requests)
+        sets = self._anim_sets
+        for clip, _time, sk in requests:
+            if sets is None or not 0 <= int(clip) < len(sets[0][2]):
+                raise ValueError(f"pose_skeletons: clip {clip} is not registered (animation_add)")
+            if not 0 <= int(sk) < len(self.skeletons) or self.skeletons[int(sk)] is None:
+                raise ValueError(f"pose_skeletons: skeleton {sk} does not exist (a bad handle, or removed)")
+            rig_joints = int(sets[0][0]["n"][int(sets[0][2]["rig"][int(clip)])])
+            stored = len(self.skeletons[int(sk)]["matrices"])
+            if rig_joints > stored:
+                raise ValueError(f"pose_skeletons: the rig of clip {clip} has {rig_joints} joints, but skeleton {sk} stores only "
+                                 f"{stored} joint matrices")
         self.world_version += 1
         for clip, time, sk in requests:
             self._pose_state[sk] = (int(clip), np.float32(time))
