@@ -18,11 +18,12 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "_obj")
 SO = os.path.join(HERE, "librend3_amd.so")
-COMMON = ["layouts.h", "device_math.h", "../../include/r3n.h"]
+COMMON = ["layouts.h", "device_math.h", "exact_math.h", "../../include/r3n.h"]
 # translation unit -> the headers it includes (besides COMMON)
 UNITS = {
     "r3n.hip": ["texture.h", "kernels_cull.h", "kernels_raster.h", "kernels_shade.h", "comm.h", "skybox.h", "blend_sort.h", "morph.h", "normals.h", "tangents.h",
-                "vertex_block.h", "vertex_gather.h", "exact_math.h", "texel_alloc.h", "texel_compact.h", "texel_tail.h", "texture_jobs.h", "mesh_reloc.h"],
+                "vertex_block.h", "vertex_gather.h", "exact_math.h", "texel_alloc.h", "texel_compact.h", "texel_tail.h", "texture_jobs.h", "mesh_reloc.h",
+                "hip_owned.h"],
     "shade.hip": ["texture.h", "kernels_shade.h"],
     "shade_cls.hip": ["texture.h", "kernels_shade.h"],
     "shade_ms.hip": ["texture.h", "kernels_shade.h"],

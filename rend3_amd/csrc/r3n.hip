@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "comm.h"
+#include "hip_owned.h"
 #include "kernels_cull.h"
 #include "kernels_raster.h"
 #define R3N_SHADE_DECL_ONLY
@@ -33,11 +34,11 @@
 
 namespace {
 
-struct DevBuf {
-    void *p = nullptr;
-    size_t bytes = 0;
-    template <class T> T *as() const { return reinterpret_cast<T *>(p); }
-};
+using hip_owned::DeviceBuffer;
+using hip_owned::DeviceSpan;
+using hip_owned::Event;
+using hip_owned::PinnedHost;
+using hip_owned::Stream;
 
 struct CamState {
     r3n_camera_header240 hdr{};
@@ -47,20 +48,20 @@ struct CamState {
     int cur = 0;                 // ping-pong index written by this frame's cull
     int last = -1;               // index holding the most recent cull results (for readbacks)
     uint32_t vp_x = 0, vp_y = 0, vp_size = 0;
-    DevBuf d_hdr;                // NOT owned: points into the frame-constants block of the current frame slot (canon: into own_hdr)
-    DevBuf own_hdr;
+    DeviceSpan d_hdr;            // points into the frame-constants block of the current frame slot (canon: into own_hdr)
+    DeviceBuffer own_hdr;
     uint64_t hdr_frame = ~0ull;  // frame whose constants block already carries this camera's header (r3n_render_frame)
     uint64_t baked_frame = ~0ull;  // frame of the last r3n_uniform_bake: the header in THIS frame's constants block is only valid then
-    DevBuf chain;                // k_object_pass_chained: one ObjChainRec per block, tagged with the launch's epoch
+    DeviceBuffer chain;                // k_object_pass_chained: one ObjChainRec per block, tagged with the launch's epoch
     uint32_t chain_epoch = 0;
     uint64_t object_pass_frame = ~0ull;  // frame whose object pass already ran, fused with the bake (r3n_render_frame)
-    DevBuf baked, vis_flags, vis_list, block_sums, block_off;
-    DevBuf first_entry;          // kernels_cull.h write_first_entries: the work-list entry owning every R3N_CHUNK_ITERS-th wave slot
-    DevBuf slot_base[2], mask[2], predicted[2], sub_counts[2], counts[2];
+    DeviceBuffer baked, vis_flags, vis_list, block_sums, block_off;
+    DeviceBuffer first_entry;          // kernels_cull.h write_first_entries: the work-list entry owning every R3N_CHUNK_ITERS-th wave slot
+    DeviceBuffer slot_base[2], mask[2], predicted[2], sub_counts[2], counts[2];
     uint32_t subcap[2] = {0, 0};  // list entries reserved per (material key, sub-list)
     uint64_t key_objects[2][3] = {};  // enabled objects per material key AS THE CULL OF THAT INDEX SAW THEM: last frame's predicted
                                       // triangles sit in last frame's draw ranges (forward.rs:224-232,286), whatever the keys are now
-    DevBuf residual;
+    DeviceBuffer residual;
     bool range_set = false;      // r3n_set_camera_object_range: this camera's own object range (multi-GPU: shadow views owned whole)
     uint32_t range_begin = 0, range_end = 0xFFFFFFFFu;
     uint32_t band_begin = 0, band_end = 0xFFFFFFFFu;  // shadow view split by rows over several ranks (r3n_render_frame, native exchange): the rows this rank rasterises
@@ -96,13 +97,13 @@ static_assert(R3N_AUX_STREAMS >= 1, "the shadow views draw on auxiliary streams"
 
 struct r3n_ctx {
     int device = 0;
-    hipStream_t stream = nullptr;  // main stream: uploads, viewport chain, resolve, tonemap, collectives
+    Stream stream;  // main stream: uploads, viewport chain, resolve, tonemap, collectives
     // Shadow views are independent of each other and of the viewport's pass-1 / Hi-Z / cull chain until the
     // resolve reads the atlas, and their kernels are latency-bound rather than throughput-bound: each shadow camera
     // runs on its own auxiliary stream (forked after the frame's clears, joined before the resolve) so the five
     // chains overlap and the launch gaps of one hide behind the work of the others.
-    hipStream_t aux[R3N_AUX_STREAMS] = {};
-    hipEvent_t fork_ev[R3N_AUX_STREAMS] = {};
+    Stream aux[R3N_AUX_STREAMS];
+    Event fork_ev[R3N_AUX_STREAMS];
     // Frames in flight.  The resolve is VALU-bound and everything before it (culls, rasterisers, Hi-Z) is latency- and
     // atomic-bound, so frame N's resolve runs on its own stream while the main stream and the lanes already work on frame
     // N + 1.  Everything the resolve reads that the next frame rewrites exists twice; the two sets swap at frame_begin:
@@ -116,8 +117,8 @@ struct r3n_ctx {
     // stream, so the shade stream carries the resolve alone and one frame's resolve follows the previous one's directly.
     // close_frame keeps the join wherever the frame's resolve did not go to the shade stream, or outside work is ordered against
     // the streams (communicators, exchange callbacks); join_lanes / join_frames give everything else the order it needs.
-    hipStream_t shade = nullptr;
-    hipEvent_t vp_ev = nullptr, shade_done[2] = {nullptr, nullptr};
+    Stream shade;
+    Event vp_ev, shade_done[2];
     bool shade_pending[2] = {false, false};
     bool shade_unjoined = false;      // the main stream has not yet been ordered after the latest resolve
     int shade_last = 0;               // the slot of that resolve
@@ -127,7 +128,7 @@ struct r3n_ctx {
     bool always_fork = false;     // R3N_ALWAYS_FORK=1: the shadow lanes wait for the main stream at every fork (no epoch gate)
     bool resolve_classes = true;  // R3N_RESOLVE_CLASSES=0: the general resolve kernel for every tile (A/B, tests)
     bool fused_frame = false;  // inside r3n_render_frame: a camera's bake and object pass are ONE launch, issued at its r3n_uniform_bake
-    DevBuf alt_vis, alt_atlas, alt_vp_baked;
+    DeviceBuffer alt_vis, alt_atlas, alt_vp_baked;
     // Frame-constants block: FrameUniforms, the viewport's camera header, the directional-light buffer, every shadow view's camera
     // header and the point-light buffer of one frame live in ONE device block per frame slot (fu / dir_buf / point_buf / d_hdr
     // point into it), filled through one pinned host image per frame in flight: r3n_render_frame uploads a frame's constants
@@ -135,29 +136,30 @@ struct r3n_ctx {
     static constexpr size_t kFbUniforms = 0, kFbViewportHdr = 512, kFbDir = 768, kFbShadowHdr = 3072,
                             kFbPoint = kFbShadowHdr + 256 * R3N_MAX_SHADOW_VIEWS, kFbBytes = kFbPoint + 8448;
     static constexpr int kFbHost = 4;
-    DevBuf fb_dev[2];
-    uint8_t *fb_host[kFbHost] = {};
-    hipEvent_t fb_ev[kFbHost] = {};
+    DeviceBuffer fb_dev[2];
+    PinnedHost fb_host[kFbHost];
+    Event fb_ev[kFbHost];
     bool fb_pending[kFbHost] = {};
     // fork_lane is a no-op while nothing the lanes depend on has been enqueued on the main stream since their last fork
     uint64_t main_epoch = 1, lane_epoch[R3N_AUX_STREAMS] = {};
     // the work-queue counters of every lane, one block per frame slot (big_count[] views the current slot's): r3n_frame_begin zeroes
     // its slot's block on the main stream while the lanes may still be consuming the other block's counters (previous frame)
-    DevBuf big_count_all;
+    DeviceBuffer big_count_all;
     static constexpr size_t kBigCountWords = (size_t)(1 + R3N_QLANES) * 64 * R3N_BIGQ;  // per slot
     bool exchanged_this_frame = false;  // an exchange callback / r3n_exchange_*: outside work was ordered against this frame's streams
     std::vector<uint8_t> h_dir, h_point;   // the light buffers as last written (uploaded into the frame's slot at frame_begin)
     uint64_t lights_version = 1, slot_lights_version[2] = {0, 0};
-    hipEvent_t join_ev[R3N_AUX_STREAMS] = {};
+    Event join_ev[R3N_AUX_STREAMS];
     bool aux_used[R3N_AUX_STREAMS] = {};
     bool multi_stream = true;
     std::string err;
     // world data
-    DevBuf mesh, objects, materials, material_keys, dir_buf, point_buf, fu;
+    DeviceBuffer mesh, objects, materials, material_keys;
+    DeviceSpan dir_buf, point_buf, fu;  // into the frame slot's constants block (fb_dev)
     // structure-of-arrays view of the objects for the object pass (kernels_cull.h ObjSoA): bounding spheres, and per slot
     // (enabled ? index_count / 3 : 0) | material key << 30 -- written beside the 128-byte records by r3n_objects_write, the key
     // bits refreshed from the host mirrors when r3n_materials_write changed a key (refresh_obj_meta)
-    DevBuf spheres, obj_meta;
+    DeviceBuffer spheres, obj_meta;
     bool meta_dirty = false;
     uint32_t capacity = 0, n_materials = 0;
     std::vector<uint32_t> h_ntri;  // host mirror: triangles per enabled object slot
@@ -167,8 +169,8 @@ struct r3n_ctx {
     // "the sampler's short path applies", the feature word per material on the device and the variants the census found
     std::vector<r3n_material208> h_materials;
     std::vector<uint8_t> h_tex_short;
-    DevBuf material_feat;
-    DevBuf view_lights[2];  // ViewLights of the frame set (k_stage_view_lights writes it in front of the single-sample resolve)
+    DeviceBuffer material_feat;
+    DeviceBuffer view_lights[2];  // ViewLights of the frame set (k_stage_view_lights writes it in front of the single-sample resolve)
     uint32_t resolve_variants = 0;
     bool classes_dirty = true;
     // Launch parameters that decide how the frame's kernels SHARE the chip (profiles/r04_summary.md section 6a: the frame is the sum of
@@ -193,18 +195,18 @@ struct r3n_ctx {
     uint64_t key_objects[3] = {0, 0, 0};  // enabled objects per material key
     uint64_t total_tris = 0;
     bool tri_base_dirty = true;
-    DevBuf tri_base, slot_table;
+    DeviceBuffer tri_base, slot_table;
     // skinning (row S1): cached skeleton records + the wave -> skeleton map derived from them
-    DevBuf skin_inputs, skin_matrices, skin_wave_skeleton, skin_wave_first, skin_joint_counts;
+    DeviceBuffer skin_inputs, skin_matrices, skin_wave_skeleton, skin_wave_first, skin_joint_counts;
     uint32_t skinning_mode = R3N_SKIN_EXACT, skin_max_joints = 0;
     std::vector<r3n_skinning_input40> h_skin_inputs;
     uint32_t skin_total_waves = 0;
     // morph targets (morph.h): the records, wave map and weight terms of ONE r3n_morph call, as one block behind one staged copy
-    DevBuf morph_block;
+    DeviceBuffer morph_block;
     // recomputed normals (normals.h): the records and wave map of ONE r3n_vertex_normals call, one block behind one staged copy
-    DevBuf normals_block;
+    DeviceBuffer normals_block;
     // generated tangents (tangents.h): the same, of ONE r3n_vertex_tangents call
-    DevBuf tangents_block;
+    DeviceBuffer tangents_block;
     uint32_t slot_table_size = 0;
     CamState canon;  // scratch camera used to (re)build the canonical tri_base scan
     // frame targets
@@ -213,23 +215,24 @@ struct r3n_ctx {
     bool in_frame = false;
     bool blended_this_frame = false;
     bool resolved_this_frame = false;  // the resolve also wrote the tonemapped image
-    DevBuf vis, hdr16, out8, out_f32, atlas, hiz;
+    DeviceBuffer vis, hdr16, out8, out_f32, atlas, hiz;
     r3n_hiz_desc hizd{};
     bool hiz_plane_ready = false;  // mip 0 already holds the (merged) pass-1 depth: r3n_exchange_depth
     // transparent pass (row N3)
     // per-triangle vertex-stage records of the resolve (kernels_raster.h TriRecord), written by the prepass on the main stream; one
     // set per frame slot while frames are pipelined (swapped at frame_begin: the previous frame's resolve still reads the other)
-    DevBuf tri_rec, alt_tri_rec, tri_seen;
-    DevBuf blend_order, blend_rank_base, frag_keys, frag_vals, frag_count, frag_head, samples16;
-    uint32_t *status_host = nullptr, *status_dev = nullptr;  // host-mapped word the kernels raise when a fixed-size buffer ran out
+    DeviceBuffer tri_rec, alt_tri_rec, tri_seen;
+    DeviceBuffer blend_order, blend_rank_base, frag_keys, frag_vals, frag_count, frag_head, samples16;
+    PinnedHost status_host;
+    uint32_t *status_dev = nullptr;  // host-mapped word the kernels raise when a fixed-size buffer ran out
     std::vector<uint32_t> h_blend_order;
     uint32_t n_blend = 0, blend_tris = 0;
     // sorted mode (blend_sort.h): the blend set of r3n_blend_objects_write and the scratch of r3n_blend_sort, sized at the upload.
     // The last of r3n_blend_order_write / r3n_blend_objects_write decides where blend_order and blend_rank_base come from.
-    DevBuf blend_set_slots, blend_set_locations, blend_sort_scratch;
+    DeviceBuffer blend_set_slots, blend_set_locations, blend_sort_scratch;
     bool blend_sorted = false;
     uint32_t frag_capacity = 32u << 20;  // fragment nodes (12 B each), allocated on first use
-    DevBuf tex_descs, tex_texels, tex_level_off, srgb8_decode;  // bindless texture array (row N2): descriptors, RGBA8 texel pool, decode tables  // bindless texture array (row N2) + sRGB8 -> linear table
+    DeviceBuffer tex_descs, tex_texels, tex_level_off, srgb8_decode;  // bindless texture array (row N2): descriptors, RGBA8 texel pool, decode tables  // bindless texture array (row N2) + sRGB8 -> linear table
     uint32_t n_textures = 0;  // table length (streamed path: removed slots included)
     uint64_t n_texels = 0;    // pool words in use: the allocator's high-water mark
     // Streamed texture path (r3n_textures_update / r3n_textures_remove; texel_alloc.h): the host's mirror of the table and who owns
@@ -240,12 +243,12 @@ struct r3n_ctx {
     std::vector<uint8_t> h_tex_live;              // per slot: holds a texture
     std::vector<uint8_t> h_tex_hot;               // per slot: held a texture at some time since the last full wait (a frame in flight may read it)
     uint64_t sync_serial = 0, tex_sync_seen = 0;  // sync_all counts its calls; the texture path compares
-    DevBuf tex_stage, tex_jobs;                   // grow-only, owned by the texture path alone: the call's payload, its job tables
-    std::vector<void *> tex_retired;              // outgrown blocks of those two: freed behind the next full wait (hipFree waits for the device)
+    DeviceBuffer tex_stage, tex_jobs;                   // grow-only, owned by the texture path alone: the call's payload, its job tables
+    std::vector<DeviceBuffer> tex_retired;             // outgrown blocks of those two: freed behind the next full wait (hipFree waits for the device)
     // The streamed path's own stream (created by the first r3n_textures_update): the payload copy, the table rows, the decode and
     // the generated levels run on it, and the call waits for IT alone -- the frames in flight on the main stream, the lanes and the
     // shade stream keep running.  Everything enqueued after the call comes after its work, because the call has waited for it.
-    hipStream_t tex_stream = nullptr;
+    Stream tex_stream;
     r3n_texture_counters tex_stats{};
     // Pooled mesh blocks (r3n_mesh_blocks_add / _remove / r3n_mesh_compact): who owns which mesh-buffer words.  The allocator is the
     // texel pool's (texel_alloc.h is generic over "a pool of u32 words"); the path shares the texture path's stream, staging and
@@ -256,28 +259,29 @@ struct r3n_ctx {
     bool mesh_appended = false;                // r3n_mesh_buffer_write wrote outside pooled mode
     uint64_t mesh_sync_seen = 0;               // sync_serial when the mesh path last looked (parked words are clean after a full wait)
     r3n_mesh_counters mesh_stats{};
-    hipEvent_t mesh_reloc_ev[2] = {nullptr, nullptr};  // around the relocation kernel (r3n_mesh_compact_result::relocate_ns)
+    Event mesh_reloc_ev[2];  // around the relocation kernel (r3n_mesh_compact_result::relocate_ns)
     // cube textures + the skybox node (skybox.h): the bordered faces of every cube, where each cube starts, which one is bound
     struct Cube { size_t first_word; uint32_t n, srgb; };
-    DevBuf cube_texels;
+    DeviceBuffer cube_texels;
     std::vector<Cube> cubes;
     uint32_t sky_cube = 0;            // r3n_skybox_set: 0 = none, i + 1 = cubes[i]
     bool sky_window = false;          // between r3n_resolve_opaque and the transparent pass / tonemap: where r3n_skybox is legal
     bool resolve_on_shade = false;    // the stream this frame's resolve went to (the sky follows it there)
     uint32_t sky_samples_form = R3N_SKY_SAMPLES_ALL;  // four samples: where this frame's resolve left the per-sample colours
     // rend3-anim tables (row N4) and the pose requests queued for the next r3n_skinning
-    DevBuf edge_list, edge_count;  // split MSAA resolve (kernels_raster.h k_resolve_edges)
+    DeviceBuffer edge_list, edge_count;  // split MSAA resolve (kernels_raster.h k_resolve_edges)
     uint32_t edge_capacity_override = 0;
-    DevBuf anim_rigs, anim_joints, anim_clips, anim_tracks, anim_times, anim_values, pose_requests;
+    DeviceBuffer anim_rigs, anim_joints, anim_clips, anim_tracks, anim_times, anim_values, pose_requests;
     std::vector<r3n_anim_rig16> h_anim_rigs;
     std::vector<r3n_anim_clip16> h_anim_clips;
     uint32_t n_pose_requests = 0, pose_matrix_end = 0, anim_max_joints = 1;
-    DevBuf big_uv[1 + R3N_QLANES];
-    DevBuf srgb_thr;  // 255 floats: smallest linear value whose Rgba8UnormSrgb code is >= c (GPU mip generation)
-    DevBuf srgb_lut;  // 8-bit output code of every half in [0, 1): kernels_raster.h k_build_srgb_lut (or r3n_set_output_format)
+    DeviceBuffer big_uv[1 + R3N_QLANES];
+    DeviceBuffer srgb_thr;  // 255 floats: smallest linear value whose Rgba8UnormSrgb code is >= c (GPU mip generation)
+    DeviceBuffer srgb_lut;  // 8-bit output code of every half in [0, 1): kernels_raster.h k_build_srgb_lut (or r3n_set_output_format)
     uint32_t output_format = R3N_OUTPUT_RGBA8_UNORM_SRGB;
     uint32_t shade_mode = R3N_SHADE_EXACT;
-    DevBuf big_items[1 + R3N_QLANES], big_count[1 + R3N_QLANES];  // work queues: [0] the viewport's, 1.. one per concurrently drawn shadow view
+    DeviceBuffer big_items[1 + R3N_QLANES];
+    DeviceSpan big_count[1 + R3N_QLANES];  // work queues: [0] the viewport's, 1.. one per concurrently drawn shadow view
     uint32_t forward_index_lane[1 + R3N_QLANES] = {};
     uint32_t big_capacity = (2u << 20) / R3N_BIGQ;  // entries (64 B) per work sub-queue (R3N_BIGQ of them)
     CamState viewport;
@@ -291,22 +295,22 @@ struct r3n_ctx {
         bool by_objects = false;  // r3n_comm_set_split(R3N_SHARD_OBJECTS): object-range split (depth MAX all-reduce + key MAX reduce-scatter)
         uint32_t rank = 0, world = 1;
         ncclComm_t main = nullptr, shadow = nullptr, rows = nullptr;
-        DevBuf stage[R3N_MAX_SHADOW_VIEWS];  // contiguous copies of the shadow rectangles (what a broadcast moves)
-        hipEvent_t order_ev = nullptr;       // tune.comm_serial: behind the last collective enqueued, on whichever stream that was
+        DeviceBuffer stage[R3N_MAX_SHADOW_VIEWS];  // contiguous copies of the shadow rectangles (what a broadcast moves)
+        Event order_ev;                      // tune.comm_serial: behind the last collective enqueued, on whichever stream that was
         bool order_pending = false;
     } comm;
-    DevBuf owners;  // r3n_set_object_owners: owner rank per object slot (p == nullptr: slot ranges)
+    DeviceBuffer owners;  // r3n_set_object_owners: owner rank per object slot (p == nullptr: slot ranges)
     uint32_t owner_rank = 0, owners_n = 0;
     // pinned staging ring for small per-frame uploads (headers, uniforms, light buffers): the caller owns its
     // pointers only for the duration of a call, and the frame path must not synchronise with the GPU.
     static constexpr uint32_t kStageSlots = 256, kStageSlotBytes = 4096;
-    uint8_t *stage = nullptr;
+    PinnedHost stage;
     uint32_t stage_next = 0;
-    hipEvent_t stage_half_done[2] = {nullptr, nullptr};
+    Event stage_half_done[2];
     bool stage_half_pending[2] = {false, false};
     // pinned staging for LARGE per-frame uploads (joint matrices, pose requests): the caller owns its pointer only for the duration
     // of the call and the frame path must not wait for the GPU; a buffer is reused once the copy issued from it has executed
-    struct Bulk { uint8_t *p = nullptr; size_t bytes = 0; hipEvent_t ev = nullptr; bool pending = false; } bulk[4];
+    struct Bulk { PinnedHost host; Event ev; bool pending = false; } bulk[4];
     uint32_t bulk_next = 0;
     // R3N_BREADCRUMBS=<prefix>: one line per stage / collective into <prefix>.pid<pid>.ctx<n> as it is ENQUEUED (write(2), no
     // buffering) -- where a rank that stopped answering was last seen (tests/mp_harness.py, tools/soak_native.py); -1: off
@@ -314,11 +318,11 @@ struct r3n_ctx {
     bool sync_stages = false;  // R3N_SYNC_STAGES=1: every stage is waited for where it is enqueued (diagnosis of a kernel that does not return)
     // timing taps
     bool timing = false;
-    struct Span { hipEvent_t a, b; int stage; hipStream_t stream; };
+    struct Span { Event a, b; int stage; hipStream_t stream; };
     std::vector<Span> spans;
     double span_overhead_ms = 0.0;  // two events around an empty launch (median of 32), measured when timing is switched on
     bool span_calibrated = false;
-    std::vector<hipEvent_t> event_pool;
+    std::vector<Event> event_pool;
     double stage_ms[R3N_STAGE_COUNT] = {0};
     int hbm_best_variant = -1;
     uint64_t stage_launches[R3N_STAGE_COUNT] = {0};
@@ -345,6 +349,11 @@ static void crumb(const r3n_ctx *c, const char *what, long long a = -1, long lon
         if (_e != hipSuccess)                                                                     \
             return fail((c), R3N_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));    \
     } while (0)
+#define TRY(expr)                      \
+    do {                               \
+        int _r = (expr);               \
+        if (_r != R3N_OK) return _r;   \
+    } while (0)
 
 int sync_all(r3n_ctx *c);
 int join_shade(r3n_ctx *c);
@@ -352,36 +361,33 @@ int join_lanes(r3n_ctx *c);
 int join_frames(r3n_ctx *c);
 
 // Grow-only device buffer.  preserve: keep old contents; fill: byte value for the newly allocated tail.
-int ensure(r3n_ctx *c, DevBuf &b, size_t bytes, bool preserve, int fill) {
+int ensure(r3n_ctx *c, DeviceBuffer &b, size_t bytes, bool preserve, int fill) {
     if (bytes <= b.bytes && b.p) return R3N_OK;
     size_t want = std::max<size_t>(bytes, 256);
     ++c->main_epoch;  // copies / fills below run on the main stream
     if (b.bytes) want = std::max(want, b.bytes + b.bytes / 2);  // amortised growth
-    void *np = nullptr;
-    HIP_TRY(c, hipMalloc(&np, want));
+    DeviceBuffer nb;  // (every early return releases it)
+    HIP_TRY(c, nb.alloc(want));
     size_t kept = 0;
     if (preserve && b.p && b.bytes) {
         // a lane or the shade stream may still be writing the old allocation: the snapshot must come after them
-        int r = join_lanes(c);
-        if (r == R3N_OK) r = join_shade(c);
-        if (r != R3N_OK) { (void)hipFree(np); return r; }
-        HIP_TRY(c, hipMemcpyAsync(np, b.p, b.bytes, hipMemcpyDeviceToDevice, c->stream));
+        TRY(join_lanes(c));
+        TRY(join_shade(c));
+        HIP_TRY(c, hipMemcpyAsync(nb.p, b.p, b.bytes, hipMemcpyDeviceToDevice, c->stream));
         kept = b.bytes;
     }
-    if (fill >= 0) HIP_TRY(c, hipMemsetAsync(static_cast<char *>(np) + kept, fill, want - kept, c->stream));
+    if (fill >= 0) HIP_TRY(c, hipMemsetAsync(nb.as<char>() + kept, fill, want - kept, c->stream));
     if (b.p) {
-        int r = sync_all(c);  // any stream may still be reading the old allocation
-        if (r != R3N_OK) return r;
-        HIP_TRY(c, hipFree(b.p));
+        TRY(sync_all(c));  // any stream may still be reading the old allocation
+        HIP_TRY(c, b.reset());
     }
-    b.p = np;
-    b.bytes = want;
+    b = std::move(nb);
     return R3N_OK;
 }
 
 // Asynchronous small upload through the pinned ring; falls back to a synchronous copy for large payloads.
 int upload_small(r3n_ctx *c, void *dst, const void *src, size_t bytes) {
-    if (bytes > r3n_ctx::kStageSlotBytes || !c->stage) {
+    if (bytes > r3n_ctx::kStageSlotBytes || !c->stage.p) {
         HIP_TRY(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream));
         HIP_WAIT(c, hipStreamSynchronize(c->stream));
         return R3N_OK;
@@ -394,7 +400,7 @@ int upload_small(r3n_ctx *c, void *dst, const void *src, size_t bytes) {
         HIP_WAIT(c, hipEventSynchronize(c->stage_half_done[half]));
         c->stage_half_pending[half] = false;
     }
-    uint8_t *h = c->stage + (size_t)slot * r3n_ctx::kStageSlotBytes;
+    uint8_t *h = c->stage.as<uint8_t>() + (size_t)slot * r3n_ctx::kStageSlotBytes;
     std::memcpy(h, src, bytes);
     HIP_TRY(c, hipMemcpyAsync(dst, h, bytes, hipMemcpyHostToDevice, c->stream));
     ++c->main_epoch;
@@ -415,16 +421,10 @@ int upload_bulk(r3n_ctx *c, void *dst, const void *src, size_t bytes) {
         HIP_WAIT(c, hipEventSynchronize(b.ev));
         b.pending = false;
     }
-    if (b.bytes < bytes) {
-        if (b.p) (void)hipHostFree(b.p);
-        b.p = nullptr; b.bytes = 0;
-        const size_t want = bytes + bytes / 4;
-        HIP_TRY(c, hipHostMalloc((void **)&b.p, want, hipHostMallocDefault));
-        b.bytes = want;
-    }
-    if (!b.ev) HIP_TRY(c, hipEventCreateWithFlags(&b.ev, hipEventDisableTiming));
-    std::memcpy(b.p, src, bytes);
-    HIP_TRY(c, hipMemcpyAsync(dst, b.p, bytes, hipMemcpyHostToDevice, c->stream));
+    if (b.host.bytes < bytes) HIP_TRY(c, b.host.alloc(bytes + bytes / 4, hipHostMallocDefault));
+    if (!b.ev) HIP_TRY(c, b.ev.create(hipEventDisableTiming));
+    std::memcpy(b.host.p, src, bytes);
+    HIP_TRY(c, hipMemcpyAsync(dst, b.host.p, bytes, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipEventRecord(b.ev, c->stream));
     b.pending = true;
     ++c->main_epoch;
@@ -434,23 +434,17 @@ int upload_bulk(r3n_ctx *c, void *dst, const void *src, size_t bytes) {
 // A kernel of an EARLIER call ran out of a fixed-size buffer (transparent pass: fragment nodes / work items).  Nothing on the
 // frame path reads counts back, so the condition surfaces here: at the next frame, sync or read-back.
 int check_async_status(r3n_ctx *c) {
-    if (c->status_host && c->status_host[0] != 0u) {
-        c->status_host[0] = 0u;
+    if (c->status_host.p && c->status_host.as<uint32_t>()[0] != 0u) {
+        c->status_host.as<uint32_t>()[0] = 0u;
         return fail(c, R3N_ERR_CAPACITY, "an earlier transparent pass overflowed the fragment buffer or the raster work queue (r3n_config.max_big_items); that frame's image is incomplete");
     }
     return R3N_OK;
 }
 
-#define TRY(expr)                      \
-    do {                               \
-        int _r = (expr);               \
-        if (_r != R3N_OK) return _r;   \
-    } while (0)
-
 // A vertex stage's host block (vertex_block.h) into the stage's own buffer -- ONE copy through pinned staging, no wait for the GPU --
 // and the device pointers into it.
 template <class Rec>
-int stage_wave_block(r3n_ctx *c, DevBuf &buf, const std::vector<uint32_t> &block, const vertex_block::layout &l, uint64_t total_waves,
+int stage_wave_block(r3n_ctx *c, DeviceBuffer &buf, const std::vector<uint32_t> &block, const vertex_block::layout &l, uint64_t total_waves,
                      vertex_gather::Args<Rec> &a) {
     TRY(ensure(c, buf, block.size() * 4, false, -1));
     TRY(upload_bulk(c, buf.p, block.data(), block.size() * 4));
@@ -479,15 +473,15 @@ struct Timed {
     r3n_ctx *c;
     int stage;
     hipStream_t stream;
-    hipEvent_t a = nullptr, b = nullptr;
-    Timed(r3n_ctx *ctx, int st, hipStream_t on = nullptr) : c(ctx), stage(st), stream(on ? on : ctx->stream) {
+    Event a, b;
+    Timed(r3n_ctx *ctx, int st, hipStream_t on = nullptr) : c(ctx), stage(st), stream(on ? on : (hipStream_t)ctx->stream) {
         c->stage_launches[stage]++;
         crumb(c, kStageNames[stage]);
         if (!c->timing) return;
         auto get = [&]() {
-            hipEvent_t e;
-            if (!c->event_pool.empty()) { e = c->event_pool.back(); c->event_pool.pop_back(); }
-            else (void)hipEventCreate(&e);
+            Event e;
+            if (!c->event_pool.empty()) { e = std::move(c->event_pool.back()); c->event_pool.pop_back(); }
+            else (void)e.create();
             return e;
         };
         a = get(); b = get();
@@ -500,7 +494,7 @@ struct Timed {
         }
         if (!a) return;
         (void)hipEventRecord(b, stream);
-        c->spans.push_back({a, b, stage, stream});
+        c->spans.push_back({std::move(a), std::move(b), stage, stream});
     }
 };
 
@@ -575,14 +569,6 @@ CamState *find_cam(r3n_ctx *c, r3n_camera cam, bool create) {
     if (it != c->shadows.end()) return &it->second;
     if (!create) return nullptr;
     return &c->shadows[cam];
-}
-
-void free_cam(CamState &s) {
-    DevBuf *bufs[] = {&s.own_hdr, &s.chain, &s.baked, &s.vis_flags, &s.vis_list, &s.first_entry, &s.block_sums, &s.block_off, &s.slot_base[0],
-                      &s.slot_base[1], &s.mask[0], &s.mask[1], &s.predicted[0], &s.predicted[1], &s.sub_counts[0],
-                      &s.sub_counts[1], &s.counts[0], &s.counts[1], &s.residual};
-    for (DevBuf *b : bufs)
-        if (b->p) { (void)hipFree(b->p); b->p = nullptr; b->bytes = 0; }
 }
 
 // the object slots a camera culls / draws here: its own range when it has one (a shadow view owned whole), else the context's
@@ -708,7 +694,7 @@ int refresh_tri_base(r3n_ctx *c) {
     h.object_count = c->capacity;
     h.shadow_index = 0;
     TRY(ensure(c, c->canon.own_hdr, sizeof h, false, -1));
-    c->canon.d_hdr = c->canon.own_hdr;
+    c->canon.d_hdr = DeviceSpan{c->canon.own_hdr.p, c->canon.own_hdr.bytes};
     ++c->main_epoch;  // tri_base / slot_table are rebuilt on the main stream: the lanes' rasterisers read them
     HIP_TRY(c, hipMemcpyAsync(c->canon.d_hdr.p, &h, sizeof h, hipMemcpyHostToDevice, c->stream));
     HIP_WAIT(c, hipStreamSynchronize(c->stream));  // h is a stack temporary
@@ -739,6 +725,15 @@ size_t hiz_elements(const r3n_hiz_desc &d) {
     return n;
 }
 
+// the pending spans' events go back to the pool
+void recycle_spans(r3n_ctx *c) {
+    for (auto &s : c->spans) {
+        c->event_pool.push_back(std::move(s.a));
+        c->event_pool.push_back(std::move(s.b));
+    }
+    c->spans.clear();
+}
+
 int drain_timing(r3n_ctx *c) {
     if (c->spans.empty()) return R3N_OK;
     TRY(sync_all(c));
@@ -747,10 +742,8 @@ int drain_timing(r3n_ctx *c) {
         // the span of an EMPTY launch between two events (calibrated in r3n_timing_enable) is the events' own cost: taken off, so
         // that a stage's figure is its kernels' time -- what rocprofv3's kernel trace reports -- not kernels + dispatch gaps
         if (hipEventElapsedTime(&ms, s.a, s.b) == hipSuccess) c->stage_ms[s.stage] += std::max(0.0, (double)ms - c->span_overhead_ms);
-        c->event_pool.push_back(s.a);
-        c->event_pool.push_back(s.b);
     }
-    c->spans.clear();
+    recycle_spans(c);
     return R3N_OK;
 }
 
@@ -770,10 +763,8 @@ int read_timeline(r3n_ctx *c, float *out, int max) {
             out[4 * n + 0] = (float)s.stage; out[4 * n + 1] = (float)si; out[4 * n + 2] = t0; out[4 * n + 3] = t1;
             ++n;
         }
-        c->event_pool.push_back(s.a);
-        c->event_pool.push_back(s.b);
     }
-    c->spans.clear();
+    recycle_spans(c);
     return n;
 }
 
@@ -817,6 +808,12 @@ int apply_tuning(r3n_ctx *c, const char *kv) {
 // process); R3N_TUNE applies the same string at r3n_create.
 extern "C" int r3n_internal_set_tuning(r3n_ctx *c, const char *kv) { return c ? apply_tuning(c, kv) : R3N_ERR_INVALID_ARG; }
 extern "C" int r3n_internal_read_timeline(r3n_ctx *c, float *out, int max) { return c && out ? read_timeline(c, out, max) : -1; }
+// what the process holds right now (hip_owned.h): device allocations, pinned host allocations, events, streams
+extern "C" int r3n_internal_live_resources(uint64_t out[4]) {
+    if (!out) return R3N_ERR_INVALID_ARG;
+    for (int k = 0; k < 4; ++k) out[k] = hip_owned::live_resources[k].load();
+    return R3N_OK;
+}
 
 // The frame's clears in one launch: three zero fills (16-byte stores; a buffer's last < 4 words go singly).
 __global__ __launch_bounds__(256) static void k_frame_clear(uint32_t *__restrict__ a, size_t a_words, uint32_t *__restrict__ b, size_t b_words,
@@ -866,26 +863,26 @@ r3n_ctx *r3n_create(int hip_device, const r3n_config *config) {
             return nullptr;
         }
     // (stream priorities, ctx.tune.prio_*: 0 high, 1 normal, 2 low -- the runtime's range is [-1, 1])
-    e = hipStreamCreateWithPriority(&c->stream, hipStreamNonBlocking, (int)c->tune.prio_main - 1);
+    e = c->stream.create(hipStreamNonBlocking, (int)c->tune.prio_main - 1);
     if (e != hipSuccess) {
-        g_create_error = std::string("hipStreamCreate: ") + hipGetErrorString(e);
+        g_create_error = std::string("stream creation: ") + hipGetErrorString(e);
         delete c;
         return nullptr;
     }
-    if (hipHostMalloc((void **)&c->stage, (size_t)r3n_ctx::kStageSlots * r3n_ctx::kStageSlotBytes, hipHostMallocDefault) != hipSuccess ||
-        hipEventCreateWithFlags(&c->stage_half_done[0], hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->stage_half_done[1], hipEventDisableTiming) != hipSuccess) {
+    if (c->stage.alloc((size_t)r3n_ctx::kStageSlots * r3n_ctx::kStageSlotBytes, hipHostMallocDefault) != hipSuccess ||
+        c->stage_half_done[0].create(hipEventDisableTiming) != hipSuccess ||
+        c->stage_half_done[1].create(hipEventDisableTiming) != hipSuccess) {
         g_create_error = "pinned staging ring allocation failed";
         r3n_destroy(c);
         return nullptr;
     }
-    if (hipHostMalloc((void **)&c->status_host, 64, hipHostMallocMapped) != hipSuccess ||
-        hipHostGetDevicePointer((void **)&c->status_dev, c->status_host, 0) != hipSuccess) {
+    if (c->status_host.alloc(64, hipHostMallocMapped) != hipSuccess ||
+        hipHostGetDevicePointer((void **)&c->status_dev, c->status_host.p, 0) != hipSuccess) {
         g_create_error = "host-mapped status word allocation failed";
         r3n_destroy(c);
         return nullptr;
     }
-    c->status_host[0] = 0u;
+    c->status_host.as<uint32_t>()[0] = 0u;
     if (const char *eb = std::getenv("R3N_BREADCRUMBS")) {
         static std::atomic<int> n_ctx{0};
         const std::string path = std::string(eb) + ".pid" + std::to_string((long long)getpid()) + ".ctx" + std::to_string(n_ctx.fetch_add(1));
@@ -904,18 +901,18 @@ r3n_ctx *r3n_create(int hip_device, const r3n_config *config) {
         if (const uint32_t n = (uint32_t)std::strtoul(e7, nullptr, 10)) c->big_capacity = n;
     if (const char *e8 = std::getenv("R3N_FRAG_CAPACITY"))
         if (const uint32_t n = (uint32_t)std::strtoul(e8, nullptr, 10)) c->frag_capacity = n;
-    if (hipStreamCreateWithPriority(&c->shade, hipStreamNonBlocking, (int)c->tune.prio_shade - 1) != hipSuccess ||
-        hipEventCreateWithFlags(&c->vp_ev, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->shade_done[0], hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->shade_done[1], hipEventDisableTiming) != hipSuccess) {
+    if (c->shade.create(hipStreamNonBlocking, (int)c->tune.prio_shade - 1) != hipSuccess ||
+        c->vp_ev.create(hipEventDisableTiming) != hipSuccess ||
+        c->shade_done[0].create(hipEventDisableTiming) != hipSuccess ||
+        c->shade_done[1].create(hipEventDisableTiming) != hipSuccess) {
         g_create_error = "shade stream creation failed";
         r3n_destroy(c);
         return nullptr;
     }
     for (int k = 0; k < R3N_AUX_STREAMS; ++k)
-        if (hipStreamCreateWithPriority(&c->aux[k], hipStreamNonBlocking, (int)c->tune.prio_aux - 1) != hipSuccess ||
-            hipEventCreateWithFlags(&c->fork_ev[k], hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&c->join_ev[k], hipEventDisableTiming) != hipSuccess) {
+        if (c->aux[k].create(hipStreamNonBlocking, (int)c->tune.prio_aux - 1) != hipSuccess ||
+            c->fork_ev[k].create(hipEventDisableTiming) != hipSuccess ||
+            c->join_ev[k].create(hipEventDisableTiming) != hipSuccess) {
             g_create_error = "auxiliary stream creation failed";
             r3n_destroy(c);
             return nullptr;
@@ -927,14 +924,12 @@ r3n_ctx *r3n_create(int hip_device, const r3n_config *config) {
     {
         hipStream_t order[2 + R3N_AUX_STREAMS] = {c->stream, c->shade};
         for (int k = 0; k < R3N_AUX_STREAMS; ++k) order[2 + k] = c->aux[k];
-        void *probe = nullptr;
-        if (hipMalloc(&probe, 256) == hipSuccess) {
+        DeviceBuffer probe;
+        if (probe.alloc(256) == hipSuccess)
             for (hipStream_t st : order) {
-                (void)hipMemsetAsync(probe, 0, 256, st);
+                (void)hipMemsetAsync(probe.p, 0, 256, st);
                 (void)hipStreamSynchronize(st);
             }
-            (void)hipFree(probe);
-        }
     }
     // empty light buffers: count = 0
     bool ok = ensure(c, c->srgb_lut, R3N_SRGB_LUT_SIZE, false, -1) == R3N_OK && ensure(c, c->srgb8_decode, 512 * 4, false, -1) == R3N_OK &&
@@ -943,10 +938,9 @@ r3n_ctx *r3n_create(int hip_device, const r3n_config *config) {
     // frame-constants blocks (zero: light counts 0) and their pinned host images
     for (int k = 0; ok && k < 2; ++k) ok = ensure(c, c->fb_dev[k], r3n_ctx::kFbBytes, false, 0) == R3N_OK;
     for (int k = 0; ok && k < r3n_ctx::kFbHost; ++k)
-        ok = hipHostMalloc((void **)&c->fb_host[k], r3n_ctx::kFbBytes, hipHostMallocDefault) == hipSuccess &&
-             hipEventCreateWithFlags(&c->fb_ev[k], hipEventDisableTiming) == hipSuccess;
+        ok = c->fb_host[k].alloc(r3n_ctx::kFbBytes, hipHostMallocDefault) == hipSuccess && c->fb_ev[k].create(hipEventDisableTiming) == hipSuccess;
     if (ok) {
-        for (int k = 0; k < r3n_ctx::kFbHost; ++k) std::memset(c->fb_host[k], 0, r3n_ctx::kFbBytes);
+        for (int k = 0; k < r3n_ctx::kFbHost; ++k) std::memset(c->fb_host[k].p, 0, r3n_ctx::kFbBytes);
         c->fu.p = c->fb_dev[0].as<uint8_t>() + r3n_ctx::kFbUniforms; c->fu.bytes = 512;
         c->dir_buf.p = c->fb_dev[0].as<uint8_t>() + r3n_ctx::kFbDir; c->dir_buf.bytes = r3n_ctx::kFbShadowHdr - r3n_ctx::kFbDir;
         c->point_buf.p = c->fb_dev[0].as<uint8_t>() + r3n_ctx::kFbPoint; c->point_buf.bytes = 8448;
@@ -1009,50 +1003,9 @@ void r3n_destroy(r3n_ctx *c) {
     if (c->shade) (void)hipStreamSynchronize(c->shade);
     for (int k = 0; k < R3N_AUX_STREAMS; ++k)
         if (c->aux[k]) (void)hipStreamSynchronize(c->aux[k]);
-    for (int lane = 0; lane < 1 + R3N_QLANES; ++lane)
-        for (DevBuf *b : {&c->big_items[lane], &c->big_uv[lane]})
-            if (b->p) (void)hipFree(b->p);
-    for (int k = 0; k < r3n_ctx::kFbHost; ++k) {
-        if (c->fb_host[k]) (void)hipHostFree(c->fb_host[k]);
-        if (c->fb_ev[k]) (void)hipEventDestroy(c->fb_ev[k]);
-    }
-    DevBuf *bufs[] = {&c->mesh, &c->objects, &c->spheres, &c->obj_meta, &c->materials, &c->material_keys, &c->fb_dev[0], &c->fb_dev[1], &c->big_count_all, &c->owners,
-                      &c->tri_base, &c->slot_table, &c->skin_inputs, &c->skin_matrices, &c->skin_wave_skeleton,
-                      &c->skin_wave_first, &c->skin_joint_counts, &c->morph_block, &c->normals_block, &c->tangents_block, &c->vis, &c->hdr16, &c->out8, &c->out_f32, &c->atlas, &c->hiz, &c->alt_vis, &c->alt_atlas, &c->alt_vp_baked, &c->srgb_lut, &c->srgb_thr, &c->tex_descs, &c->tex_texels, &c->tex_level_off, &c->srgb8_decode, &c->tex_stage, &c->tex_jobs,
-                      &c->tri_rec, &c->alt_tri_rec, &c->tri_seen, &c->blend_order, &c->blend_rank_base, &c->frag_keys, &c->frag_vals, &c->frag_head,
-                      &c->frag_count, &c->samples16, &c->anim_rigs, &c->anim_joints, &c->anim_clips, &c->anim_tracks,
-                      &c->anim_times, &c->anim_values, &c->pose_requests, &c->edge_list, &c->edge_count, &c->material_feat, &c->view_lights[0],
-                      &c->view_lights[1], &c->cube_texels, &c->blend_set_slots, &c->blend_set_locations, &c->blend_sort_scratch};
-    for (DevBuf *b : bufs)
-        if (b->p) (void)hipFree(b->p);
-    free_cam(c->canon);
-    free_cam(c->viewport);
-    for (auto &kv : c->shadows) free_cam(kv.second);
-    if (c->vp_ev) (void)hipEventDestroy(c->vp_ev);
-    for (auto e : c->shade_done)
-        if (e) (void)hipEventDestroy(e);
-    if (c->shade) (void)hipStreamDestroy(c->shade);
-    for (auto &s : c->spans) { (void)hipEventDestroy(s.a); (void)hipEventDestroy(s.b); }
-    for (auto e : c->event_pool) (void)hipEventDestroy(e);
-    for (int k = 0; k < R3N_AUX_STREAMS; ++k) {
-        if (c->fork_ev[k]) (void)hipEventDestroy(c->fork_ev[k]);
-        if (c->join_ev[k]) (void)hipEventDestroy(c->join_ev[k]);
-        if (c->aux[k]) (void)hipStreamDestroy(c->aux[k]);
-    }
-    if (c->stage) (void)hipHostFree(c->stage);
-    if (c->status_host) (void)hipHostFree(c->status_host);
-    for (auto &b : c->bulk) {
-        if (b.p) (void)hipHostFree(b.p);
-        if (b.ev) (void)hipEventDestroy(b.ev);
-    }
-    for (auto e : c->stage_half_done)
-        if (e) (void)hipEventDestroy(e);
-    if (c->tex_stream) (void)hipStreamDestroy(c->tex_stream);
-    for (void *p : c->tex_retired) (void)hipFree(p);
-    for (hipEvent_t ev : c->mesh_reloc_ev)
-        if (ev) (void)hipEventDestroy(ev);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
+    if (c->tex_stream) (void)hipStreamSynchronize(c->tex_stream);
+    if (c->crumb_fd >= 0) (void)close(c->crumb_fd);
+    delete c;  // every member releases what it owns (hip_owned.h); the streams, declared first, go last
 }
 
 const char *r3n_last_error(const r3n_ctx *c) { return c ? c->err.c_str() : g_create_error.c_str(); }
@@ -1132,7 +1085,7 @@ int r3n_objects_write(r3n_ctx *c, const uint32_t *slots, const r3n_object128 *re
         // disabled for a frame before it is reused, but legal through this ABI) must not index last frame's result bits
         // with this frame's triangle numbers: it counts as "not batched last frame" (batching.rs:226).
         if (c->h_ntri[slots[i]] != 0u && nt != c->h_ntri[slots[i]] && c->viewport.has_prev) {
-            DevBuf &pb = c->viewport.slot_base[1 - c->viewport.cur];
+            DeviceBuffer &pb = c->viewport.slot_base[1 - c->viewport.cur];
             if (pb.p && (size_t)(slots[i] + 1u) * 4u <= pb.bytes)
                 HIP_TRY(c, hipMemsetAsync(pb.as<uint32_t>() + slots[i], 0xFF, 4, c->stream));
         }
@@ -1422,14 +1375,14 @@ int r3n_textures_write_encoded(r3n_ctx *c, const r3n_texture_desc32 *descs, uint
         // a block of the call's own, payload | job tables, freed before it returns: nothing payload-sized stays resident behind a
         // whole-array write (the grow-only tex_stage / tex_jobs are the update path's)
         const uint64_t jobs_at = (std::max<uint64_t>(payload_bytes, 4) + 255u) & ~255ull;
-        void *scratch = nullptr;
-        HIP_TRY(c, hipMalloc(&scratch, jobs_at + work.job_block.size() * 4u));
+        DeviceBuffer scratch;
+        HIP_TRY(c, scratch.alloc(jobs_at + work.job_block.size() * 4u));
         uint64_t launches = 0;  // (r3n_texture_stats counts the update path alone)
         hipError_t e = hipMemcpyAsync(c->tex_descs.p, internal.data(), (size_t)n * sizeof(r3n_texture_desc32), hipMemcpyHostToDevice, c->stream);
         if (e == hipSuccess)
-            e = enqueue_texture_work(c, work, payload, payload_bytes, c->stream, scratch, reinterpret_cast<uint32_t *>(static_cast<char *>(scratch) + jobs_at), launches);
+            e = enqueue_texture_work(c, work, payload, payload_bytes, c->stream, scratch.p, reinterpret_cast<uint32_t *>(scratch.as<char>() + jobs_at), launches);
         const hipError_t e2 = hipStreamSynchronize(c->stream);  // the caller owns the sources only for the duration of the call
-        (void)hipFree(scratch);
+        (void)scratch.reset();
         if (e != hipSuccess) return fail(c, R3N_ERR_HIP, std::string("textures write (encoded): ") + hipGetErrorString(e));
         if (e2 != hipSuccess) return fail(c, R3N_ERR_HIP, std::string("textures write (encoded): ") + hipGetErrorString(e2));
     }
@@ -1452,8 +1405,7 @@ static void texture_note_syncs(r3n_ctx *c) {
     c->tex_alloc.release();
     c->n_texels = c->tex_alloc.end();
     c->h_tex_hot = c->h_tex_live;
-    for (void *p : c->tex_retired) (void)hipFree(p);  // the device is idle: the free stalls nothing
-    c->tex_retired.clear();
+    c->tex_retired.clear();  // the device is idle: the frees stall nothing
 }
 
 // what the device holds for a slot: a removed (or never written) slot is a 1 x 1, one-level RGBA8 entry at pool word 0
@@ -1497,35 +1449,29 @@ static int upload_texture_slots(r3n_ctx *c, const std::vector<uint32_t> &slots, 
 // Grow-only block the texture path alone uses (payload staging, job tables); contents are not kept.  Every call that used it
 // waited for its own work, so nothing reads the old block; it is freed behind the next full wait (texture_note_syncs), because
 // hipFree waits for the whole device.
-static int grow_texture_scratch(r3n_ctx *c, DevBuf &b, size_t bytes) {
+static int grow_texture_scratch(r3n_ctx *c, DeviceBuffer &b, size_t bytes) {
     if (b.p && bytes <= b.bytes) return R3N_OK;
     const size_t want = std::max<size_t>(std::max<size_t>(bytes, 2 * b.bytes), 4096);
-    if (b.p) {
-        c->tex_retired.push_back(b.p);
-        b.p = nullptr; b.bytes = 0;
-    }
-    HIP_TRY(c, hipMalloc(&b.p, want));
-    b.bytes = want;
+    DeviceBuffer nb;
+    HIP_TRY(c, nb.alloc(want));
+    std::swap(b, nb);
+    if (nb.p) c->tex_retired.push_back(std::move(nb));
     return R3N_OK;
 }
 
 // Geometric growth of a resident buffer, contents kept: one device-to-device copy.  The caller has waited for every frame.
-static int grow_texture_resident(r3n_ctx *c, DevBuf &b, size_t bytes, size_t most) {
+static int grow_texture_resident(r3n_ctx *c, DeviceBuffer &b, size_t bytes, size_t most) {
     if (b.p && bytes <= b.bytes) return R3N_OK;
     const size_t want = std::max(bytes, std::min<size_t>(2 * b.bytes, most));
-    void *np = nullptr;
-    HIP_TRY(c, hipMalloc(&np, want));
+    DeviceBuffer nb;
+    HIP_TRY(c, nb.alloc(want));
     hipError_t e = hipSuccess;
-    if (b.p && b.bytes) e = hipMemcpyAsync(np, b.p, b.bytes, hipMemcpyDeviceToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(static_cast<char *>(np) + b.bytes, 0, want - b.bytes, c->stream);
+    if (b.p && b.bytes) e = hipMemcpyAsync(nb.p, b.p, b.bytes, hipMemcpyDeviceToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(nb.as<char>() + b.bytes, 0, want - b.bytes, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) {
-        (void)hipFree(np);
-        return fail(c, R3N_ERR_HIP, std::string("textures update: growing a buffer: ") + hipGetErrorString(e));
-    }
-    if (b.p) HIP_TRY(c, hipFree(b.p));
-    b.p = np;
-    b.bytes = want;
+    if (e != hipSuccess) return fail(c, R3N_ERR_HIP, std::string("textures update: growing a buffer: ") + hipGetErrorString(e));
+    HIP_TRY(c, b.reset());
+    b = std::move(nb);
     ++c->main_epoch;
     return R3N_OK;
 }
@@ -1551,7 +1497,7 @@ static int place_textures(r3n_ctx *c, const std::string &what, const uint32_t *s
     if (std::adjacent_find(p.touched.begin(), p.touched.end()) != p.touched.end()) return fail(c, R3N_ERR_INVALID_ARG, what + ": one slot named twice");
     p.new_table = std::max(p.table, p.touched.back() + 1u);
     HIP_TRY(c, hipSetDevice(c->device));
-    if (!c->tex_stream) HIP_TRY(c, hipStreamCreateWithFlags(&c->tex_stream, hipStreamNonBlocking));
+    if (!c->tex_stream) HIP_TRY(c, c->tex_stream.create(hipStreamNonBlocking));
     texture_note_syncs(c);
     p.syncs_before = c->sync_serial;
 
@@ -1757,19 +1703,16 @@ int r3n_sample_probe(r3n_ctx *c, uint32_t form, const r3n_sample_query40 *querie
     HIP_TRY(c, hipSetDevice(c->device));
     TRY(sync_all(c));  // texture calls run on a stream of their own: what they wrote is there now
     const TextureArgs t = texture_args(c);
-    void *dq = nullptr, *dr = nullptr;
-    int rc = R3N_OK;
+    DeviceBuffer dq, dr;
     const size_t qb = (size_t)n * sizeof(r3n_sample_query40), rb = (size_t)n * sizeof(r3n_sample_result52);
-    hipError_t e = hipMalloc(&dq, qb);
-    if (e == hipSuccess) e = hipMalloc(&dr, rb);
-    if (e == hipSuccess) e = hipMemcpyAsync(dq, queries, qb, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = (hipError_t)r3n_internal_sample_probe(&t, form, (const r3n_sample_query40 *)dq, n, (r3n_sample_result52 *)dr, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(out, dr, rb, hipMemcpyDeviceToHost, c->stream);
+    hipError_t e = dq.alloc(qb);
+    if (e == hipSuccess) e = dr.alloc(rb);
+    if (e == hipSuccess) e = hipMemcpyAsync(dq.p, queries, qb, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = (hipError_t)r3n_internal_sample_probe(&t, form, dq.as<const r3n_sample_query40>(), n, dr.as<r3n_sample_result52>(), c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(out, dr.p, rb, hipMemcpyDeviceToHost, c->stream);
     const hipError_t e2 = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess || e2 != hipSuccess) rc = fail(c, R3N_ERR_HIP, std::string("sample probe: ") + hipGetErrorString(e != hipSuccess ? e : e2));
-    if (dq) (void)hipFree(dq);
-    if (dr) (void)hipFree(dr);
-    return rc;
+    if (e != hipSuccess || e2 != hipSuccess) return fail(c, R3N_ERR_HIP, std::string("sample probe: ") + hipGetErrorString(e != hipSuccess ? e : e2));
+    return R3N_OK;
 }
 
 extern "C" int r3n_internal_move_segments(const uint32_t *block, uint64_t o_first, uint64_t o_inst, uint32_t first_wave, uint32_t waves,
@@ -1807,7 +1750,7 @@ int r3n_textures_compact(r3n_ctx *c, const r3n_texture_compact_opts *opts, r3n_t
     if ((last.src + last.words) * 4u > c->tex_texels.bytes) return fail(c, R3N_ERR_STATE, "textures compact: a live texture ends outside the texel pool");
 
     HIP_TRY(c, hipSetDevice(c->device));
-    if (!c->tex_stream) HIP_TRY(c, hipStreamCreateWithFlags(&c->tex_stream, hipStreamNonBlocking));
+    if (!c->tex_stream) HIP_TRY(c, c->tex_stream.create(hipStreamNonBlocking));
     const uint64_t syncs_before = c->sync_serial;
     TRY(sync_all(c));  // a frame in flight may read every word that moves, and every word moved over
     texture_note_syncs(c);
@@ -1986,7 +1929,7 @@ int r3n_mesh_blocks_add(r3n_ctx *c, const r3n_mesh_block24 *blocks, uint32_t n, 
     }
     if (!n) return R3N_OK;
     HIP_TRY(c, hipSetDevice(c->device));
-    if (!c->tex_stream) HIP_TRY(c, hipStreamCreateWithFlags(&c->tex_stream, hipStreamNonBlocking));
+    if (!c->tex_stream) HIP_TRY(c, c->tex_stream.create(hipStreamNonBlocking));
     mesh_note_syncs(c);
     const uint64_t syncs_before = c->sync_serial;
     texel_alloc::Pool plan = c->mesh_alloc;
@@ -2100,7 +2043,7 @@ int r3n_mesh_compact(r3n_ctx *c, const r3n_mesh_compact_opts *opts, r3n_mesh_com
     std::memcpy(block.data() + table_at, table.data(), table.size() * sizeof(mesh_reloc::Entry));
 
     HIP_TRY(c, hipSetDevice(c->device));
-    if (!c->tex_stream) HIP_TRY(c, hipStreamCreateWithFlags(&c->tex_stream, hipStreamNonBlocking));
+    if (!c->tex_stream) HIP_TRY(c, c->tex_stream.create(hipStreamNonBlocking));
     const uint64_t syncs_before = c->sync_serial;
     TRY(sync_all(c));  // a frame in flight may read every word that moves, every word moved over, and every record that is patched
     mesh_note_syncs(c);
@@ -2120,8 +2063,8 @@ int r3n_mesh_compact(r3n_ctx *c, const r3n_mesh_compact_opts *opts, r3n_mesh_com
     uint64_t launches = plan.launches.size();
     bool relocated = false;
     if (e == hipSuccess && c->capacity && c->objects.p) {
-        for (hipEvent_t &ev : c->mesh_reloc_ev)
-            if (!ev && e == hipSuccess) e = hipEventCreate(&ev);
+        for (Event &ev : c->mesh_reloc_ev)
+            if (!ev && e == hipSuccess) e = ev.create();
         if (e == hipSuccess) e = hipEventRecord(c->mesh_reloc_ev[0], c->tex_stream);
         if (e == hipSuccess) e = (hipError_t)r3n_internal_relocate_objects(c->objects.as<uint32_t>(), c->capacity, jobs + table_at, (uint32_t)table.size(), c->tex_stream);
         if (e == hipSuccess) e = hipEventRecord(c->mesh_reloc_ev[1], c->tex_stream);
@@ -2238,7 +2181,7 @@ static int frame_begin_impl(r3n_ctx *c, const r3n_frame_uniforms496 *u, uint32_t
         HIP_WAIT(c, hipEventSynchronize(c->fb_ev[hs]));
         c->fb_pending[hs] = false;
     }
-    uint8_t *host = c->fb_host[hs];
+    uint8_t *host = c->fb_host[hs].as<uint8_t>();
     std::memcpy(host + r3n_ctx::kFbUniforms, u, sizeof *u);
     if (c->h_dir.size() < 16) c->h_dir.assign(16, 0);
     if (c->h_point.size() < 16) c->h_point.assign(16, 0);
@@ -2566,7 +2509,7 @@ int r3n_animation_write(r3n_ctx *c, const r3n_anim_rig16 *rigs, uint32_t n_rigs,
     }
     HIP_TRY(c, hipSetDevice(c->device));
     TRY(sync_all(c));
-    auto put = [&](DevBuf &b, const void *src, size_t bytes) -> int {
+    auto put = [&](DeviceBuffer &b, const void *src, size_t bytes) -> int {
         TRY(ensure(c, b, std::max<size_t>(bytes, 16), false, -1));
         if (bytes) HIP_TRY(c, hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, c->stream));
         return R3N_OK;
@@ -3541,9 +3484,8 @@ int r3n_comm_destroy(r3n_ctx *c) {
     crumb(c, "comm_destroy synced");
     for (ncclComm_t *k : {&c->comm.main, &c->comm.shadow, &c->comm.rows})
         if (*k) { (void)rccl().CommDestroy(*k); *k = nullptr; }
-    for (DevBuf &b : c->comm.stage)
-        if (b.p) { (void)hipFree(b.p); b = DevBuf{}; }
-    if (c->comm.order_ev) { (void)hipEventDestroy(c->comm.order_ev); c->comm.order_ev = nullptr; }
+    for (DeviceBuffer &b : c->comm.stage) (void)b.reset();
+    c->comm.order_ev.reset();
     c->comm.order_pending = false;
     c->comm.on = false; c->comm.by_objects = false; c->comm.world = 1; c->comm.rank = 0;
     c->shard_rows = false; c->row_begin = 0; c->row_end = 0xFFFFFFFFu;
@@ -3577,7 +3519,7 @@ static int shadow_part_of(uint32_t world, uint32_t n_views, uint32_t rank, uint3
 // (the worst case above), so an order dependence between communicators shows up as a time-out there.
 static int comm_order_begin(r3n_ctx *c, hipStream_t on) {
     if (!c->tune.comm_serial) return R3N_OK;
-    if (!c->comm.order_ev) HIP_TRY(c, hipEventCreateWithFlags(&c->comm.order_ev, hipEventDisableTiming));
+    if (!c->comm.order_ev) HIP_TRY(c, c->comm.order_ev.create(hipEventDisableTiming));
     if (c->comm.order_pending) HIP_TRY(c, hipStreamWaitEvent(on, c->comm.order_ev, 0));
     return R3N_OK;
 }
@@ -3596,11 +3538,10 @@ static int comm_exchange_shadows(r3n_ctx *c, const r3n_frame_desc *d) {
     const uint32_t world = c->comm.world, rank = c->comm.rank, aw = c->atlas_w;
     for (uint32_t v = 0; v < d->n_shadow_views; ++v) {  // staging first: allocations synchronise
         const size_t want = (size_t)d->shadow_views[v].size * d->shadow_views[v].size * 4;
-        DevBuf &b = c->comm.stage[v];
+        DeviceBuffer &b = c->comm.stage[v];
         if (b.bytes < want) {
-            if (b.p) { TRY(sync_all(c)); HIP_TRY(c, hipFree(b.p)); b = DevBuf{}; }
-            HIP_TRY(c, hipMalloc(&b.p, want));
-            b.bytes = want;
+            if (b.p) { TRY(sync_all(c)); HIP_TRY(c, b.reset()); }
+            HIP_TRY(c, b.alloc(want));
         }
     }
     Timed t(c, R3N_STAGE_EXCHANGE_SHADOW, on);
@@ -3827,7 +3768,7 @@ int r3n_set_object_owners(r3n_ctx *c, const uint8_t *owners, uint32_t n, uint32_
     HIP_TRY(c, hipSetDevice(c->device));
     TRY(sync_all(c));  // world-edit rate, not per frame
     if (!owners || n == 0) {  // back to r3n_set_object_range
-        if (c->owners.p) { (void)hipFree(c->owners.p); c->owners.p = nullptr; c->owners.bytes = 0; }
+        (void)c->owners.reset();
         c->owners_n = 0;
         return R3N_OK;
     }
@@ -4176,8 +4117,8 @@ int r3n_timing_enable(r3n_ctx *c, int enable) {
         // what a timed span holds besides its kernels: the two event packets and the dispatch of a launch between them
         HIP_TRY(c, hipSetDevice(c->device));
         TRY(sync_all(c));
-        hipEvent_t ea[32], eb[32];
-        for (int k = 0; k < 32; ++k) { HIP_TRY(c, hipEventCreate(&ea[k])); HIP_TRY(c, hipEventCreate(&eb[k])); }
+        Event ea[32], eb[32];
+        for (int k = 0; k < 32; ++k) { HIP_TRY(c, ea[k].create()); HIP_TRY(c, eb[k].create()); }
         for (int k = 0; k < 32; ++k) {
             HIP_TRY(c, hipEventRecord(ea[k], c->stream));
             hipLaunchKernelGGL(k_empty, dim3(1), dim3(64), 0, c->stream);
@@ -4188,7 +4129,6 @@ int r3n_timing_enable(r3n_ctx *c, int enable) {
         for (int k = 0; k < 32; ++k) {
             float ms = 0.f;
             if (hipEventElapsedTime(&ms, ea[k], eb[k]) == hipSuccess) v.push_back(ms);
-            (void)hipEventDestroy(ea[k]); (void)hipEventDestroy(eb[k]);
         }
         std::sort(v.begin(), v.end());
         c->span_overhead_ms = v.empty() ? 0.0 : (double)v[v.size() / 2];
@@ -4257,23 +4197,23 @@ int r3n_hbm_copy_rate(r3n_ctx *c, uint64_t bytes, uint32_t repeats, double *gb_p
     if (!c || !gb_per_s || bytes < (64ull << 20) || repeats == 0) return fail(c, R3N_ERR_INVALID_ARG, "hbm_copy_rate: bytes >= 64 MiB, repeats >= 1");
     HIP_TRY(c, hipSetDevice(c->device));
     TRY(sync_all(c));
-    void *a = nullptr, *b = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
+    DeviceBuffer a, b;
+    Event e0, e1;
     const size_t n = bytes / 16;
     int rc = R3N_OK;
     float best = 0.0f;
-    if (hipMalloc(&a, n * 16) != hipSuccess || hipMalloc(&b, n * 16) != hipSuccess || hipEventCreate(&e0) != hipSuccess ||
-        hipEventCreate(&e1) != hipSuccess || hipMemsetAsync(a, 1, n * 16, c->stream) != hipSuccess) {
+    if (a.alloc(n * 16) != hipSuccess || b.alloc(n * 16) != hipSuccess || e0.create() != hipSuccess || e1.create() != hipSuccess ||
+        hipMemsetAsync(a.p, 1, n * 16, c->stream) != hipSuccess) {
         rc = fail(c, R3N_ERR_HIP, "hbm_copy_rate: scratch allocation failed");
     } else {
-        const f4v *src = (const f4v *)a;
-        f4v *dst = (f4v *)b;
+        const f4v *src = a.as<const f4v>();
+        f4v *dst = b.as<f4v>();
         const unsigned grids[4] = {256u * 4u, 256u * 8u, 256u * 16u, 256u * 32u};
         const int kVariants = 4 * 6 + 1;  // 6 kernels x 4 grids + the runtime's own copy
         for (uint32_t r = 0; r <= (uint32_t)kVariants * repeats && rc == R3N_OK; ++r) {  // first pass untimed (page mapping, clocks)
             const int v = (int)(r % (uint32_t)kVariants);
             (void)hipEventRecord(e0, c->stream);
-            if (v == kVariants - 1) (void)hipMemcpyAsync(b, a, n * 16, hipMemcpyDeviceToDevice, c->stream);
+            if (v == kVariants - 1) (void)hipMemcpyAsync(b.p, a.p, n * 16, hipMemcpyDeviceToDevice, c->stream);
             else {
                 const dim3 g(grids[v % 4]), t(256);
                 switch (v / 4) {
@@ -4294,10 +4234,6 @@ int r3n_hbm_copy_rate(r3n_ctx *c, uint64_t bytes, uint32_t repeats, double *gb_p
             }
         }
     }
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    if (a) (void)hipFree(a);
-    if (b) (void)hipFree(b);
     if (rc == R3N_OK) *gb_per_s = best > 0.0f ? 2.0 * (double)(n * 16) / ((double)best * 1e-3) / 1e9 : 0.0;
     if (rc == R3N_OK && std::getenv("R3N_VERBOSE")) std::fprintf(stderr, "r3n_hbm_copy_rate: best variant %d (kernel %d, grid %u): %.1f GB/s\n", c->hbm_best_variant, c->hbm_best_variant / 4, c->hbm_best_variant < 24 ? 256u * (4u << (c->hbm_best_variant % 4)) : 0u, *gb_per_s);
     return rc;
