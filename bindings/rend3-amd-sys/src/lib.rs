@@ -484,6 +484,17 @@ pub struct r3n_frame_desc {
 
 #[repr(C)]
 #[derive(Clone, Copy)]
+pub struct r3n_shadow_occlusion_counters {
+    pub active: u32,
+    pub predicted: u32,
+    pub deferred: u32,
+    pub dropped: u32,
+    pub survivors: u32,
+    pub capacity: u32,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
 pub struct r3n_tri_ref {
     pub object: u32,
     pub triangle: u32,
@@ -579,6 +590,7 @@ extern "C" {
     pub fn r3n_hdr_write(ctx: *mut r3n_ctx, rgba16f: *const u16, first_pixel: u64, n_pixels: u64) -> c_int;
     pub fn r3n_frame_end(ctx: *mut r3n_ctx) -> c_int;
     pub fn r3n_render_frame(ctx: *mut r3n_ctx, desc: *const r3n_frame_desc) -> c_int;
+    pub fn r3n_shadow_occlusion_stats(ctx: *mut r3n_ctx, camera: u32, out: *mut r3n_shadow_occlusion_counters) -> c_int;
     pub fn r3n_set_object_range(ctx: *mut r3n_ctx, begin: u32, end: u32) -> c_int;
     pub fn r3n_set_object_owners(ctx: *mut r3n_ctx, owners: *const u8, n: u32, rank: u32) -> c_int;
     pub fn r3n_set_shard_mode(ctx: *mut r3n_ctx, mode: u32) -> c_int;

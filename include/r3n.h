@@ -757,6 +757,18 @@ typedef struct r3n_frame_desc {
     void *exchange_user;
 } r3n_frame_desc;
 int r3n_render_frame(r3n_ctx *ctx, const r3n_frame_desc *desc);
+/*      r3n_render_frame draws the opaque key of a shadow view in two phases: triangles the previous frame's
+ *      tile minima of the view call hidden are set aside, tested against this frame's minima behind everything else, and drawn
+ *      only if they can still change a texel.  The atlas is bit for bit the one-phase atlas.  The figures of the LAST frame for one
+ *      shadow camera (waits for the frame): active = the view was drawn in two phases (a power-of-two view of at least 64 texels on
+ *      a four-texel boundary, no communicators / exchange callback / row range / bands, R3N_TUNE shadow_occlusion not 0);
+ *      predicted = phase 1 had a prediction (not on a context's first frame, nor after the view's size or anything but the
+ *      translation of its view-projection changed, nor when it moved by a fraction of a texel); deferred = triangles set aside,
+ *      dropped + survivors = deferred; capacity = records the deferred list holds (a triangle beyond it is drawn in phase 1). */
+typedef struct r3n_shadow_occlusion_counters {
+    uint32_t active, predicted, deferred, dropped, survivors, capacity;
+} r3n_shadow_occlusion_counters;
+int r3n_shadow_occlusion_stats(r3n_ctx *ctx, r3n_camera camera, r3n_shadow_occlusion_counters *out);
 
 /* ---- multi-GPU support: object-range sharding (not in the reference).
  * Only objects with slot in [begin, end) are culled/drawn by this context; buffers stay replicated.  The ranges are the CALLER's

@@ -79,6 +79,7 @@ SIGNATURES = {
     "r3n_hdr_write": (cint, [vp, vp, u64, u64]),
     "r3n_frame_end": (cint, [vp]),
     "r3n_render_frame": (cint, [vp, vp]),
+    "r3n_shadow_occlusion_stats": (cint, [vp, u32, vp]),
     "r3n_set_object_range": (cint, [vp, u32, u32]),
     "r3n_set_object_owners": (cint, [vp, vp, u32, u32]),
     "r3n_exchange_buffers": (cint, [vp, vp, vp, vp, vp]),
@@ -218,6 +219,11 @@ class MeshCounters(ctypes.Structure):
     """r3n_mesh_counters"""
     _fields_ = [(name, u64) for name in ("add_calls", "remove_calls", "compact_calls", "bytes_staged", "launches", "full_waits", "growths",
                                          "blocks_live", "live_words", "pool_words", "free_ranges", "buffer_words")]
+
+
+class ShadowOcclusionCounters(ctypes.Structure):
+    """r3n_shadow_occlusion_counters"""
+    _fields_ = [(name, u32) for name in ("active", "predicted", "deferred", "dropped", "survivors", "capacity")]
 
 
 class TextureTail16(ctypes.Structure):

@@ -153,6 +153,7 @@ struct TriSetup {
     float z[3];     // the depth plane: depth(x, y) = (z[0] * x + z[1] * y) + z[2] in viewport pixels (see setup_triangle)
     float det;      // oriented determinant (> 0 when valid)
     bool valid;
+    bool planar;    // z[] is the window-space plane through the vertices, not the homogeneous fallback (set by setup_triangle only)
 };
 
 // p[k] = clip-space position of vertex k.  Pixel-space homogeneous coords: Xh = (x + w) * W/2,
@@ -207,6 +208,7 @@ R3N_DEV void setup_triangle(const float p[3][4], float half_w, float half_h, boo
             planar = true;
         }
     }
+    ts.planar = planar;
     if (!planar) {
         ts.z[0] = ((ts.e[0][0] * zc[0] + ts.e[1][0] * zc[1]) + ts.e[2][0] * zc[2]) / det;
         ts.z[1] = ((ts.e[0][1] * zc[0] + ts.e[1][1] * zc[1]) + ts.e[2][1] * zc[2]) / det;

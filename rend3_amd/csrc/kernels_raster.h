@@ -19,6 +19,35 @@
 #include "device_math.h"
 #include "texture.h"
 
+// Shadow-view occlusion (the two-phase depth draw further down): what phase 1, the tile-min kernel and phase 2 share.
+struct r3n_deferred32 {  // a triangle phase 1 did not draw: its scan box inside the view (inclusive corners, x | y << 16) and its depth bound
+    uint32_t object, triangle, xy0, xy1;
+    float bound;
+    uint32_t _pad[3];
+};
+// The deferred list is R3N_OCC_SUBLISTS sub-lists with a counter each, chosen per wave like the work queue's sub-queues, and the
+// counters are 256 bytes apart: appended through ONE counter, the eight thousand wave-folded atomics of a launch queued up behind
+// each other at one address of the memory side (phase 1 took 72 instead of 44 us per view).
+#define R3N_OCC_SUBLISTS 32
+#define R3N_OCC_CTL_STRIDE 64   // words between two counters
+#define R3N_OCC_CTL_COUNT(parity, q) (((parity) * R3N_OCC_SUBLISTS + (q)) * R3N_OCC_CTL_STRIDE)  // phase 1 of a frame appends through
+                                // [parity]; the tile-min kernel zeroes the other set for the next frame
+#define R3N_OCC_CTL_LAST (2 * R3N_OCC_SUBLISTS * R3N_OCC_CTL_STRIDE)  // [R3N_OCC_SUBLISTS]: records per sub-list phase 2 walks (the frame's `deferred`)
+#define R3N_OCC_CTL_DROPPED (R3N_OCC_CTL_LAST + R3N_OCC_SUBLISTS)    // the last frame's other figures (r3n_shadow_occlusion_stats): dropped, ...
+#define R3N_OCC_CTL_SURVIVORS (R3N_OCC_CTL_DROPPED + 1)              // ... and drawn after all
+#define R3N_OCC_CTL_WORDS (R3N_OCC_CTL_LAST + 2 * R3N_OCC_SUBLISTS)
+struct OcclusionArgs {
+    float *pyramid;         // tile minima of the view's atlas rectangle, levels 2..6 (4^2 .. 64^2 texels), level L at occ_level_offset(L)
+    uint32_t *ctl;          // R3N_OCC_CTL_*
+    r3n_deferred32 *list;
+    uint32_t capacity;      // records ONE sub-list holds (sub-list q starts at list + q * capacity)
+    uint32_t log2_size;     // the view is (1 << log2_size)^2 texels, log2_size >= 6
+    uint32_t parity;
+    uint32_t predict;       // phase 1: the pyramid holds the previous frame's minima and the view moved by whole texels since; 0: defer nothing
+    int shift_x, shift_y;   // texels a static point moved in the view since the pyramid was built
+    float shift_z;          // and its change of depth
+};
+
 struct RasterArgs {
     const r3n_camera_header240 *hdr;
     const r3n_object128 *objects;
@@ -50,6 +79,7 @@ struct RasterArgs {
     uint32_t *frag_head;                   // per pixel sample: first node of its list, R3N_INVALID = none
     uint32_t *status;                      // host-visible: bit 0 set when nodes / work items ran out (reported by a later call)
     uint32_t row_begin, row_end;           // rows of the viewport this launch may touch: everything ([0, 0xFFFFFFFF)) unless the rank is sharded by rows
+    OcclusionArgs occ;                     // shadow views of r3n_render_frame with the two-phase draw on; zero otherwise
 };
 
 // opaque.wgsl:214-235 / depth.wgsl:98-125 (untextured paths): alpha the cutout test compares with the threshold
@@ -93,12 +123,48 @@ struct TriWork {
     bool cutout;
     float thr[3];    // device_math.h::edge_threshold of the three edges
     int x0, y0, x1, y1;
+    float bound;     // OCC instantiations: upper bound of every depth the scans can write for this triangle (occ_depth_bound), or
+                     // R3N_OCC_NEVER when the triangle is not to be deferred
 };
+#define R3N_OCC_NEVER 2.0f  // (no tile minimum exceeds 1)
+#define R3N_OCC_MAX_BOX 64  // boxes wider or taller are never deferred: the pyramid ends at 64^2 tiles
+
+// Upper bound of the depths the scans write for a triangle.  Both scans (shade_pixel, shade_pixel_cmpx) write
+// frag_depth(ts, x + 0.5, y + 0.5) for covered pixel centres inside the box [x0, x1] x [y0, y1], and only values in [0, 1].
+// frag_depth is (z0 * px + z1 * py) + z2 in f32, every operation rounded once (no contraction in this build): for fixed
+// coefficients each product is monotone in its coordinate and each sum in its operands, so the SAME expression at the corner of
+// the box picked by the signs of z0 and z1 is >= the value at every pixel of the box -- the argument block_may_cover makes for
+// the edge functions.  (Where an intermediate overflows to inf - inf the corner's value is NaN and fminf returns 1, which bounds
+// everything the scans write; a pixel whose own value is NaN is written by neither scan.)  Vertex depths are NOT such a bound:
+// on an edge-on sliver the plane at a covered centre leaves the vertices' range.
+R3N_DEV float occ_depth_bound(const TriSetup &ts, int x0, int y0, int x1, int y1) {
+    const float px = (float)(f32_positive(ts.z[0]) ? x1 : x0) + 0.5f, py = (float)(f32_positive(ts.z[1]) ? y1 : y0) + 0.5f;
+    return fminf(frag_depth(ts, px, py), 1.0f);
+}
+// first float of level L (2..6) of a pyramid over a (1 << ls)^2 view
+R3N_DEV uint32_t occ_level_offset(uint32_t ls, uint32_t L) {
+    uint32_t off = 0u;
+    for (uint32_t l = 2u; l < L; ++l) off += 1u << (2u * (ls - l));
+    return off;
+}
+// Minimum of the pyramid over a box inside the view, at most R3N_OCC_MAX_BOX texels per side: at level
+// L = max(2, ceil_log2(max(w, h))) the box touches at most 2 x 2 tiles -- four loads.
+R3N_DEV float occ_tile_min(const OcclusionArgs &o, int x0, int y0, int x1, int y1) {
+    const uint32_t m = (uint32_t)max(x1 - x0, y1 - y0);  // longest side - 1, < 64
+    const uint32_t L = max(2u, 32u - (uint32_t)__clz((int)m));
+    const float *lv = o.pyramid + occ_level_offset(o.log2_size, L);
+    const uint32_t n = o.log2_size - L;
+    const uint32_t tx0 = (uint32_t)x0 >> L, tx1 = (uint32_t)x1 >> L, r0 = ((uint32_t)y0 >> L) << n, r1 = ((uint32_t)y1 >> L) << n;
+    const float a = lv[r0 + tx0], b = lv[r0 + tx1], c = lv[r1 + tx0], d = lv[r1 + tx1];
+    return fminf(fminf(a, b), fminf(c, d));
+}
+
 
 
 // TEX: the launch may meet cutout materials whose alpha comes from the albedo texture (row N2).  The lean variant
 // (no texture code, fewer registers) is launched whenever the world has no textures or the key is not cutout.
-template <bool DEPTH_ONLY, bool TEX, bool NOCUT = false>
+// OCC: also the triangle's depth bound for the shadow views' two-phase draw (tw.bound).
+template <bool DEPTH_ONLY, bool TEX, bool NOCUT = false, bool OCC = false>
 R3N_DEV bool prepare_triangle(const RasterArgs &a, uint32_t obj, uint32_t tri, bool positive_visible, TriWork &tw) {
     const r3n_object128 &ob = a.objects[obj];
     // The record's fields this function needs in TWO loads issued together -- bytes 80..95 (first_index, index_count, material_index,
@@ -128,6 +194,13 @@ R3N_DEV bool prepare_triangle(const RasterArgs &a, uint32_t obj, uint32_t tri, b
     tw.y0 = max(tw.y0, (int)a.row_begin);
     tw.y1 = min(tw.y1, (int)min(a.row_end, a.vp_h) - 1);
     if (tw.y0 > tw.y1) return false;
+    if (OCC) {
+        // deferred only: the affine window-space plane (not the homogeneous fallback) of a triangle whose three w are exactly 1 --
+        // what an orthographic shadow view produces -- in a box the pyramid covers with four loads
+        const bool can = tw.ts.planar && p[0][3] == 1.0f && p[1][3] == 1.0f && p[2][3] == 1.0f && tw.x1 - tw.x0 < R3N_OCC_MAX_BOX &&
+                         tw.y1 - tw.y0 < R3N_OCC_MAX_BOX;
+        tw.bound = can ? occ_depth_bound(tw.ts, tw.x0, tw.y0, tw.x1, tw.y1) : R3N_OCC_NEVER;
+    }
 #pragma unroll
     for (int i = 0; i < 3; ++i) tw.thr[i] = edge_threshold(tw.ts.e[i][0], tw.ts.e[i][1]);
     // NOCUT: the launch draws the opaque key (r3n_forward picks the instantiation): what the cutout test needs -- vertex alphas,
@@ -447,9 +520,75 @@ R3N_DEV uint32_t pack_thresholds(const float thr[3]) {
 // (viewport 22.9 -> 37.6 us, shadow 43.8 -> 45.9 us per launch); an XCD-affine walk of the work queue (shadow 81.7 -> 87.1 us);
 // the record after the next one pulled into the local L2 by an unwaited vector load (81.6 -> 81.3 us, frame 1.017 -> 1.024 ms).
 
+// Shadow views, two-phase depth draw (r3n_render_frame, opaque key; DESIGN.md section 2 lists it with the other exact shortcuts).
+//   phase 1  k_raster_small<depth, OCC>: a triangle the PREVIOUS frame's tile minima (shifted by the view's motion) say is hidden
+//            is not drawn but appended to the view's deferred list with its box and depth bound; everything else is drawn as ever.
+//            The prediction is a heuristic: whatever it answers, the result is the same -- it only decides who is drawn early.
+//   then     the work items of phase 1, the cutout key's launches, and k_shadow_tile_min over what they left in the atlas
+//   phase 2  k_shadow_deferred: a record whose bound is BELOW the minimum of the tiles its box touches is dropped; the others
+//            are set up again and drawn through the same code as phase 1 (raster_prepared), their work items by one more
+//            k_raster_big.
+// Why dropping is exact: the atlas is a per-texel maximum and every stored value only grows, so minima taken after phase 1 are
+// lower bounds of every later state of their texels.  bound (occ_depth_bound) is >= every depth the scans could write for the
+// triangle, and they write inside its box only.  bound < tile minimum therefore means every fragment of the triangle is
+// strictly below what its texel already holds: no max would have changed a bit.  The lists and result bits of the cull are not
+// involved.
+// Scan of one prepared triangle: in place up to R3N_SMALL_MAX^2 px, as work items beyond.  bq: the wave's work sub-queue.
+template <bool DEPTH_ONLY, int S, bool TEX, bool SHORTA>
+R3N_DEV void raster_prepared(const RasterArgs &a, const TriWork &tw, uint32_t bq) {
+    const int bw = tw.x1 - tw.x0 + 1, bh = tw.y1 - tw.y0 + 1;
+    if (bw <= R3N_SMALL_MAX && bh <= R3N_SMALL_MAX) {
+        for (int y = tw.y0; y <= tw.y1; ++y)
+            for (int x = tw.x0; x <= tw.x1; ++x) shade_pixel<DEPTH_ONLY, R3N_PREREAD_SMALL != 0, S, TEX, false, false, SHORTA>(a, tw, x, y);
+    } else {
+        // Work items start on a multiple of R3N_ITEM_ALIGN pixels in x: the scan's blocks then sit on the target's
+        // 64-byte lines (16 depth texels, 8 keys) instead of straddling them, and one atomic instruction touches fewer lines --
+        // the work-item kernel is bound by the number of line-sized atomic requests a CU can have in flight to the memory
+        // side (profiles/r04_summary.md).  The box only limits the scan: results are unchanged.
+        const int ax0 = tw.x0 & ~(R3N_ITEM_ALIGN - 1);
+        const uint32_t tx = (uint32_t)(tw.x1 - ax0 + R3N_TILE) / R3N_TILE, ty = (uint32_t)(bh + (R3N_TILE - 1)) / R3N_TILE;
+        const uint32_t cnt = tx * ty;
+        const uint32_t start = global_add_u32(&a.big_count[bq], cnt);
+        r3n_big_item *big = a.big_items + (size_t)bq * a.big_capacity;
+        for (uint32_t t = 0; t < cnt; ++t) {
+            const uint32_t ix = t % tx, iy = t / tx;
+            // the item's box stays inside the triangle's (the scan never leaves the box the oracle scans: the boxes of
+            // triangles that cross the depth-clip planes are not supersets of their coverage); the consumer lays its block
+            // grid out from rx0 rounded down to R3N_ITEM_ALIGN, which is this column's aligned start
+            const int rx0 = max(ax0 + (int)ix * R3N_TILE, tw.x0), ry0 = tw.y0 + (int)iy * R3N_TILE;
+            const int rx1 = min(ax0 + (int)ix * R3N_TILE + (R3N_TILE - 1), tw.x1), ry1 = min(ry0 + (R3N_TILE - 1), tw.y1);
+            if (start + t < a.big_capacity) {
+                r3n_big_item it;
+#pragma unroll
+                for (int i = 0; i < 3; ++i) {
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) it.e[i][c] = tw.ts.e[i][c];
+                    it.z[i] = tw.ts.z[i];
+                }
+                it.slot1 = DEPTH_ONLY ? 0u : tw.slot1;
+                it.material = tw.material | pack_thresholds(tw.thr);  // (material indices stay below 2^29: r3n_materials_write)
+                it.xy0 = (uint32_t)rx0 | ((uint32_t)ry0 << 16);
+                it.xy1 = (uint32_t)rx1 | ((uint32_t)ry1 << 16);
+                big[start + t] = it;
+                if (tw.cutout) {  // (launch-uniform) vertex alpha, and the uvs of a textured alpha
+                    r3n_big_uv bu;
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) { bu.uv[k][0] = tw.uv[k][0]; bu.uv[k][1] = tw.uv[k][1]; bu.va[k] = tw.va[k]; }
+                    bu._pad[0] = bu._pad[1] = bu._pad[2] = 0u;
+                    a.big_uv[(size_t)bq * a.big_capacity + start + t] = bu;
+                }
+            } else {
+                // queue full: never drop work -- scan the region here (slow path)
+                for (int y = ry0; y <= ry1; ++y)
+                    for (int x = rx0; x <= rx1; ++x) shade_pixel<DEPTH_ONLY, R3N_PREREAD_SMALL != 0, S, TEX, false, false, SHORTA>(a, tw, x, y);
+            }
+        }
+    }
+}
+
 // Stage 1: one thread per list entry.  Small triangles are scanned in place; larger ones are split into
 // <= R3N_TILE x R3N_TILE px items for stage 2.
-template <bool DEPTH_ONLY, int S = 1, bool TEX = false, bool NOCUT = false, bool SHORTA = false>
+template <bool DEPTH_ONLY, int S = 1, bool TEX = false, bool NOCUT = false, bool SHORTA = false, bool OCC = false>
 R3N_DEV void raster_small_body(const RasterArgs &a) {
     // block b walks sub-list (b % R3N_SUBQ) of the region, and appends to work sub-queue (b % R3N_BIGQ)
     const uint32_t q = blockIdx.x % R3N_SUBQ;
@@ -464,61 +603,120 @@ R3N_DEV void raster_small_body(const RasterArgs &a) {
     for (uint32_t i = (blockIdx.x / R3N_SUBQ) * blockDim.x + threadIdx.x; i < n; i += stride) {
         const r3n_tri_ref8 ref = list[i];
         TriWork tw;
-        if (!prepare_triangle<DEPTH_ONLY, TEX, NOCUT>(a, ref.object, ref.triangle, positive_visible, tw)) continue;
-        const int bw = tw.x1 - tw.x0 + 1, bh = tw.y1 - tw.y0 + 1;
-        if (bw <= R3N_SMALL_MAX && bh <= R3N_SMALL_MAX) {
-            for (int y = tw.y0; y <= tw.y1; ++y)
-                for (int x = tw.x0; x <= tw.x1; ++x) shade_pixel<DEPTH_ONLY, R3N_PREREAD_SMALL != 0, S, TEX, false, false, SHORTA>(a, tw, x, y);
-        } else {
-            // Work items start on a multiple of R3N_ITEM_ALIGN pixels in x: the scan's blocks then sit on the target's
-            // 64-byte lines (16 depth texels, 8 keys) instead of straddling them, and one atomic instruction touches fewer lines --
-            // the work-item kernel is bound by the number of line-sized atomic requests a CU can have in flight to the memory
-            // side (profiles/r04_summary.md).  The box only limits the scan: results are unchanged.
-            const int ax0 = tw.x0 & ~(R3N_ITEM_ALIGN - 1);
-            const uint32_t tx = (uint32_t)(tw.x1 - ax0 + R3N_TILE) / R3N_TILE, ty = (uint32_t)(bh + (R3N_TILE - 1)) / R3N_TILE;
-            const uint32_t cnt = tx * ty;
-            const uint32_t start = global_add_u32(&a.big_count[bq], cnt);
-            r3n_big_item *big = a.big_items + (size_t)bq * a.big_capacity;
-            for (uint32_t t = 0; t < cnt; ++t) {
-                const uint32_t ix = t % tx, iy = t / tx;
-                // the item's box stays inside the triangle's (the scan never leaves the box the oracle scans: the boxes of
-                // triangles that cross the depth-clip planes are not supersets of their coverage); the consumer lays its block
-                // grid out from rx0 rounded down to R3N_ITEM_ALIGN, which is this column's aligned start
-                const int rx0 = max(ax0 + (int)ix * R3N_TILE, tw.x0), ry0 = tw.y0 + (int)iy * R3N_TILE;
-                const int rx1 = min(ax0 + (int)ix * R3N_TILE + (R3N_TILE - 1), tw.x1), ry1 = min(ry0 + (R3N_TILE - 1), tw.y1);
-                if (start + t < a.big_capacity) {
-                    r3n_big_item it;
-#pragma unroll
-                    for (int i = 0; i < 3; ++i) {
-#pragma unroll
-                        for (int c = 0; c < 3; ++c) it.e[i][c] = tw.ts.e[i][c];
-                        it.z[i] = tw.ts.z[i];
-                    }
-                    it.slot1 = DEPTH_ONLY ? 0u : tw.slot1;
-                    it.material = tw.material | pack_thresholds(tw.thr);  // (material indices stay below 2^29: r3n_materials_write)
-                    it.xy0 = (uint32_t)rx0 | ((uint32_t)ry0 << 16);
-                    it.xy1 = (uint32_t)rx1 | ((uint32_t)ry1 << 16);
-                    big[start + t] = it;
-                    if (tw.cutout) {  // (launch-uniform) vertex alpha, and the uvs of a textured alpha
-                        r3n_big_uv bu;
-#pragma unroll
-                        for (int k = 0; k < 3; ++k) { bu.uv[k][0] = tw.uv[k][0]; bu.uv[k][1] = tw.uv[k][1]; bu.va[k] = tw.va[k]; }
-                        bu._pad[0] = bu._pad[1] = bu._pad[2] = 0u;
-                        a.big_uv[(size_t)bq * a.big_capacity + start + t] = bu;
-                    }
-                } else {
-                    // queue full: never drop work -- scan the region here (slow path)
-                    for (int y = ry0; y <= ry1; ++y)
-                        for (int x = rx0; x <= rx1; ++x) shade_pixel<DEPTH_ONLY, R3N_PREREAD_SMALL != 0, S, TEX, false, false, SHORTA>(a, tw, x, y);
-                }
+        if (!prepare_triangle<DEPTH_ONLY, TEX, NOCUT, OCC>(a, ref.object, ref.triangle, positive_visible, tw)) continue;
+        if (OCC && a.occ.predict != 0u && tw.bound <= 1.0f) {
+            // phase 1 of the two-phase draw: where this box was when the pyramid was built, and what was stored there
+            const int sx0 = tw.x0 - a.occ.shift_x, sy0 = tw.y0 - a.occ.shift_y, sx1 = tw.x1 - a.occ.shift_x, sy1 = tw.y1 - a.occ.shift_y;
+            const int lim = 1 << a.occ.log2_size;
+            if (sx0 >= 0 && sy0 >= 0 && sx1 < lim && sy1 < lim && tw.bound - a.occ.shift_z < occ_tile_min(a.occ, sx0, sy0, sx1, sy1)) {
+                // (a wave-uniform counter address: the wave's appends fold into one atomic, as the work queue's do)
+                const uint32_t sub = bq % R3N_OCC_SUBLISTS;
+                const uint32_t at = global_add_u32(&a.occ.ctl[R3N_OCC_CTL_COUNT(a.occ.parity, sub)], 1u);
+                if (at < a.occ.capacity) {
+                    uint4 *rec = reinterpret_cast<uint4 *>(a.occ.list + (size_t)sub * a.occ.capacity + at);
+                    rec[0] = make_uint4(ref.object, ref.triangle,(uint32_t)tw.x0 | ((uint32_t)tw.y0 << 16), (uint32_t)tw.x1 | ((uint32_t)tw.y1 << 16));
+                    rec[1] = make_uint4(__float_as_uint(tw.bound), 0u, 0u, 0u);
+                    continue;
+                }  // list full: drawn here
             }
         }
+        raster_prepared<DEPTH_ONLY, S, TEX, SHORTA>(a, tw, bq);
     }
 }
 
-template <bool DEPTH_ONLY, int S = 1, bool TEX = false, bool NOCUT = false, bool SHORTA = false>
+template <bool DEPTH_ONLY, int S = 1, bool TEX = false, bool NOCUT = false, bool SHORTA = false, bool OCC = false>
+// (OCC: 82 vector registers, five waves per SIMD, against 80 / six of the instantiation it stands in for.  Held at 80 by a launch
+// bound of six workgroups per CU it spills two registers to scratch and the frame is the same, 0.817-0.827 against 0.818-0.822 ms:
+// left alone.)
 __global__ __launch_bounds__(256, R3N_SMALL_OCC) void k_raster_small(RasterArgs a) {
-    raster_small_body<DEPTH_ONLY, S, TEX, NOCUT, SHORTA>(a);
+    raster_small_body<DEPTH_ONLY, S, TEX, NOCUT, SHORTA, OCC>(a);
+}
+
+// Tile minima of one shadow view's atlas rectangle (r3n_render_frame, two-phase depth draw): one workgroup per 64 x 64 texels,
+// thread = one 4 x 4 tile read as four float4 rows, then 8^2 .. 64^2 through LDS.  Depths are the bits of floats in [0, 1] (0 where
+// nothing was drawn), so the float minimum is the minimum.  The view's corner and the atlas pitch are multiples of four texels
+// (the host checks).  Workgroup 0 also turns the deferred-list counters over: the set phase 1 of this frame appended through
+// becomes the counts phase 2 walks (clamped to the capacity), the other set -- the next frame's -- and the frame's figures go to zero.
+__global__ __launch_bounds__(256) void k_shadow_tile_min(const uint32_t *__restrict__ atlas, uint32_t pitch, uint32_t vp_x, uint32_t vp_y, OcclusionArgs o) {
+    __shared__ float s2[256], s3[64], s4[16], s5[4];
+    const uint32_t ls = o.log2_size, t = threadIdx.x;
+    const uint32_t bx = blockIdx.x & ((1u << (ls - 6u)) - 1u), by = blockIdx.x >> (ls - 6u);
+    {
+        const uint32_t tx = t & 15u, ty = t >> 4;
+        const uint32_t *row = atlas + (size_t)(vp_y + by * 64u + ty * 4u) * pitch + (vp_x + bx * 64u + tx * 4u);
+        float m = INFINITY;
+#pragma unroll
+        for (uint32_t r = 0; r < 4u; ++r) {
+            const float4 v = *reinterpret_cast<const float4 *>(row + (size_t)r * pitch);
+            m = fminf(m, fminf(fminf(v.x, v.y), fminf(v.z, v.w)));
+        }
+        s2[t] = m;
+        o.pyramid[occ_level_offset(ls, 2u) + ((by * 16u + ty) << (ls - 2u)) + bx * 16u + tx] = m;
+    }
+    __syncthreads();
+    if (t < 64u) {
+        const uint32_t cx = t & 7u, cy = t >> 3, at = cy * 32u + cx * 2u;
+        const float m = fminf(fminf(s2[at], s2[at + 1u]), fminf(s2[at + 16u], s2[at + 17u]));
+        s3[t] = m;
+        o.pyramid[occ_level_offset(ls, 3u) + ((by * 8u + cy) << (ls - 3u)) + bx * 8u + cx] = m;
+    }
+    __syncthreads();
+    if (t < 16u) {
+        const uint32_t cx = t & 3u, cy = t >> 2, at = cy * 16u + cx * 2u;
+        const float m = fminf(fminf(s3[at], s3[at + 1u]), fminf(s3[at + 8u], s3[at + 9u]));
+        s4[t] = m;
+        o.pyramid[occ_level_offset(ls, 4u) + ((by * 4u + cy) << (ls - 4u)) + bx * 4u + cx] = m;
+    }
+    __syncthreads();
+    if (t < 4u) {
+        const uint32_t cx = t & 1u, cy = t >> 1, at = cy * 8u + cx * 2u;
+        const float m = fminf(fminf(s4[at], s4[at + 1u]), fminf(s4[at + 4u], s4[at + 5u]));
+        s5[t] = m;
+        o.pyramid[occ_level_offset(ls, 5u) + ((by * 2u + cy) << (ls - 5u)) + bx * 2u + cx] = m;
+    }
+    __syncthreads();
+    if (t == 0u) {
+        o.pyramid[occ_level_offset(ls, 6u) + (by << (ls - 6u)) + bx] = fminf(fminf(s5[0], s5[1]), fminf(s5[2], s5[3]));
+    }
+    if (blockIdx.x == 0u && t < R3N_OCC_SUBLISTS) {
+        o.ctl[R3N_OCC_CTL_LAST + t] = min(o.ctl[R3N_OCC_CTL_COUNT(o.parity, t)], o.capacity);
+        o.ctl[R3N_OCC_CTL_COUNT(o.parity ^ 1u, t)] = 0u;
+        if (t < 2u) o.ctl[R3N_OCC_CTL_DROPPED + t] = 0u;
+    }
+}
+
+// Phase 2: one thread per deferred record, against the minima k_shadow_tile_min has just taken (a.occ.pyramid; same stream).
+// Block b walks sub-list b % R3N_OCC_SUBLISTS.  The figures go through LDS: one pair of global atomics per workgroup.
+// (Measured and not kept: collecting the workgroup's survivors in LDS so that one wave draws them -- the kernel is bound by the
+// latency of its chain of loads, 18 us per 2048^2 view either way, and the frame did not move; profiles/shadow_occlusion.md.)
+__global__ __launch_bounds__(256) void k_shadow_deferred(RasterArgs a) {
+    __shared__ uint32_t tally[2];
+    if (threadIdx.x < 2u) tally[threadIdx.x] = 0u;
+    __syncthreads();
+    const uint32_t q = blockIdx.x % R3N_OCC_SUBLISTS;
+    const uint32_t n = a.occ.ctl[R3N_OCC_CTL_LAST + q];
+    const r3n_deferred32 *list = a.occ.list + (size_t)q * a.occ.capacity;
+    const uint32_t stride = (gridDim.x / R3N_OCC_SUBLISTS) * blockDim.x;
+    const uint32_t bq = __builtin_amdgcn_readfirstlane((blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) % R3N_BIGQ);
+    const bool positive_visible = (a.hdr->flags & R3N_PCU_POSITIVE_AREA_VISIBLE) != 0u;
+    uint32_t dropped = 0u, survivors = 0u;
+    for (uint32_t i = (blockIdx.x / R3N_OCC_SUBLISTS) * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const uint4 *rec = reinterpret_cast<const uint4 *>(list + i);
+        const uint4 r = rec[0];
+        const float bound = __uint_as_float(rec[1].x);
+        if (bound < occ_tile_min(a.occ, (int)(r.z & 0xFFFFu), (int)(r.z >> 16), (int)(r.w & 0xFFFFu), (int)(r.w >> 16))) {
+            ++dropped;
+            continue;
+        }
+        ++survivors;
+        TriWork tw;
+        if (!prepare_triangle<true, false, true>(a, r.x, r.y, positive_visible, tw)) continue;  // (it was prepared before: never taken)
+        raster_prepared<true, 1, false, false>(a, tw, bq);
+    }
+    if (dropped) atomicAdd(&tally[0], dropped);
+    if (survivors) atomicAdd(&tally[1], survivors);
+    __syncthreads();
+    if (threadIdx.x < 2u && tally[threadIdx.x]) (void)global_add_u32(&a.occ.ctl[R3N_OCC_CTL_DROPPED + threadIdx.x], tally[threadIdx.x]);
 }
 // Transparent pass, stage 1 (row N3): one thread per triangle of the blend-key objects, in DRAW ORDER -- objects back
 // to front (blend_order, sorted on the host like batching.rs:146-176), triangles in index order; g is therefore

@@ -65,6 +65,16 @@ struct CamState {
     bool range_set = false;      // r3n_set_camera_object_range: this camera's own object range (multi-GPU: shadow views owned whole)
     uint32_t range_begin = 0, range_end = 0xFFFFFFFFu;
     uint32_t band_begin = 0, band_end = 0xFFFFFFFFu;  // shadow view split by rows over several ranks (r3n_render_frame, native exchange): the rows this rank rasterises
+    // Two-phase depth draw of a shadow view (kernels_raster.h, r3n_render_frame): the tile-min pyramid, the deferred list and the
+    // control words, all touched on this camera's lane only; and what the HOST knows of the pyramid's contents -- the frame whose
+    // atlas it was taken from, that frame's view-projection and size.  (The host keeps the matrix: a kernel reading it from the
+    // other frame slot's constants block could meet the next frame's head overwriting that block.)
+    DeviceBuffer occ_pyramid, occ_ctl, occ_list;
+    uint32_t occ_capacity = 0, occ_parity = 0;
+    uint64_t occ_frame = ~0ull;     // frame_no of the frame that filled occ_pyramid (and the control block's last-frame figures)
+    uint32_t occ_size = 0;
+    float occ_view_proj[16] = {};
+    uint32_t occ_predicted = 0;     // that frame's phase 1 ran with a prediction
 };
 
 std::string g_create_error;
@@ -92,6 +102,8 @@ std::string g_create_error;
 #define R3N_BIG_LDS 40960           // shadow views (tools/tune_caps.py, round 5: 40960 -- 49152 on the bench scene, 32768 on the million-object one)
 #define R3N_SMALL_LDS 24576         // the shadow views' per-triangle pass: six workgroups per CU (bench scene 0.9285 -> 0.9148 ms, round 5)
 #define R3N_VIEWPORT_BIG_LDS 49152  // viewport
+#define R3N_OCC_DEFERRED_GRID 1024  // phase 2 of the shadow views' two-phase draw: 32 workgroups per sub-list of the deferred list (four loads per record)
+#define R3N_OCC_LATE_BIG_GRID 256   // its survivors' work items: a few hundred per view
 #define R3N_QLANES R3N_AUX_STREAMS  // work queues beside the viewport's: one per auxiliary stream (a shadow view draws on lane 1 + view mod R3N_AUX_STREAMS)
 static_assert(R3N_AUX_STREAMS >= 1, "the shadow views draw on auxiliary streams");
 
@@ -128,6 +140,10 @@ struct r3n_ctx {
     bool always_fork = false;     // R3N_ALWAYS_FORK=1: the shadow lanes wait for the main stream at every fork (no epoch gate)
     bool resolve_classes = true;  // R3N_RESOLVE_CLASSES=0: the general resolve kernel for every tile (A/B, tests)
     bool fused_frame = false;  // inside r3n_render_frame: a camera's bake and object pass are ONE launch, issued at its r3n_uniform_bake
+    // r3n_render_frame's two-phase depth draw of a shadow view: occ_wanted is up around the view's opaque r3n_forward when the frame
+    // qualifies; the forward that launched phase 1 leaves its launch arguments in occ_args (occ_open) for shadow_occlusion_finish
+    bool occ_wanted = false, occ_open = false;
+    RasterArgs occ_args{};
     DeviceBuffer alt_vis, alt_atlas, alt_vp_baked;
     // Frame-constants block: FrameUniforms, the viewport's camera header, the directional-light buffer, every shadow view's camera
     // header and the point-light buffer of one frame live in ONE device block per frame slot (fu / dir_buf / point_buf / d_hdr
@@ -189,6 +205,7 @@ struct r3n_ctx {
         uint32_t resolve_lds = 0;                                           // single-sample resolve
         uint32_t big_grid = R3N_BIG_GRID, small_grid = R3N_SMALL_GRID;
         uint32_t comm_serial = 1;  // r3n_comm_init: the three communicators' collectives in ONE total order per device (comm_order_*)
+        uint32_t shadow_occlusion = 1;  // r3n_render_frame: two-phase depth draw of the shadow views (0: everything drawn in one phase)
     } tune;
     bool cutout_short_dirty = true, cutout_short = false;  // cutout_alpha_short(): census of the cutout materials' albedo maps
     bool key_census_dirty = true;
@@ -787,7 +804,7 @@ int apply_tuning(r3n_ctx *c, const char *kv) {
             {"cut_small_lds", &t.cut_small_lds, 0, 65536, 1}, {"vp_cut_small_lds", &t.vp_cut_small_lds, 0, 65536, 1}, {"cull_lds", &t.cull_lds, 0, 65000, 1}, {"vp_cull_lds", &t.vp_cull_lds, 0, 65000, 1},
             {"resolve_lds", &t.resolve_lds, 0, 61440, 1}, {"big_grid", &t.big_grid, 256, 65536, 1},
             {"small_grid", &t.small_grid, R3N_SUBQ, 32768, R3N_SUBQ}, {"timed_pipeline", &t.timed_pipeline, 0, 1, 1},
-            {"comm_serial", &t.comm_serial, 0, 1, 1}, {"prio_main", &t.prio_main, 0, 2, 1}, {"prio_shade", &t.prio_shade, 0, 2, 1}, {"prio_aux", &t.prio_aux, 0, 2, 1}};  // (read at r3n_create only)  // (a multiple of R3N_SUBQ: whole blocks per sub-list)
+            {"comm_serial", &t.comm_serial, 0, 1, 1}, {"shadow_occlusion", &t.shadow_occlusion, 0, 1, 1}, {"prio_main", &t.prio_main, 0, 2, 1}, {"prio_shade", &t.prio_shade, 0, 2, 1}, {"prio_aux", &t.prio_aux, 0, 2, 1}};  // (read at r3n_create only)  // (a multiple of R3N_SUBQ: whole blocks per sub-list)
         bool known = false;
         for (auto &k : keys)
             if (key == k.name) {
@@ -2114,6 +2131,26 @@ int r3n_mesh_stats(r3n_ctx *c, r3n_mesh_counters *out, int reset) {
     return R3N_OK;
 }
 
+int r3n_shadow_occlusion_stats(r3n_ctx *c, r3n_camera cam, r3n_shadow_occlusion_counters *out) {
+    if (!c || !out) return fail(c, R3N_ERR_INVALID_ARG, "shadow occlusion stats: null");
+    *out = r3n_shadow_occlusion_counters{};
+    CamState *s = cam == R3N_CAMERA_VIEWPORT ? nullptr : find_cam(c, cam, false);
+    if (!s) return fail(c, R3N_ERR_INVALID_ARG, "shadow occlusion stats: not a shadow camera of this context");
+    if (c->in_frame) return fail(c, R3N_ERR_STATE, "shadow occlusion stats: a frame is open");
+    if (!s->occ_ctl.p || s->occ_frame != c->frame_no) return R3N_OK;  // the last frame drew this view in one phase
+    std::vector<uint32_t> w(R3N_OCC_CTL_WORDS);
+    HIP_TRY(c, hipSetDevice(c->device));
+    TRY(sync_all(c));
+    HIP_TRY(c, hipMemcpy(w.data(), s->occ_ctl.p, w.size() * 4u, hipMemcpyDeviceToHost));
+    out->active = 1;
+    out->predicted = s->occ_predicted;
+    for (uint32_t q = 0; q < R3N_OCC_SUBLISTS; ++q) out->deferred += w[R3N_OCC_CTL_LAST + q];
+    out->dropped = w[R3N_OCC_CTL_DROPPED];
+    out->survivors = w[R3N_OCC_CTL_SURVIVORS];
+    out->capacity = s->occ_capacity * R3N_OCC_SUBLISTS;
+    return R3N_OK;
+}
+
 int r3n_lights_write(r3n_ctx *c, const void *dir, uint64_t dir_bytes, const void *point, uint64_t point_bytes) {
     if (!c) return R3N_ERR_INVALID_ARG;
     // kept on the host; r3n_frame_begin uploads them into the frame's own copy (frames in flight: the previous frame's
@@ -2753,6 +2790,97 @@ static bool cutout_alpha_short(r3n_ctx *c) {
     return ok;
 }
 
+// ------------------------------------------------------------------------------------------------ shadow views: two-phase depth draw
+// (kernels_raster.h has the scheme and the proof.)  Only r3n_render_frame uses it, for the opaque key of a view that is a power of two
+// of at least 64 texels on a four-texel boundary of the atlas, in a frame without communicators, exchange callback, row range or
+// shadow bands; R3N_TUNE="shadow_occlusion=0" switches it off.  The node-by-node entry points draw in one phase.
+namespace {
+
+static bool occ_view_qualifies(const r3n_ctx *c, const CamState &s) {
+    const uint32_t n = s.vp_size;
+    return n >= 64u && (n & (n - 1u)) == 0u && n <= 32768u && (s.vp_x & 3u) == 0u && (c->atlas_w & 3u) == 0u && s.band_begin == 0u && s.band_end == 0xFFFFFFFFu;
+}
+
+// In front of phase 1: buffers, and whether the pyramid -- as the previous frame left it -- may predict.  It may when that frame
+// was the one before this, the view's size and the 3 x 3 part of its view-projection are what they were, the last row is
+// (0, 0, 0, 1) in both -- a directional light's orthographic view, under which a static point moves by the SAME amount
+// everywhere -- and that amount is within 1e-3 of whole texels.  Otherwise nothing is deferred and the frame is the one-phase frame.
+static int shadow_occlusion_begin(r3n_ctx *c, CamState &s, RasterArgs &a) {
+    const uint32_t n = s.vp_size;
+    uint32_t ls = 0;
+    while ((1u << ls) < n) ++ls;
+    size_t floats = 0;
+    for (uint32_t l = 2; l <= 6; ++l) floats += (size_t)1 << (2u * (ls - l));
+    // records per sub-list (beyond it phase 1 draws): every triangle of the key could land in one, up to 32 MB of records per view
+    const uint32_t capacity = (uint32_t)std::min<uint64_t>((uint64_t)R3N_SUBQ * a.subcap, (1u << 20) / R3N_OCC_SUBLISTS);
+    TRY(ensure(c, s.occ_pyramid, floats * 4u, false, -1));
+    TRY(ensure(c, s.occ_ctl, R3N_OCC_CTL_WORDS * 4u, false, 0));
+    if (capacity > s.occ_capacity || !s.occ_list.p) {
+        TRY(ensure(c, s.occ_list, (size_t)capacity * R3N_OCC_SUBLISTS * sizeof(r3n_deferred32), false, -1));
+        s.occ_capacity = (uint32_t)(s.occ_list.bytes / sizeof(r3n_deferred32) / R3N_OCC_SUBLISTS);
+    }
+    OcclusionArgs &o = a.occ;
+    o.pyramid = s.occ_pyramid.as<float>();
+    o.ctl = s.occ_ctl.as<uint32_t>();
+    o.list = s.occ_list.as<r3n_deferred32>();
+    o.capacity = s.occ_capacity;
+    o.log2_size = ls;
+    o.parity = s.occ_parity;
+    o.predict = 0u;
+    const float *m = s.hdr.view_proj, *pm = s.occ_view_proj;  // column-major: translation in [12..14], last row [3], [7], [11], [15]
+    // "What it was" for the 3 x 3 part is one part in a million of its largest entry, not bit for bit: the shadow camera is rebuilt
+    // from the snapped location every frame (host.cpp r3n_host_shadow_camera: look_at of location and location + direction), which
+    // moves the last bits of the rotation on a third to a half of the frames of a dolly, and 1e-6 of a 2048-texel view is 2e-3 texels.
+    bool same = s.occ_frame + 1u == c->frame_no && s.occ_size == n;
+    float scale = 0.0f;
+    for (int col = 0; col < 3; ++col)
+        for (int row = 0; row < 3; ++row) scale = std::max(scale, std::fabs(pm[col * 4 + row]));
+    for (int col = 0; col < 3 && same; ++col)
+        for (int row = 0; row < 3; ++row) same = same && std::fabs(m[col * 4 + row] - pm[col * 4 + row]) <= 1e-6f * scale;
+    for (const float *q : {m, pm}) same = same && q[3] == 0.0f && q[7] == 0.0f && q[11] == 0.0f && q[15] == 1.0f;
+    if (same) {
+        const float half = (float)n / 2.0f;
+        const float fx = (m[12] - pm[12]) * half, fy = -(m[13] - pm[13]) * half, fz = m[14] - pm[14];  // window x = (x + 1) W/2, y = (1 - y) H/2
+        const float rx = std::nearbyint(fx), ry = std::nearbyint(fy);
+        if (std::fabs(fx - rx) <= 1e-3f && std::fabs(fy - ry) <= 1e-3f && std::fabs(rx) < (float)n && std::fabs(ry) < (float)n && fz - fz == 0.0f) {
+            o.predict = 1u;
+            o.shift_x = (int)rx; o.shift_y = (int)ry; o.shift_z = fz;
+        }
+    }
+    s.occ_predicted = o.predict;
+    return R3N_OK;
+}
+
+// Behind the view's last launch of the frame (phase 1's work items, the cutout key): tile minima, phase 2, the survivors' work items.
+static int shadow_occlusion_finish(r3n_ctx *c, r3n_camera cam) {
+    if (!c->occ_open) return R3N_OK;
+    c->occ_open = false;
+    CamState *s = find_cam(c, cam, false);
+    if (!s) return R3N_OK;
+    RasterArgs a = c->occ_args;
+    const int lane = cam_lane(c, cam);
+    hipStream_t stream = lane_stream(c, lane);
+    // a work-queue counter block of its own (zero since the frame began, like every forward's); the items' storage is the lane's,
+    // free again: every consumer so far is in front of these launches on the lane's stream
+    const uint32_t fwd = std::min(c->forward_index_lane[lane]++, 63u);
+    a.big_count = c->big_count[lane].as<uint32_t>() + (size_t)fwd * R3N_BIGQ;
+    if (fwd == 63u) HIP_TRY(c, hipMemsetAsync(a.big_count, 0, R3N_BIGQ * 4, stream));
+    const uint32_t tiles = 1u << (a.occ.log2_size - 6u);
+    {
+        Timed t(c, R3N_STAGE_SHADOW_RASTER, stream);
+        hipLaunchKernelGGL(k_shadow_tile_min, dim3(tiles * tiles), dim3(256), 0, stream, (const uint32_t *)a.depth, a.target_pitch, a.vp_x, a.vp_y, a.occ);
+    }
+    { Timed t(c, R3N_STAGE_SHADOW_RASTER, stream); hipLaunchKernelGGL(k_shadow_deferred, dim3(R3N_OCC_DEFERRED_GRID), dim3(256), 0, stream, a); }
+    { Timed t(c, R3N_STAGE_SHADOW_RASTER_BIG, stream); hipLaunchKernelGGL((k_raster_big<true, 1, false, false, true>), dim3(R3N_OCC_LATE_BIG_GRID), dim3(256), 0, stream, a); }
+    s->occ_parity ^= 1u;
+    s->occ_frame = c->frame_no;
+    s->occ_size = s->vp_size;
+    std::memcpy(s->occ_view_proj, s->hdr.view_proj, sizeof s->occ_view_proj);
+    return check_launch(c, "shadow occlusion");
+}
+
+}  // namespace
+
 int r3n_forward(r3n_ctx *c, r3n_camera cam, uint32_t pass, uint32_t source, uint32_t key) {
     if (!c || pass > R3N_PASS_FORWARD || source > R3N_SOURCE_RESIDUAL || key > R3N_KEY_BLEND)
         return fail(c, R3N_ERR_INVALID_ARG, "forward: bad args");
@@ -2812,6 +2940,8 @@ int r3n_forward(r3n_ctx *c, r3n_camera cam, uint32_t pass, uint32_t source, uint
     a.big_uv = c->big_uv[lane].as<r3n_big_uv>();
     a.tex = texture_args(c);
     const uint32_t small_grid = c->tune.small_grid;  // multiple of R3N_SUBQ and R3N_BIGQ: 64 blocks per sub-list
+    const bool occ = !viewport && c->occ_wanted && key == R3N_KEY_OPAQUE && source == R3N_SOURCE_RESIDUAL;
+    if (occ) TRY(shadow_occlusion_begin(c, *s, a));  // (allocations fill on the main stream: in front of the fork)
     TRY(fork_lane(c, lane));
     if (fwd == 63u) HIP_TRY(c, hipMemsetAsync(a.big_count, 0, R3N_BIGQ * 4, stream));  // the first 63 calls of a lane have counters zeroed at frame begin
     a.row_begin = 0; a.row_end = 0xFFFFFFFFu;
@@ -2854,7 +2984,13 @@ int r3n_forward(r3n_ctx *c, r3n_camera cam, uint32_t pass, uint32_t source, uint
             { Timed t(c, R3N_STAGE_SHADOW_RASTER, stream); hipLaunchKernelGGL((k_raster_small<true, 1, true>), dim3(small_grid), dim3(256), c->tune.cut_small_lds, stream, a); }
             { Timed t(c, R3N_STAGE_SHADOW_RASTER_BIG, stream); hipLaunchKernelGGL((k_raster_big<true, 1, true>), dim3(c->tune.big_grid), dim3(256), c->tune.cut_big_lds, stream, a); }
         } else if (key != R3N_KEY_CUTOUT) {
-            { Timed t(c, R3N_STAGE_SHADOW_RASTER, stream); hipLaunchKernelGGL((k_raster_small<true, 1, false, true>), dim3(small_grid), dim3(256), c->tune.small_lds, stream, a); }
+            if (occ) {  // phase 1: what the previous frame's tile minima call hidden goes to the deferred list instead of the atlas
+                { Timed t(c, R3N_STAGE_SHADOW_RASTER, stream); hipLaunchKernelGGL((k_raster_small<true, 1, false, true, false, true>), dim3(small_grid), dim3(256), c->tune.small_lds, stream, a); }
+                c->occ_args = a;
+                c->occ_open = true;
+            } else {
+                { Timed t(c, R3N_STAGE_SHADOW_RASTER, stream); hipLaunchKernelGGL((k_raster_small<true, 1, false, true>), dim3(small_grid), dim3(256), c->tune.small_lds, stream, a); }
+            }
             { Timed t(c, R3N_STAGE_SHADOW_RASTER_BIG, stream); hipLaunchKernelGGL((k_raster_big<true, 1, false, false, true>), dim3(c->tune.big_grid), dim3(256), c->tune.big_lds, stream, a); }
         } else {
             { Timed t(c, R3N_STAGE_SHADOW_RASTER, stream); hipLaunchKernelGGL((k_raster_small<true, 1, false>), dim3(small_grid), dim3(256), c->tune.cut_small_lds, stream, a); }
@@ -3709,6 +3845,9 @@ int r3n_render_frame(r3n_ctx *c, const r3n_frame_desc *d) {
     }
     // skinning (base.rs:145)
     if (d->n_skeletons) TRY(r3n_skinning(c, d->skin_inputs, d->n_skeletons, d->joint_matrices, d->n_joint_matrices));
+    // two-phase depth draw of the shadow views: not where outside work is ordered against the lanes or a view is drawn in parts
+    const bool occlusion = c->tune.shadow_occlusion != 0u && !native && !d->exchange && !c->shard_rows && c->row_begin == 0u && c->row_end == 0xFFFFFFFFu;
+    c->occ_open = false;
     auto shadow_nodes = [&]() -> int {
         for (uint32_t v = 0; v < d->n_shadow_views; ++v)  // shadow_object_uniform_upload (base.rs:148)
             if (mine(v)) TRY(r3n_uniform_bake(c, v, &d->shadow_views[v].header));
@@ -3716,8 +3855,13 @@ int r3n_render_frame(r3n_ctx *c, const r3n_frame_desc *d) {
             if (mine(v)) TRY(r3n_cull(c, v));
         for (uint32_t v = 0; v < d->n_shadow_views; ++v)  // pbr_shadow_rendering (base.rs:153,366-396)
             if (mine(v)) {
-                TRY(r3n_forward(c, v, R3N_PASS_DEPTH, R3N_SOURCE_RESIDUAL, R3N_KEY_OPAQUE));
-                TRY(r3n_forward(c, v, R3N_PASS_DEPTH, R3N_SOURCE_RESIDUAL, R3N_KEY_CUTOUT));
+                const CamState *s = find_cam(c, v, false);
+                c->occ_wanted = occlusion && s && occ_view_qualifies(c, *s);
+                const int r = r3n_forward(c, v, R3N_PASS_DEPTH, R3N_SOURCE_RESIDUAL, R3N_KEY_OPAQUE);
+                c->occ_wanted = false;
+                TRY(r);
+                TRY(r3n_forward(c, v, R3N_PASS_DEPTH, R3N_SOURCE_RESIDUAL, R3N_KEY_CUTOUT));  // (in front of the tile minima: a valid occluder)
+                TRY(shadow_occlusion_finish(c, v));
             }
         if (d->exchange && d->n_shadow_views && d->exchange(d->exchange_user, R3N_EXCHANGE_SHADOW) != 0)
             return fail(c, R3N_ERR_STATE, "render_frame: the shadow exchange callback failed");

@@ -887,6 +887,12 @@ class Renderer:
         self._check(self.lib.r3n_mesh_stats(self.ctx, ctypes.byref(out), 1 if reset else 0), "r3n_mesh_stats")
         return {name: int(getattr(out, name)) for name, _ in _ffi.MeshCounters._fields_}
 
+    def shadow_occlusion_stats(self, view):
+        """Figures of the last frame's two-phase depth draw of shadow view `view` (r3n_shadow_occlusion_stats) as a dict."""
+        out = _ffi.ShadowOcclusionCounters()
+        self._check(self.lib.r3n_shadow_occlusion_stats(self.ctx, int(view), ctypes.byref(out)), "r3n_shadow_occlusion_stats")
+        return {name: int(getattr(out, name)) for name, _ in _ffi.ShadowOcclusionCounters._fields_}
+
     def readback_objects(self, first_slot=0, n=None):
         """r3n_readback_objects: the 128-byte records as the device holds them, uint32[n, 32]."""
         n = self.capacity - first_slot if n is None else int(n)
