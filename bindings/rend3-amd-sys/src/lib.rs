@@ -564,6 +564,7 @@ extern "C" {
     pub fn r3n_texture_stats(ctx: *mut r3n_ctx, out: *mut r3n_texture_counters, reset: c_int) -> c_int;
     pub fn r3n_sample_probe(ctx: *mut r3n_ctx, form: u32, queries: *const r3n_sample_query40, n: u32, out: *mut r3n_sample_result52) -> c_int;
     pub fn r3n_texture_cubes_write(ctx: *mut r3n_ctx, descs: *const r3n_texture_desc32, n_cubes: u32, texels: *const u32, n_texels: u64) -> c_int;
+    pub fn r3n_texture_cubes_write_encoded(ctx: *mut r3n_ctx, descs: *const r3n_texture_desc32, n_cubes: u32, payload: *const c_void, payload_bytes: u64) -> c_int;
     pub fn r3n_skybox_set(ctx: *mut r3n_ctx, cube_id: u32) -> c_int;
     pub fn r3n_blend_order_write(ctx: *mut r3n_ctx, objects_back_to_front: *const u32, n: u32) -> c_int;
     pub fn r3n_blend_objects_write(ctx: *mut r3n_ctx, slots: *const u32, locations: *const f32, n: u32) -> c_int;
@@ -618,6 +619,7 @@ extern "C" {
     pub fn r3n_readback_joint_matrices(ctx: *mut r3n_ctx, first_matrix: u32, dst: *mut f32, n_matrices: u32) -> c_int;
     pub fn r3n_readback_texture_descs(ctx: *mut r3n_ctx, descs: *mut r3n_texture_desc32, capacity: u32, n_slots: *mut u32) -> c_int;
     pub fn r3n_readback_texels(ctx: *mut r3n_ctx, first_texel: u64, rgba8: *mut u32, n_texels: u64) -> c_int;
+    pub fn r3n_readback_cube_face(ctx: *mut r3n_ctx, cube: u32, level: u32, face: u32, dst: *mut c_void, words: u64, pool_class: *mut u32) -> c_int;
     pub fn r3n_readback_visibility(ctx: *mut r3n_ctx, keys: *mut u64) -> c_int;
     pub fn r3n_readback_depth(ctx: *mut r3n_ctx, depth: *mut f32) -> c_int;
     pub fn r3n_readback_hiz(ctx: *mut r3n_ctx, pyramid: *mut f32, count: u64) -> c_int;

@@ -533,6 +533,24 @@ int r3n_sample_probe(r3n_ctx *ctx, uint32_t form, const r3n_sample_query40 *quer
  *      Synchronises.  A skybox bound to a cube that no longer exists (r3n_skybox_set) is unbound. */
 int r3n_texture_cubes_write(r3n_ctx *ctx, const r3n_texture_desc32 *descs, uint32_t n_cubes, const uint32_t *texels,
                             uint64_t n_texels);
+/*      The same array from ENCODED faces with their mip chains: Renderer::add_texture_cube with any TextureFormat and
+ *      MipmapCount::Specific(n), MipmapSource::Uploaded (TextureManager::add(.., cube = true), rend3/src/managers/texture.rs:98-196).
+ *      Replaces the whole cube array like r3n_texture_cubes_write.  A cube is width == height == N, `mips` levels, in any format
+ *      r3n_textures_write_encoded accepts.  desc.offset = byte offset in `payload` of face +X level 0, 4-byte aligned; the layout is
+ *      the reference's LayerMajor: for face +X, -X, +Y, -Y, +Z, -Z its levels 0 .. mips - 1 back to back, every level in its
+ *      format's own byte count (block formats: ceil(n / 4)^2 blocks), level k of extent n_k = max(1, N >> k).
+ *      Refused before anything changes: width != height, N == 0 or N > 16384, more mips than the extent has, a face outside
+ *      `payload`, a misaligned offset, an unknown format id -> R3N_ERR_INVALID_ARG; stored_mips neither 0 nor mips ->
+ *      R3N_ERR_UNSUPPORTED (a cube's chain is never generated: the reference asserts it, texture.rs:147); a cube pool beyond 2^32
+ *      words, or a job family beyond 2^31 wave slots -> R3N_ERR_CAPACITY.  Inside a frame -> R3N_ERR_STATE.
+ *      Every (cube, face, level) is decoded on the device by the kernels of the 2D path (at most four launches for the call) into a
+ *      scratch block that is freed before the call returns; one further launch builds the bordered faces (csrc/skybox.h).  The
+ *      formats that decode to f32 (R3N_TEXTURE_R8_SNORM and above: BC6H, the float and the 16-bit formats ...) cost 16 bytes per
+ *      texel, as in the 2D pool; all others 4.  Synchronises.  A skybox bound to a cube that no longer exists is unbound.  The
+ *      skybox node selects the level from the direction's screen-space differences and filters trilinearly;
+ *      a one-level RGBA8 cube gives the same device words and frames through either entry. */
+int r3n_texture_cubes_write_encoded(r3n_ctx *ctx, const r3n_texture_desc32 *descs, uint32_t n_cubes, const void *payload,
+                                    uint64_t payload_bytes);
 /*      SkyboxRoutine::set_background_texture (rend3-routine/src/skybox.rs): cube_id 0 = no skybox, i + 1 = cube i of the array
  *      above; an id past the array -> R3N_ERR_INVALID_ARG.  Between frames only (R3N_ERR_STATE inside one). */
 int r3n_skybox_set(r3n_ctx *ctx, uint32_t cube_id);
@@ -895,6 +913,11 @@ int r3n_readback_texture_descs(r3n_ctx *ctx, r3n_texture_desc32 *descs, uint32_t
 int r3n_readback_texels(r3n_ctx *ctx, uint64_t first_texel, uint32_t *rgba8, uint64_t n_texels); /* the decoded RGBA8 texel pool (after
                                                                                          r3n_textures_write_encoded: texture i's levels back to back, textures
                                                                                          in array order, each starting on a 4-texel boundary) */
+/* Diagnostic: bordered face `face` (0 .. 5: +X, -X, +Y, -Y, +Z, -Z) of level `level` of cube `cube` as the device holds it:
+ * (n_level + 2)^2 texels, row-major, the four corner texels zero.  *pool_class (may be NULL) = 0 / 1: one RGBA8 word per texel
+ * (Rgba8Unorm / Rgba8UnormSrgb), 2: four f32 words per texel.  `words` = the 32-bit words `dst` has room for.  A cube, level or
+ * face that does not exist, or a `dst` shorter than the face -> R3N_ERR_INVALID_ARG. */
+int r3n_readback_cube_face(r3n_ctx *ctx, uint32_t cube, uint32_t level, uint32_t face, void *dst, uint64_t words, uint32_t *pool_class);
 int r3n_readback_visibility(r3n_ctx *ctx, uint64_t *keys);  /* width*height*samples, a pixel's samples contiguous */
 int r3n_readback_depth(r3n_ctx *ctx, float *depth);         /* width*height, from the visibility keys (min over samples) */
 int r3n_readback_hiz(r3n_ctx *ctx, float *pyramid, uint64_t count); /* all mips, mip0 first */

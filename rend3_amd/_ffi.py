@@ -53,6 +53,7 @@ SIGNATURES = {
     "r3n_texture_stats": (cint, [vp, vp, cint]),
     "r3n_sample_probe": (cint, [vp, u32, vp, u32, vp]),
     "r3n_texture_cubes_write": (cint, [vp, vp, u32, vp, u64]),
+    "r3n_texture_cubes_write_encoded": (cint, [vp, vp, u32, vp, u64]),
     "r3n_skybox_set": (cint, [vp, u32]),
     "r3n_animation_write": (cint, [vp, vp, u32, vp, u32, vp, u32, vp, u32, vp, u32, vp, u32]),
     "r3n_pose_skeletons": (cint, [vp, vp, u32]),
@@ -107,6 +108,7 @@ SIGNATURES = {
     "r3n_readback_objects": (cint, [vp, u32, vp, u32]),
     "r3n_readback_texture_descs": (cint, [vp, vp, u32, vp]),
     "r3n_readback_texels": (cint, [vp, u64, vp, u64]),
+    "r3n_readback_cube_face": (cint, [vp, u32, u32, u32, vp, u64, vp]),
     "r3n_readback_joint_matrices": (cint, [vp, u32, vp, u32]),
     "r3n_readback_visibility": (cint, [vp, vp]),
     "r3n_readback_depth": (cint, [vp, vp]),

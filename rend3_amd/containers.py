@@ -8,6 +8,9 @@ TextureFormats a float-sampled texture binding cannot hold or this library has n
 EAC, ASTC) raise TextureUnsupported; formats the maps reject raise the reference's own error kinds.
 
 Host-side parsing only; decoding happens on the GPU (r3n_textures_write_encoded, csrc/texture_decode.hip).
+
+Cube maps: parse_ktx2 / parse_dds refuse them (a material cannot use one); parse_ktx2_cube / parse_dds_cube read them for
+Renderer.add_texture_cube_encoded (the skybox), with the same format maps and error kinds.
 """
 import struct
 
@@ -143,6 +146,42 @@ def parse_ktx2(data, srgb):
     return {"format": fmt, "width": w, "height": h, "levels": out}
 
 
+def parse_ktx2_cube(data, srgb):
+    """A KTX2 cube map: faceCount == 6, square, one layer, no supercompression.  Per level the file holds the six faces back to
+    back in +X, -X, +Y, -Y, +Z, -Z order, located through the level index.  Returns {"format", "width", "faces"} with
+    faces[f][k] = the bytes of face f level k, or None when `data` is not a KTX2 file."""
+    if len(data) < 80 or bytes(data[:12]) != KTX2_MAGIC:
+        return None
+    (vk, _type_size, w, h, depth, layers, faces, levels, scheme) = struct.unpack_from("<9I", data, 12)
+    fmt = map_ktx2_format(vk, srgb)
+    if fmt is None:
+        raise TextureLoadError("TextureBadKxt2Format", f"vkFormat {vk}")
+    if levels == 0:
+        raise TextureLoadError("TextureZeroLevels")
+    if layers >= 2:
+        raise TextureUnsupported("KTX2 arrays of cube maps")
+    if scheme != 0:
+        raise TextureUnsupported(f"KTX2 supercompression scheme {scheme}")
+    if faces != 6:
+        raise TextureUnsupported(f"KTX2 with {faces} face(s) is not a whole cube map")
+    if w != h or w == 0 or depth != 0:
+        raise TextureUnsupported("KTX2 cube map whose faces are not square")
+    index = 80
+    if len(data) < index + 24 * levels:
+        return None
+    out = [[] for _ in range(6)]
+    for k in range(levels):
+        off, length, _unc = struct.unpack_from("<3Q", data, index + 24 * k)
+        if off + length > len(data):
+            return None
+        n = level_bytes(fmt, max(1, w >> k), max(1, w >> k))
+        if length != 6 * n:
+            raise TextureLoadError("TextureDecode", f"KTX2 cube level {k}: {length} bytes, expected {6 * n}")
+        for f in range(6):
+            out[f].append(bytes(data[off + f * n:off + (f + 1) * n]))
+    return {"format": fmt, "width": w, "faces": out}
+
+
 # ---------------------------------------------------------------------------------------------- DDS
 _DXGI = {  # map_dxgi_format; typeless members of a family behave like its unorm one
     27: ("rgba",), 28: ("rgba",), 29: ("rgba",), 48: ("rg",), 49: ("rg",), 60: ("r",), 61: ("r",),
@@ -244,6 +283,64 @@ def parse_dds(data, srgb):
         offset += n
     del layers
     return {"format": fmt, "width": w, "height": h, "levels": out}
+
+
+DDS_CUBEMAP, DDS_CUBEMAP_ALLFACES = 0x200, 0xFC00  # DDSCAPS2_CUBEMAP, the six DDSCAPS2_CUBEMAP_POSITIVEX .. NEGATIVEZ bits
+
+
+def parse_dds_cube(data, srgb):
+    """A DDS cube map: the legacy cube-map caps with all six faces, or the DX10 header's cube flag with arraySize == 1.  Per face
+    (+X, -X, +Y, -Y, +Z, -Z) the file holds its levels back to back.  Returns {"format", "width", "faces"} with faces[f][k] = the
+    bytes of face f level k, or None when `data` is not a DDS file."""
+    if len(data) < 128 or bytes(data[:4]) != b"DDS ":
+        return None
+    (size, flags, h, w, _pitch, _depth, mips) = struct.unpack_from("<7I", data, 4)
+    if size != 124:
+        return None
+    (pf_size, pf_flags, fourcc, bits, rm, gm, bm, am) = struct.unpack_from("<II4s5I", data, 76)
+    if pf_size != 32:
+        return None
+    (caps2,) = struct.unpack_from("<I", data, 112)
+    offset = 128
+    if pf_flags & 0x4 and fourcc == b"DX10":
+        if len(data) < 148:
+            return None
+        (dxgi, dim, misc, array_size, _misc2) = struct.unpack_from("<5I", data, 128)
+        offset = 148
+        fmt = map_dxgi_format(dxgi, srgb)
+        if fmt is None:
+            raise TextureLoadError("TextureBadDxgiFormat", f"DXGI format {dxgi}")
+        if dim != 3 or not misc & 0x4:
+            raise TextureUnsupported("DDS without the cube flag is not a cube map")
+        if array_size != 1:
+            raise TextureUnsupported("DDS arrays of cube maps")
+    else:
+        name = _d3d_format(pf_flags, fourcc, bits, rm, gm, bm, am)
+        if name is None:
+            raise TextureLoadError("TextureBadD3DFormat", f"pixel format flags {pf_flags:#x} fourcc {fourcc!r}")
+        fmt = map_d3d_format(name, srgb)
+        if fmt is None:
+            raise TextureLoadError("TextureBadD3DFormat", name)
+        if not caps2 & DDS_CUBEMAP:
+            raise TextureUnsupported("DDS without the cube-map caps is not a cube map")
+    if caps2 & DDS_CUBEMAP and caps2 & DDS_CUBEMAP_ALLFACES != DDS_CUBEMAP_ALLFACES:
+        raise TextureUnsupported("DDS partial cube map")
+    if w != h or w == 0:
+        raise TextureUnsupported("DDS cube map whose faces are not square")
+    levels = mips if flags & 0x20000 else 1
+    if levels == 0:
+        raise TextureLoadError("TextureZeroLevels")
+    out = []
+    for f in range(6):
+        face = []
+        for k in range(levels):
+            n = level_bytes(fmt, max(1, w >> k), max(1, w >> k))
+            if offset + n > len(data):
+                raise TextureLoadError("TextureTooManyLayers", "DDS data shorter than its header says")
+            face.append(bytes(data[offset:offset + n]))
+            offset += n
+        out.append(face)
+    return {"format": fmt, "width": w, "faces": out}
 
 
 def generate_mips_allowed(fmt):

@@ -21,6 +21,7 @@
 #define R3N_SHADE_DECL_ONLY
 #include "kernels_shade.h"
 #include "skybox.h"
+#include "cube_faces.h"
 #include "blend_sort.h"
 #include "mesh_reloc.h"
 #include "morph.h"
@@ -278,7 +279,8 @@ struct r3n_ctx {
     r3n_mesh_counters mesh_stats{};
     Event mesh_reloc_ev[2];  // around the relocation kernel (r3n_mesh_compact_result::relocate_ns)
     // cube textures + the skybox node (skybox.h): the bordered faces of every cube, where each cube starts, which one is bound
-    struct Cube { size_t first_word; uint32_t n, srgb; };
+    // (cls: 0 Rgba8Unorm words, 1 Rgba8UnormSrgb words, 2 four f32 per texel; the levels lie as cube_faces.h lays them out)
+    struct Cube { size_t first_word; uint32_t n, srgb, mips = 1, cls = 0; };
     DeviceBuffer cube_texels;
     std::vector<Cube> cubes;
     uint32_t sky_cube = 0;            // r3n_skybox_set: 0 = none, i + 1 = cubes[i]
@@ -1266,6 +1268,11 @@ extern "C" int r3n_internal_generate_mip_f32(uint32_t format, uint32_t sw, uint3
 extern "C" int r3n_internal_decode_jobs(uint32_t family, const uint32_t *block, uint64_t o_first, uint64_t o_inst, uint32_t total_waves,
                                         const void *staged, uint32_t *pool, hipStream_t stream);
 
+// the RGBA8-decoded formats whose pool words are sRGB-encoded
+static bool format_is_srgb(uint32_t format) {
+    return format == R3N_TEXTURE_RGBA8_UNORM_SRGB || format == R3N_TEXTURE_BGRA8_UNORM_SRGB || format == R3N_TEXTURE_BC1_RGBA_UNORM_SRGB ||
+           format == R3N_TEXTURE_BC2_RGBA_UNORM_SRGB || format == R3N_TEXTURE_BC3_RGBA_UNORM_SRGB || format == R3N_TEXTURE_BC7_RGBA_UNORM_SRGB;
+}
 // One descriptor of r3n_textures_write_encoded / r3n_textures_update (`what` names the call in the message): validates it against
 // the payload and gives the descriptor the device holds (pool format class, offset still to be placed) and its pool words.
 static int check_encoded_desc(r3n_ctx *c, const std::string &what, const r3n_texture_desc32 &d, uint64_t payload_bytes, r3n_texture_desc32 &internal,
@@ -1286,9 +1293,7 @@ static int check_encoded_desc(r3n_ctx *c, const std::string &what, const r3n_tex
     words = texture_jobs::chain_words(d.width, d.height, d.mips, is_float ? 4u : 1u);
     if (end > payload_bytes) return fail(c, R3N_ERR_INVALID_ARG, what + ": levels outside the payload");
     if ((d.offset & 3u) != 0u) return fail(c, R3N_ERR_INVALID_ARG, what + ": level 0 must start on a 4-byte boundary");
-    const bool srgb = d.format == R3N_TEXTURE_RGBA8_UNORM_SRGB || d.format == R3N_TEXTURE_BGRA8_UNORM_SRGB ||
-                      d.format == R3N_TEXTURE_BC1_RGBA_UNORM_SRGB || d.format == R3N_TEXTURE_BC2_RGBA_UNORM_SRGB ||
-                      d.format == R3N_TEXTURE_BC3_RGBA_UNORM_SRGB || d.format == R3N_TEXTURE_BC7_RGBA_UNORM_SRGB;
+    const bool srgb = format_is_srgb(d.format);
     internal = d;
     internal.stored_mips = 0;
     internal.format = is_float ? R3N_POOL_FLOAT : (srgb ? R3N_TEXTURE_RGBA8_UNORM_SRGB : R3N_TEXTURE_RGBA8_UNORM);
@@ -1312,6 +1317,18 @@ struct TextureWork {
     std::vector<uint32_t> job_block;
     std::vector<GeneratedLevel> generated;
 };
+// lays the filled tables out as the ONE block: false when a family has more wave slots than its kernel counts
+static bool finish_texture_work(TextureWork &work) {
+    if (!texture_jobs::finish(work.tables)) return false;
+    size_t words = 0;
+    for (int f = 0; f < texture_jobs::FAMILIES; ++f) {
+        work.job_at[f] = words;
+        words += (work.tables[f].block.size() + 7u) & ~(size_t)7u;
+    }
+    work.job_block.assign(std::max<size_t>(words, 1), 0u);
+    for (int f = 0; f < texture_jobs::FAMILIES; ++f) std::copy(work.tables[f].block.begin(), work.tables[f].block.end(), work.job_block.begin() + work.job_at[f]);
+    return true;
+}
 // descs: the caller's (source format, byte offset in the payload); internal: what the device holds, placed.  false: a family has
 // more wave slots than its kernel counts.
 static bool plan_texture_work(const r3n_texture_desc32 *descs, const r3n_texture_desc32 *internal, uint32_t n, TextureWork &work) {
@@ -1332,22 +1349,14 @@ static bool plan_texture_work(const r3n_texture_desc32 *descs, const r3n_texture
             above = l;
         }
     }
-    if (!texture_jobs::finish(work.tables)) return false;
-    size_t words = 0;
-    for (int f = 0; f < texture_jobs::FAMILIES; ++f) {
-        work.job_at[f] = words;
-        words += (work.tables[f].block.size() + 7u) & ~(size_t)7u;
-    }
-    work.job_block.assign(std::max<size_t>(words, 1), 0u);
-    for (int f = 0; f < texture_jobs::FAMILIES; ++f) std::copy(work.tables[f].block.begin(), work.tables[f].block.end(), work.job_block.begin() + work.job_at[f]);
-    return true;
+    return finish_texture_work(work);
 }
 // Copy, decode: the payload once into `stage`, the tables into `job_dev` (the caller's blocks: payload_bytes, job_block.size() words
 // on a 32-byte boundary), at most four launches for every stored level of the call, the generated levels level by level behind
 // them.  Only enqueues, counting its kernels into `launches`; `payload` and `work` must outlive the caller's wait for `stream`.
 static hipError_t enqueue_texture_work(r3n_ctx *c, const TextureWork &work, const void *payload, uint64_t payload_bytes, hipStream_t stream, void *stage,
-                                       uint32_t *job_dev, uint64_t &launches) {
-    uint32_t *pool = c->tex_texels.as<uint32_t>();
+                                       uint32_t *job_dev, uint64_t &launches, uint32_t *into = nullptr) {
+    uint32_t *pool = into ? into : c->tex_texels.as<uint32_t>();  // (into: the cube path decodes into a block of its own)
     hipError_t e = hipMemcpyAsync(stage, payload, payload_bytes, hipMemcpyHostToDevice, stream);
     if (e == hipSuccess) e = hipMemcpyAsync(job_dev, work.job_block.data(), work.job_block.size() * 4u, hipMemcpyHostToDevice, stream);
     for (int f = 0; f < texture_jobs::FAMILIES && e == hipSuccess; ++f) {
@@ -3219,7 +3228,7 @@ int r3n_texture_cubes_write(r3n_ctx *c, const r3n_texture_desc32 *descs, uint32_
     for (uint32_t ci = 0; ci < n; ++ci) {
         const uint32_t N = descs[ci].width, P = N + 2u;
         const uint32_t *src = texels + descs[ci].offset;
-        cubes[ci] = {at, N, descs[ci].format == R3N_TEXTURE_RGBA8_UNORM_SRGB ? 1u : 0u};
+        cubes[ci] = {at, N, descs[ci].format == R3N_TEXTURE_RGBA8_UNORM_SRGB ? 1u : 0u, 1u, descs[ci].format == R3N_TEXTURE_RGBA8_UNORM_SRGB ? 1u : 0u};
         for (uint32_t f = 0; f < 6u; ++f) {
             uint32_t *dst = pool.data() + at + (size_t)f * P * P;
             for (uint32_t j = 0; j < N; ++j) std::memcpy(dst + (size_t)(j + 1u) * P + 1u, src + ((size_t)f * N + j) * N, (size_t)N * 4);
@@ -3238,6 +3247,90 @@ int r3n_texture_cubes_write(r3n_ctx *c, const r3n_texture_desc32 *descs, uint32_
     TRY(ensure(c, c->cube_texels, pool.size() * 4, false, -1));
     HIP_TRY(c, hipMemcpyAsync(c->cube_texels.p, pool.data(), pool.size() * 4, hipMemcpyHostToDevice, c->stream));
     HIP_WAIT(c, hipStreamSynchronize(c->stream));  // `pool` is a temporary
+    c->cubes = std::move(cubes);
+    if (c->sky_cube > n) c->sky_cube = 0;
+    return R3N_OK;
+}
+
+extern "C" int r3n_internal_cube_assemble(const uint32_t *block, uint64_t o_first, uint64_t o_inst, uint32_t total_waves, const uint32_t *dense,
+                                          uint32_t *pool, hipStream_t stream);
+
+// Cubes of any format with their stored chains.  Every (cube, face, level) is one decode job into a DENSE face of the call's scratch
+// block (at most four launches, the 2D path's kernels); k_cube_assemble then builds every bordered face of the call in one launch.
+int r3n_texture_cubes_write_encoded(r3n_ctx *c, const r3n_texture_desc32 *descs, uint32_t n, const void *payload, uint64_t payload_bytes) {
+    const std::string what = "texture cubes write (encoded)";
+    if (!c || (n && (!descs || !payload))) return fail(c, R3N_ERR_INVALID_ARG, what + ": null");
+    if (c->in_frame) return fail(c, R3N_ERR_STATE, what + ": inside a frame");
+    // ---- plan on the host; nothing changes before every cube has been accepted
+    std::vector<r3n_ctx::Cube> cubes(n);
+    std::vector<cube_faces::Record> recs;
+    TextureWork work;
+    uint64_t pool_words = 0, dense_words = 0, asm_waves = 0;
+    for (uint32_t ci = 0; ci < n; ++ci) {
+        const r3n_texture_desc32 &d = descs[ci];
+        if (d.format >= R3N_TEXTURE_FORMAT_COUNT) return fail(c, R3N_ERR_INVALID_ARG, what + ": unknown format id");
+        if (d.width != d.height) return fail(c, R3N_ERR_INVALID_ARG, what + ": a cube's faces are square");
+        if (!d.width || d.width > 16384u) return fail(c, R3N_ERR_INVALID_ARG, what + ": bad extent");
+        TRY(check_chain(c, what, d));
+        if (d.stored_mips && d.stored_mips != d.mips)
+            return fail(c, R3N_ERR_UNSUPPORTED, what + ": a cube carries all its levels (no MipmapSource::Generated for cubes, rend3/src/managers/texture.rs:147)");
+        if ((d.offset & 3u) != 0u) return fail(c, R3N_ERR_INVALID_ARG, what + ": face +X level 0 must start on a 4-byte boundary");
+        const uint32_t N = d.width, per_texel = texture_jobs::is_float(d.format) ? 4u : 1u;
+        uint64_t face_bytes = 0;
+        for (uint32_t k = 0; k < d.mips; ++k) face_bytes += r3n_internal_level_bytes(d.format, cube_faces::level_extent(N, k), cube_faces::level_extent(N, k));
+        if ((uint64_t)d.offset + 6u * face_bytes > payload_bytes) return fail(c, R3N_ERR_INVALID_ARG, what + ": faces outside the payload");
+        const uint64_t words = cube_faces::cube_words(N, d.mips, per_texel);
+        if (pool_words + words > 0xFFFFFFFFull) return fail(c, R3N_ERR_CAPACITY, what + ": the cube pool exceeds 2^32 words");
+        cubes[ci] = {(size_t)pool_words, N, format_is_srgb(d.format) ? 1u : 0u, d.mips, per_texel == 4u ? 2u : (format_is_srgb(d.format) ? 1u : 0u)};
+        uint64_t level_at = pool_words;
+        for (uint32_t k = 0; k < d.mips; ++k) {
+            const uint32_t nk = cube_faces::level_extent(N, k);
+            const uint64_t stride = cube_faces::dense_face_words(nk, per_texel), units = (uint64_t)(nk + 2u) * (nk + 2u);
+            for (uint32_t f = 0; f < 6u; ++f) {
+                // LayerMajor: face f's levels lie back to back
+                uint64_t src = (uint64_t)d.offset + f * face_bytes;
+                for (uint32_t l = 0; l < k; ++l) src += r3n_internal_level_bytes(d.format, cube_faces::level_extent(N, l), cube_faces::level_extent(N, l));
+                texture_jobs::add_level(work.tables, d.format, nk, nk, src, (uint32_t)(dense_words + f * stride));
+                recs.push_back(cube_faces::Record{nk, f, per_texel, (uint32_t)units, (uint32_t)dense_words, (uint32_t)stride,
+                                                  (uint32_t)(level_at + f * cube_faces::face_words(nk, per_texel)), 0u});
+                asm_waves += vertex_block::waves(units, cube_faces::UNITS_PER_WAVE);
+            }
+            dense_words += 6u * stride;  // (below the pool's words: a dense face is smaller than its bordered face)
+            level_at += cube_faces::level_words(nk, per_texel);
+        }
+        pool_words += words;
+    }
+    if (!finish_texture_work(work) || asm_waves > vertex_block::MAX_WAVES)
+        return fail(c, R3N_ERR_CAPACITY, what + ": more than 2^31 wave slots of decode or assemble work in one call");
+    std::vector<uint32_t> asm_block;
+    const vertex_block::layout asm_layout = vertex_block::lay_out(asm_block, (uint32_t)recs.size(), cube_faces::REC_WORDS, asm_waves, [&](uint32_t i) {
+        return vertex_block::waves(recs[i].units, cube_faces::UNITS_PER_WAVE);
+    });
+    if (!recs.empty()) std::memcpy(asm_block.data(), recs.data(), recs.size() * sizeof(cube_faces::Record));
+    // ---- device side
+    HIP_TRY(c, hipSetDevice(c->device));
+    TRY(sync_all(c));  // no frame may still sample the old array
+    TRY(ensure(c, c->cube_texels, std::max<uint64_t>(pool_words, 1) * 4, false, -1));
+    if (n) {
+        // a block of the call's own, payload | job tables | assemble table | dense faces, freed before the call returns
+        const uint64_t jobs_at = (std::max<uint64_t>(payload_bytes, 4) + 255u) & ~255ull;
+        const uint64_t asm_at = (jobs_at + work.job_block.size() * 4u + 255u) & ~255ull;
+        const uint64_t dense_at = (asm_at + asm_block.size() * 4u + 255u) & ~255ull;
+        DeviceBuffer scratch;
+        HIP_TRY(c, scratch.alloc(dense_at + std::max<uint64_t>(dense_words, 4) * 4u));
+        uint32_t *dense = reinterpret_cast<uint32_t *>(scratch.as<char>() + dense_at);
+        uint32_t *asm_dev = reinterpret_cast<uint32_t *>(scratch.as<char>() + asm_at);
+        uint64_t launches = 0;
+        hipError_t e = hipMemcpyAsync(asm_dev, asm_block.data(), asm_block.size() * 4u, hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess)
+            e = enqueue_texture_work(c, work, payload, payload_bytes, c->stream, scratch.p, reinterpret_cast<uint32_t *>(scratch.as<char>() + jobs_at), launches, dense);
+        if (e == hipSuccess)
+            e = (hipError_t)r3n_internal_cube_assemble(asm_dev, asm_layout.o_first, asm_layout.o_inst, (uint32_t)asm_waves, dense, c->cube_texels.as<uint32_t>(), c->stream);
+        const hipError_t e2 = hipStreamSynchronize(c->stream);  // the caller owns the sources only for the duration of the call
+        (void)scratch.reset();
+        if (e != hipSuccess) return fail(c, R3N_ERR_HIP, what + ": " + hipGetErrorString(e));
+        if (e2 != hipSuccess) return fail(c, R3N_ERR_HIP, what + ": " + hipGetErrorString(e2));
+    }
     c->cubes = std::move(cubes);
     if (c->sky_cube > n) c->sky_cube = 0;
     return R3N_OK;
@@ -3263,7 +3356,7 @@ int r3n_skybox(r3n_ctx *c) {
     a.fu = c->fu.as<r3n_frame_uniforms496>();
     a.texels = c->cube_texels.as<uint32_t>() + cube.first_word;
     a.decode = c->srgb8_decode.as<float>();
-    a.n = cube.n; a.srgb = cube.srgb;
+    a.n = cube.n; a.srgb = cube.srgb; a.mips = cube.mips;
     a.width = c->width; a.height = c->height; a.row_begin = r0; a.row_end = r1;
     a.hdr_out = c->hdr16.as<ushort4>();
     a.ldr_out = c->out8.as<uchar4>();
@@ -3276,7 +3369,7 @@ int r3n_skybox(r3n_ctx *c) {
     hipStream_t stream = c->resolve_on_shade ? c->shade : c->stream;
     {
         Timed t(c, R3N_STAGE_SKYBOX, stream);
-        HIP_TRY(c, (hipError_t)r3n_internal_skybox(&a, c->samples, stream));
+        HIP_TRY(c, (hipError_t)r3n_internal_skybox(&a, c->samples, cube.cls == 2u ? 1u : 0u, stream));
     }
     TRY(check_launch(c, "k_skybox"));
     // whatever waits for the resolve -- the frame that reuses these targets, the read-backs -- waits for the sky as well
@@ -4189,6 +4282,17 @@ int r3n_readback_texture_descs(r3n_ctx *c, r3n_texture_desc32 *descs, uint32_t c
         if (i >= c->h_tex_live.size() || !c->h_tex_live[i]) descs[i].width = descs[i].height = 0;  // the device holds a 1 x 1 stand-in
     return R3N_OK;
 }
+int r3n_readback_cube_face(r3n_ctx *c, uint32_t cube, uint32_t level, uint32_t face, void *dst, uint64_t words, uint32_t *pool_class) {
+    if (!c || !dst) return fail(c, R3N_ERR_INVALID_ARG, "readback_cube_face: null");
+    if (cube >= c->cubes.size() || face >= 6u || level >= c->cubes[cube].mips) return fail(c, R3N_ERR_INVALID_ARG, "readback_cube_face: no such cube, level or face");
+    const r3n_ctx::Cube &cb = c->cubes[cube];
+    const uint32_t per_texel = cb.cls == 2u ? 4u : 1u, nk = cube_faces::level_extent(cb.n, level);
+    const uint64_t need = cube_faces::face_words(nk, per_texel);
+    if (words < need) return fail(c, R3N_ERR_INVALID_ARG, "readback_cube_face: dst is shorter than the bordered face");
+    if (pool_class) *pool_class = cb.cls;
+    return d2h(c, dst, c->cube_texels.as<uint32_t>() + cb.first_word + cube_faces::level_start(cb.n, level, per_texel) + face * need, need * 4);
+}
+
 int r3n_readback_texels(r3n_ctx *c, uint64_t first_texel, uint32_t *rgba8, uint64_t n_texels) {
     if (!c || !rgba8 || (first_texel + n_texels) * 4 > c->tex_texels.bytes) return fail(c, R3N_ERR_INVALID_ARG, "readback_texels: range outside the texel pool");
     return d2h(c, rgba8, c->tex_texels.as<uint32_t>() + first_texel, n_texels * 4);

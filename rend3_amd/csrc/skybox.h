@@ -1,10 +1,16 @@
 // skybox.h -- the skybox node (rend3-routine/src/skybox.rs + skybox.wgsl): argument block and launcher of k_skybox (skybox.hip),
-// and the layout of the cube-texture pool r3n_texture_cubes_write builds (r3n.hip).
+// and the layout of the cube-texture pool r3n_texture_cubes_write / r3n_texture_cubes_write_encoded build (r3n.hip).
 //
 // Cube pool: every cube is six faces in layer order +X, -X, +Y, -Y, +Z, -Z, each stored WITH A ONE-TEXEL BORDER: (N + 2) x (N + 2)
-// RGBA8 words, row-major, interior texel (i, j) at (i + 1, j + 1).  The border of an edge holds the adjacent face's texels across
-// that edge (filled on the host at upload), so the seamless footprint of DESIGN section 2 is a plain fetch; the four corner words
-// of a face are never read -- the kernel forms a corner from the three texels that exist.
+// texels, row-major, interior texel (i, j) at (i + 1, j + 1).  The border of an edge holds the adjacent face's texels across
+// that edge (filled on the host by r3n_texture_cubes_write, by k_cube_assemble for the encoded entry), so the seamless footprint of
+// DESIGN section 2 is a plain fetch; the four corner texels of a face are never read -- the kernel forms a corner from the three
+// texels that exist.
+//
+// A texel is one RGBA8 word (classes 0 / 1: Rgba8Unorm / Rgba8UnormSrgb words) or four f32 words (class 2, the formats
+// texture_jobs::is_float names).  A cube with `mips` levels holds level 0's six bordered faces, then level 1's (extent
+// n_1 = max(1, N >> 1)), and so on; every level -- and, from the encoded entry, every cube -- starts on a 4-word boundary, so an
+// f32 texel is one aligned 16-byte access.  cube_faces.h has the arithmetic (level_start, face_words) and the edge table.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -14,10 +20,10 @@
 struct SkyboxArgs {
     const unsigned long long *vis;     // visibility keys, `samples` per pixel
     const r3n_frame_uniforms496 *fu;   // inv_origin_view_proj
-    const uint32_t *texels;            // the bound cube's six bordered faces
+    const uint32_t *texels;            // the bound cube: level 0's six bordered faces, then the further levels
     const float *decode;               // 512 entries: [0, 256) c / 255, [256, 512) sRGB8 -> linear (texture.h TextureArgs::decode)
     uint32_t n;                        // face extent in texels
-    uint32_t srgb;                     // 1: R3N_TEXTURE_RGBA8_UNORM_SRGB
+    uint32_t srgb;                     // 1: sRGB-encoded RGBA8 words
     uint32_t width, height, row_begin, row_end;
     ushort4 *hdr_out;                  // Rgba16Float
     uchar4 *ldr_out;                   // the fused tonemap blit, as the resolve writes it
@@ -30,9 +36,11 @@ struct SkyboxArgs {
     //                          has four equal samples whose value IS hdr_out (the box average of four equal halves is exact)
     ushort4 *samples;
     uint32_t samples_form;
+    uint32_t mips;                     // levels of the bound cube (read by the instantiations with level selection only)
 };
 #define R3N_SKY_SAMPLES_ALL 0u
 #define R3N_SKY_SAMPLES_EDGES 1u
 
-// enqueues k_skybox over rows [row_begin, row_end); samples 1 | 4.  Returns the hipError_t of the launch.
-extern "C" int r3n_internal_skybox(const SkyboxArgs *a, uint32_t samples, hipStream_t stream);
+// enqueues k_skybox over rows [row_begin, row_end); samples 1 | 4; f32_class: the cube's texels are four f32 words.  A cube with
+// one level of RGBA8 words runs the instantiation without level selection.  Returns the hipError_t of the launch.
+extern "C" int r3n_internal_skybox(const SkyboxArgs *a, uint32_t samples, uint32_t f32_class, hipStream_t stream);

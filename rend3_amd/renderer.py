@@ -1087,6 +1087,40 @@ class Renderer:
         self._cubes_dirty = True
         return len(self.cubes) - 1
 
+    def add_texture_cube_encoded(self, fmt, width, faces):
+        """Renderer::add_texture_cube with any TextureFormat and MipmapCount::Specific(n), MipmapSource::Uploaded: fmt = an
+        R3N_TEXTURE_* id (containers.py), faces[f][k] = the bytes of level k of face f, faces in layer order +X, -X, +Y, -Y, +Z,
+        -Z, every face with the same number of levels; level k is max(1, width >> k) texels square.  What
+        containers.parse_ktx2_cube / parse_dds_cube return fits: add_texture_cube_encoded(c["format"], c["width"], c["faces"]).
+        The cube array is re-sent when the next frame is evaluated (r3n_texture_cubes_write_encoded).  Returns the cube handle."""
+        from . import containers
+        fmt, width = int(fmt), int(width)
+        if not 0 <= fmt < containers.FORMAT_COUNT:
+            raise ValueError(f"add_texture_cube_encoded: unknown format id {fmt}")
+        if not 1 <= width <= 16384:
+            raise ValueError("add_texture_cube_encoded: a cube's extent is 1 .. 16384")
+        if len(faces) != 6:
+            raise ValueError("add_texture_cube_encoded: a cube has six faces")
+        mips = len(faces[0])
+        if mips < 1 or mips > width.bit_length():
+            raise ValueError(f"add_texture_cube_encoded: {mips} levels, an extent of {width} has 1 .. {width.bit_length()}")
+        kept = []
+        for f, levels in enumerate(faces):
+            if len(levels) != mips:
+                raise ValueError(f"add_texture_cube_encoded: face {f} has {len(levels)} levels, face 0 has {mips}")
+            row = []
+            for k, level in enumerate(levels):
+                level = bytes(level)
+                n = max(1, width >> k)
+                if len(level) != containers.level_bytes(fmt, n, n):
+                    raise ValueError(f"add_texture_cube_encoded: face {f} level {k} has {len(level)} bytes, "
+                                     f"{containers.FORMAT_NAMES[fmt]} {n} x {n} takes {containers.level_bytes(fmt, n, n)}")
+                row.append(level)
+            kept.append(row)
+        self.cubes.append(_EncodedCube(fmt, width, mips, kept))
+        self._cubes_dirty = True
+        return len(self.cubes) - 1
+
     def replace_texture_cubes(self, cubes):
         """Replaces the whole cube array: `cubes` = [(faces, srgb), ...]; handles are indices into it."""
         self.cubes = []
@@ -1100,8 +1134,31 @@ class Renderer:
         """SkyboxRoutine::set_background_texture(Option<TextureCubeHandle>) (rend3-routine/src/skybox.rs): None = no skybox."""
         self._background = cube
 
+    def _flush_cubes_encoded(self):
+        """the whole array through r3n_texture_cubes_write_encoded: LayerMajor payload, every cube on a 4-byte boundary"""
+        descs = np.zeros((max(len(self.cubes), 1), 8), dtype=np.uint32)
+        payload = bytearray()
+        for i, cube in enumerate(self.cubes):
+            payload += bytes(-len(payload) % 4)
+            if isinstance(cube, _EncodedCube):
+                descs[i, :5] = (len(payload), cube.width, cube.width, cube.mips, cube.fmt)
+                for levels in cube.faces:
+                    for level in levels:
+                        payload += level
+            else:
+                faces, srgb = cube
+                descs[i, :5] = (len(payload), faces.shape[2], faces.shape[1], 1, 1 if srgb else 0)
+                payload += faces.tobytes()
+        data = np.frombuffer(bytes(payload) + bytes(4), dtype=np.uint8)
+        self._check(self.lib.r3n_texture_cubes_write_encoded(self.ctx, _ffi.ptr(descs), len(self.cubes), _ffi.ptr(data), len(payload)),
+                    "r3n_texture_cubes_write_encoded")
+
     def _flush_cubes(self):
-        if self._cubes_dirty:
+        if self._cubes_dirty and any(isinstance(cube, _EncodedCube) for cube in self.cubes):
+            self._flush_cubes_encoded()
+            self._cubes_dirty = False
+            self._background_sent = None
+        if self._cubes_dirty:  # plain cubes only: the RGBA8 entry, as ever
             descs = np.zeros((max(len(self.cubes), 1), 8), dtype=np.uint32)
             at = 0
             for i, (faces, srgb) in enumerate(self.cubes):
@@ -1668,6 +1725,24 @@ class Renderer:
             self._check(self.lib.r3n_readback_joint_matrices(self.ctx, 0, _ffi.ptr(out), n), "r3n_readback_joint_matrices")
         return out[:n]
 
+    def readback_cube_face(self, cube, level, face):
+        """Bordered face `face` of level `level` of cube `cube` as the device holds it (r3n_readback_cube_face): (n + 2, n + 2)
+        uint32 RGBA8 words, or (n + 2, n + 2, 4) float32 for a cube of a float-decoded format; n = max(1, width >> level).  The
+        four corner texels are zero."""
+        self._flush_cubes()
+        if not 0 <= cube < len(self.cubes):
+            raise ValueError("readback_cube_face: no such cube")
+        c = self.cubes[cube]
+        width = c.width if isinstance(c, _EncodedCube) else c[0].shape[1]
+        p = max(1, width >> level) + 2
+        words = np.zeros(p * p * 4, dtype=np.uint32)
+        cls = np.zeros(1, dtype=np.uint32)
+        self._check(self.lib.r3n_readback_cube_face(self.ctx, int(cube), int(level), int(face), _ffi.ptr(words), words.size, _ffi.ptr(cls)),
+                    "r3n_readback_cube_face")
+        if int(cls[0]) == 2:
+            return words.view(np.float32).reshape(p, p, 4)
+        return words[:p * p].reshape(p, p).copy()
+
     def readback_texels(self, per_texture=False):
         """The decoded texels of every texture (levels back to back, array order): RGBA8 textures as (n, 4) u8, textures
         of the float-decoded formats as (n, 4) f32.  per_texture=False concatenates them into one (n, 4) u8 array (a float
@@ -1850,6 +1925,13 @@ class TonemappingRoutine:
             r._check(r.lib.r3n_tonemap(r.ctx, None, 0), "r3n_tonemap")
 
         graph.add_node("Tonemapping", body)
+
+
+class _EncodedCube:
+    """a cube of add_texture_cube_encoded: faces[f][k] = the bytes of face f level k"""
+
+    def __init__(self, fmt, width, mips, faces):
+        self.fmt, self.width, self.mips, self.faces = fmt, width, mips, faces
 
 
 class SkyboxRoutine:

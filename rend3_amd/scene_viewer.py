@@ -9,7 +9,7 @@ Square: `examples/src/scene_viewer`).  Follows (reference file:line):
                                            :678-681 (ambient = (a, a, a, 1), clear (0, 0, 0, 1))
   App::HANDEDNESS = Right                 :434
   the Bistro test                          :727-751 (flags + camera of BASELINE.json configs[2])
-  load_skybox                              :34-57 (six files right | left | top | bottom | front | back -> add_texture_cube,
+  load_skybox (add_skybox)                 :34-57 (six files right | left | top | bottom | front | back -> add_texture_cube,
                                            Rgba8UnormSrgb, one level), :675 (`skybox: Some(..)` in the frame's routines)
 
 `build(renderer, host_module, material_record, settings)` works on anything with the Renderer's world-edit API -- the HIP
@@ -78,8 +78,10 @@ def add_arguments(ap):
     ap.add_argument("--gltf-disable-directional-lights", action="store_true", help="ignore KHR_lights_punctual lights of the file")
     ap.add_argument("--camera", type=_camera, default=None, metavar="X,Y,Z,PITCH,YAW",
                     help="camera location and angles (default: the default scene's, mod.rs:320-322)")
-    ap.add_argument("--skybox", default=None, metavar="DIR",
-                    help="directory holding right|left|top|bottom|front|back .jpg or .png: the background cube (default: none)")
+    ap.add_argument("--skybox", default=None, metavar="PATH",
+                    help="the background cube (default: none): a directory holding right|left|top|bottom|front|back .jpg or .png, "
+                         "or a .ktx2 / .dds cube map in any supported format with its mip chain (not in the reference, whose "
+                         "example loads the six images)")
     ap.add_argument("--blend-sort", choices=("host", "gpu"), default="host",
                     help="where the transparent pass's back-to-front order is sorted (not in the reference, whose CPU batcher sorts): "
                          "host = every frame on the CPU, gpu = r3n_blend_sort")
@@ -161,6 +163,29 @@ def load_skybox(directory):
     return np.stack(faces)
 
 
+def load_skybox_file(path):
+    """A .ktx2 / .dds cube map -> {"format", "width", "faces"} (containers.parse_ktx2_cube / parse_dds_cube), sRGB as the example's
+    skybox is (Rgba8UnormSrgb)."""
+    from . import containers
+    with open(path, "rb") as f:
+        data = f.read()
+    cube = containers.parse_ktx2_cube(data, True) or containers.parse_dds_cube(data, True)
+    if cube is None:
+        raise ValueError(f"skybox: {path} is neither a KTX2 nor a DDS file")
+    return cube
+
+
+def add_skybox(r, path):
+    """binds the cube of --skybox PATH: a directory of six images, or a cube-map file"""
+    if os.path.isdir(path):
+        handle = r.add_texture_cube(load_skybox(path), srgb=True)
+    else:
+        cube = load_skybox_file(path)
+        handle = r.add_texture_cube_encoded(cube["format"], cube["width"], cube["faces"])
+    r.set_background_texture(handle)
+    return handle
+
+
 PROJECTION = ("perspective", 60.0, 0.1)  # mod.rs:645
 CLEAR = (0.0, 0.0, 0.0, 1.0)             # mod.rs:681
 
@@ -173,7 +198,7 @@ def build(r, hm, mk, settings):
     from . import gltf
     assert r.handedness == RIGHT, "scene_viewer is right-handed (App::HANDEDNESS, mod.rs:434)"
     if settings.get("skybox"):  # load_skybox (mod.rs:34-57); a renderer without cube textures fails here, it does not skip the sky
-        r.set_background_texture(r.add_texture_cube(load_skybox(settings["skybox"]), srgb=True))
+        add_skybox(r, settings["skybox"])
     if settings.get("blend_sort", "host") != "host":  # (a renderer that cannot sort on the device fails here)
         if not hasattr(r, "blend_sort"):
             raise ValueError("--blend-sort gpu: this renderer has no device sort")

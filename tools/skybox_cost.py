@@ -7,12 +7,29 @@ frame's GPU time (sum of the stages) both ways and their difference, the share o
 its traffic floor -- algorithmic bytes (8 B of key per sample read; per sky pixel 8 B of Rgba16Float + 4 B of Rgba8 written and up
 to four texel words read) over the copy rate measured on this device (r3n_hbm_copy_rate).
 
-usage: python tools/skybox_cost.py [--frames 24] [--warmup 6] [--out profiles/skybox_cost.txt]"""
-import argparse
-import os
-import sys
+usage: python tools/skybox_cost.py [--frames 24] [--warmup 6] [--out profiles/skybox_cost.txt]
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+--mips: the cost of cubes with levels and of float cubes instead (profiles/skybox_mips.md).  An EMPTY world at 3840x2160, so the sky
+is on every pixel; the `skybox` stage of
+  case 1  a 1024^2 one-level Rgba8UnormSrgb cube through r3n_texture_cubes_write (what the parent commit can load as well),
+  case 2  the same cube with its full chain (box-filtered here) through r3n_texture_cubes_write_encoded,
+  case 3  a 1024^2 Bc6hRgbUfloat cube with a full chain (random blocks: there is no encoder here; the fetches do not depend on
+          the values),
+each in --runs fresh processes, the median stage time per process (the camera's field of view is 60 degrees, which magnifies such a
+cube: every pixel stays on level 0, so cases 2 and 3 show the cost of selecting the level, not of fetching two).  With --parent-tree DIR (a checkout of the parent commit with its
+library built) case 1 alternates between the two trees, so that both spreads come from one session.  Then the host time of ONE
+r3n_texture_cubes_write_encoded call for case 3, in five fresh contexts.
+       python tools/skybox_cost.py --mips [--runs 5] [--parent-tree DIR] [--out FILE]"""
+import argparse
+import json
+import os
+import subprocess
+import sys
+import time
+
+# (--tree DIR: import the package and bench.py from another checkout -- the parent commit's, for --mips --parent-tree)
+TREE = sys.argv[sys.argv.index("--tree") + 1] if "--tree" in sys.argv else os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, TREE)
 import numpy as np
 
 import bench
@@ -85,12 +102,133 @@ def measure(samples, frames, warmup, lines):
     r.close()
 
 
+# ---------------------------------------------------------------------------------------------- --mips
+BC6H_UF, RGBA8_SRGB = 32, 1
+
+
+def box_chain(faces):
+    """the full chain of uint8[6, N, N, 4] faces (N a power of two): 2 x 2 averages, level by level"""
+    levels = [faces]
+    while levels[-1].shape[1] > 1:
+        a = levels[-1].astype(np.uint16)
+        levels.append(((a[:, 0::2, 0::2] + a[:, 1::2, 0::2] + a[:, 0::2, 1::2] + a[:, 1::2, 1::2] + 2) // 4).astype(np.uint8))
+    return [[lv[f].tobytes() for lv in levels] for f in range(6)]
+
+
+def bc6h_chain(n):
+    rng = np.random.default_rng(0xBC6)
+    mips = n.bit_length()
+    return [[rng.integers(0, 256, ((max(1, n >> k) + 3) // 4) ** 2 * 16, dtype=np.uint8).tobytes() for k in range(mips)] for _ in range(6)]
+
+
+def add_case_cube(r, case, n=1024):
+    if case == 1:
+        return r.add_texture_cube(sky_cube(n), srgb=True)
+    if case == 2:
+        return r.add_texture_cube_encoded(RGBA8_SRGB, n, box_chain(sky_cube(n)))
+    return r.add_texture_cube_encoded(BC6H_UF, n, bc6h_chain(n))
+
+
+def child_stage(case, frames, warmup):
+    """one fresh process: the median `skybox` stage over an empty world"""
+    r = r3.Renderer(r3.host.RIGHT, np.float32(W / H))
+    r.set_background_texture(add_case_cube(r, case))
+    r.set_camera_data(r3.host.look_at_rh((0, 0, 0), (1.0, 0.4, 1.0), (0, 1, 0)), ("perspective", 60.0, 0.1))
+    r.set_multi_stream(False)
+    r.timing_enable(True)
+    out = {}
+    for samples in (1, 4):
+        per_frame = []
+        for k in range(warmup + frames):
+            r.render(W, H, samples=samples, clear_color=bench.CLEAR, readback=False)
+            r.sync()
+            st = r.stage_times(reset=True)
+            if k >= warmup:
+                per_frame.append(st["skybox"][0])
+        out[str(samples)] = float(np.median(per_frame)) * 1e3
+    out["copy_gbs"] = r.hbm_copy_rate()
+    r.close()
+    print("RESULT " + json.dumps(out))
+
+
+def child_upload(contexts=5, n=1024):
+    """the host time of one r3n_texture_cubes_write_encoded call for case 3, a fresh context each"""
+    faces = bc6h_chain(n)
+    payload = np.frombuffer(b"".join(b"".join(levels) for levels in faces), dtype=np.uint8)
+    desc = np.array([[0, n, n, n.bit_length(), BC6H_UF, 0, 0, 0]], dtype=np.uint32)
+    ms = []
+    for _ in range(contexts):
+        r = r3.Renderer(r3.host.RIGHT, np.float32(W / H))
+        r.sync()
+        t0 = time.perf_counter()
+        code = r.lib.r3n_texture_cubes_write_encoded(r.ctx, r3._ffi.ptr(desc), 1, r3._ffi.ptr(payload), payload.size)
+        ms.append(1e3 * (time.perf_counter() - t0))
+        assert code == 0
+        copy_gbs = r.hbm_copy_rate()
+        r.close()
+    print("RESULT " + json.dumps({"ms": ms, "payload_bytes": int(payload.size), "copy_gbs": copy_gbs}))
+
+
+def run_child(args, tree=None):
+    env = dict(os.environ)
+    if tree:
+        args = args + ["--tree", os.path.abspath(tree)]
+        env["R3N_LIB"] = os.path.join(os.path.abspath(tree), "rend3_amd", "librend3_amd.so")
+    res = subprocess.run([sys.executable, os.path.abspath(__file__)] + args, env=env, capture_output=True, text=True, timeout=300)
+    if res.returncode != 0:
+        raise RuntimeError(f"child {args} failed ({res.returncode}):\n{res.stdout[-2000:]}{res.stderr[-2000:]}")
+    return json.loads(next(line for line in res.stdout.splitlines() if line.startswith("RESULT "))[7:])
+
+
+def mips_report(args):
+    lines = [f"tools/skybox_cost.py --mips: empty world at {W}x{H} (sky on every pixel), 1024^2 cubes, {args.runs} fresh processes per row, "
+             f"median `skybox` stage of {args.frames} frames after {args.warmup} warm-up frames per process"]
+
+    def row(name, runs):
+        for samples in ("1", "4"):
+            v = sorted(x[samples] for x in runs)
+            lines.append(f"  {name:<44} samples {samples}: median {np.median(v):8.1f} us  min {v[0]:8.1f}  max {v[-1]:8.1f}  ({' '.join(f'{x:.1f}' for x in v)})")
+
+    child = ["--child-stage", "1", "--frames", str(args.frames), "--warmup", str(args.warmup)]
+    this, parent = [], []
+    for _ in range(args.runs):  # alternating: both libraries see the same drift
+        this.append(run_child(child))
+        if args.parent_tree:
+            parent.append(run_child(child, args.parent_tree))
+    row("case 1, one-level sRGB cube, this tree", this)
+    if parent:
+        row("case 1, one-level sRGB cube, parent commit", parent)
+    for case, name in ((2, "case 2, sRGB cube, full chain"), (3, "case 3, BC6H cube, full chain")):
+        child[1] = str(case)
+        row(name, [run_child(child) for _ in range(args.runs)])
+    up = run_child(["--child-upload"])
+    lines.append(f"  r3n_texture_cubes_write_encoded, case 3 ({up['payload_bytes'] / 1e6:.1f} MB payload), five fresh contexts: "
+                 f"median {np.median(up['ms']):.2f} ms  ({' '.join(f'{x:.2f}' for x in up['ms'])}); copy rate {up['copy_gbs']:.0f} GB/s")
+    text = "\n".join(lines) + "\n"
+    print(text, end="")
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(text)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--frames", type=int, default=12, help="timed frames per block; every state is measured in two blocks")
     ap.add_argument("--warmup", type=int, default=6)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--mips", action="store_true", help="the cost of cubes with levels and of float cubes (see above)")
+    ap.add_argument("--runs", type=int, default=5)
+    ap.add_argument("--parent-tree", default=None, help="--mips: a checkout of the parent commit, its library built; measured on case 1 in alternation")
+    ap.add_argument("--tree", default=None, help=argparse.SUPPRESS)
+    ap.add_argument("--child-stage", type=int, default=None, help=argparse.SUPPRESS)
+    ap.add_argument("--child-upload", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.child_stage is not None:
+        return child_stage(args.child_stage, args.frames, args.warmup)
+    if args.child_upload:
+        return child_upload()
+    if args.mips:
+        return mips_report(args)
     lines = [f"tools/skybox_cost.py: bistro_like at {W}x{H}, 1024^2 Rgba8UnormSrgb cube"]
     for samples in (1, 4):
         measure(samples, args.frames, args.warmup, lines)
