@@ -35,6 +35,30 @@ R3N_DEV void mul_point(const float *__restrict__ m, const float v[3], float o[4]
 typedef float f2 __attribute__((ext_vector_type(2)));
 R3N_DEV f2 splat2(float v) { return (f2){v, v}; }
 
+// mul_point for the geometry front end (triangle cull, raster setup): rows (x, y) and (z, w) as f2 pairs, each component still
+// ((c0*x + c1*y) + c2*z) + c3 in the contract's order.  The contract's last product c3 * 1.0f is not formed: it is c3 itself for
+// every c3 that is not a NaN (1.0f is the multiplicative identity of IEEE arithmetic: zeros keep their sign, subnormals are kept),
+// and a NaN c3 makes the component a NaN either way -- the front end only compares it (every comparison with it is false, whatever
+// its payload) or rejects what it touches (setup_triangle's finite tests, the depth clip), so no NaN payload reaches an output.
+// Z = false: a caller that never reads depth (the cull of a shadow view) gets no z row; o[2] is left 0.
+template <bool Z = true> R3N_DEV void mul_point_pk(const float *__restrict__ m, const float v[3], float o[4]) {
+    const f2 x = splat2(v[0]), y = splat2(v[1]), z = splat2(v[2]);
+    const f2 xy = (((f2){m[0], m[1]} * x + (f2){m[4], m[5]} * y) + (f2){m[8], m[9]} * z) + (f2){m[12], m[13]};
+    o[0] = xy.x; o[1] = xy.y;
+    if (Z) {
+        const f2 zw = (((f2){m[2], m[3]} * x + (f2){m[6], m[7]} * y) + (f2){m[10], m[11]} * z) + (f2){m[14], m[15]};
+        o[2] = zw.x; o[3] = zw.y;
+    } else {
+        o[2] = 0.0f;
+        o[3] = ((m[3] * v[0] + m[7] * v[1]) + m[11] * v[2]) + m[15];
+    }
+}
+// every lane of the wave that is active here holds three clip-space w of exactly 1.0f (one ballot, a scalar compare): what an
+// affine model matrix under an orthographic projection gives.  The callers then skip their divisions by w (see there).
+R3N_DEV bool wave_unit_w(const float p[3][4]) {
+    return __ballot(!(p[0][3] == 1.0f && p[1][3] == 1.0f && p[2][3] == 1.0f)) == 0ull;
+}
+
 // Arithmetic policy of the shading code (kernels_shade.h, texture.h).
 //   MathExact  the contract of DESIGN.md section 2: a * b + c rounds twice (the TU is built with -ffp-contract=off), division and
 //              square root are the correctly rounded IEEE operations.  Bit-identical to the oracle.
@@ -158,7 +182,10 @@ struct TriSetup {
 
 // p[k] = clip-space position of vertex k.  Pixel-space homogeneous coords: Xh = (x + w) * W/2,
 // Yh = (w - y) * H/2 (y down), third coordinate w.  e0 = v1 x v2, e1 = v2 x v0, e2 = v0 x v1.
-R3N_DEV void setup_triangle(const float p[3][4], float half_w, float half_h, bool positive_visible, TriSetup &ts) {
+// unit_w (wave-uniform; prepare_triangle): the three w are exactly 1.0f, so 1 / w is RN(1 / 1) = 1 and every product by it is its
+// other factor, bit for bit (zeros, subnormals and infinities included; a NaN stays a NaN and fails the finite tests below
+// whatever its payload): the three reciprocals and nine products are skipped.
+R3N_DEV void setup_triangle(const float p[3][4], float half_w, float half_h, bool positive_visible, TriSetup &ts, bool unit_w = false) {
     float h[3][3], zc[3];
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
@@ -195,8 +222,12 @@ R3N_DEV void setup_triangle(const float p[3][4], float half_w, float half_h, boo
         float sx[3], sy[3], zn[3];
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
-            const float rw = exact_math::rcp(h[k][2]);  // 1 / w, correctly rounded
-            sx[k] = h[k][0] * rw; sy[k] = h[k][1] * rw; zn[k] = zc[k] * rw;
+            if (unit_w) {
+                sx[k] = h[k][0]; sy[k] = h[k][1]; zn[k] = zc[k];
+            } else {
+                const float rw = exact_math::rcp(h[k][2]);  // 1 / w, correctly rounded
+                sx[k] = h[k][0] * rw; sy[k] = h[k][1] * rw; zn[k] = zc[k] * rw;
+            }
         }
         const float ax = sx[1] - sx[0], ay = sy[1] - sy[0], bx = sx[2] - sx[0], by = sy[2] - sy[0];
         const float az = zn[1] - zn[0], bz = zn[2] - zn[0];
@@ -256,15 +287,18 @@ R3N_DEV float frag_depth(const TriSetup &ts, float px, float py) { return (ts.z[
 // box gives identical results.  Triangles that cross the depth-clip planes (0 <= z <= w, which also implies
 // w >= 0) are clipped for the purpose of the box: without this a triangle with a vertex behind the camera would
 // be scanned over the whole viewport.
+// unit_w (wave-uniform; prepare_triangle): the three w are exactly 1.0f -- all_front holds, add() sees w = 1, and x / 1.0f is x for
+// every bit pattern of x that is not a NaN (a NaN quotient is a NaN either way and fails add()'s finite test): no divisions.
 R3N_DEV bool tri_bounds(const float p[3][4], float half_w, float half_h, int vw, int vh, int &x0, int &y0, int &x1,
-                        int &y1) {
+                        int &y1, bool unit_w = false) {
     float mnx = INFINITY, mny = INFINITY, mxx = -INFINITY, mxy = -INFINITY;
     bool ok = true;      // false -> fall back to the whole viewport
     bool any = false;    // some point contributes
     auto add = [&](float x, float y, float w) {
         if (!(w > 1e-30f)) { ok = false; return; }
-        const float sx = (x / w + 1.0f) * half_w;
-        const float sy = (1.0f - y / w) * half_h;
+        const float qx = unit_w ? x : x / w, qy = unit_w ? y : y / w;
+        const float sx = (qx + 1.0f) * half_w;
+        const float sy = (1.0f - qy) * half_h;
         if (!(sx - sx == 0.0f) || !(sy - sy == 0.0f)) { ok = false; return; }  // inf / NaN
         mnx = fminf(mnx, sx); mxx = fmaxf(mxx, sx);
         mny = fminf(mny, sy); mxy = fmaxf(mxy, sy);

@@ -704,18 +704,31 @@ R3N_DEV float hiz_sample_min(const HizView &hz, float u, float v, uint32_t mip) 
 }
 
 // cull.wgsl:264-324, from the clip-space positions p[k] = model_view_proj * vertex k
-R3N_DEV bool execute_culling_clip(const float p[3][4], uint32_t flags, bool shadow, float res_x, float res_y, const HizView &hz) {
+// unit_w (wave-uniform: wave_unit_w of these p; false = the code as the reference writes it): every w is exactly 1.0f, and
+// x / 1.0f is x for EVERY bit pattern of x -- division by one is exact, zeros keep their sign, subnormals and infinities are
+// themselves, a NaN stays a NaN and everything below only compares it (false either way, whatever its payload).  So ndc = p
+// without the nine IEEE divisions.  The decision is read off the data, not off the matrix: a non-finite vertex gives
+// w = 0 * inf = NaN != 1 and sends its whole wave slot through the divisions, as does an object whose model matrix is not affine.
+R3N_DEV bool execute_culling_clip(const float p[3][4], uint32_t flags, bool shadow, float res_x, float res_y, const HizView &hz,
+                                  bool unit_w = false) {
     const float det = det3_xyw(p[0], p[1], p[2]);
     if (flags & R3N_PCU_POSITIVE_AREA_VISIBLE) {
         if (det <= 0.0f) return false;
     } else {
         if (det >= 0.0f) return false;
     }
-    float ndc[3][3];
+    float ndc[3][2];  // (z further down: only lanes that reach the Hi-Z test pay for its quotients)
+    if (unit_w) {
 #pragma unroll
-    for (int k = 0; k < 3; ++k)
+        for (int k = 0; k < 3; ++k)
 #pragma unroll
-        for (int c = 0; c < 3; ++c) ndc[k][c] = p[k][c] / p[k][3];
+            for (int c = 0; c < 2; ++c) ndc[k][c] = p[k][c];
+    } else {
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+#pragma unroll
+            for (int c = 0; c < 2; ++c) ndc[k][c] = p[k][c] / p[k][3];
+    }
     float mn[2], mx[2];
 #pragma unroll
     for (int c = 0; c < 2; ++c) {
@@ -743,14 +756,30 @@ R3N_DEV bool execute_culling_clip(const float p[3][4], uint32_t flags, bool shad
     const float longest = fmaxf(smax[0] - smin[0], smax[1] - smin[1]);
     uint32_t mip = ceil_log2_ge1(longest);
     if (mip > hz.d.mips - 1u) mip = hz.d.mips - 1u;  // App. D.1: clamp to the last level
-    const float depth = fmaxf(fmaxf(ndc[0][2], ndc[1][2]), ndc[2][2]);
+    float ndc_z[3];
+    if (unit_w) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) ndc_z[k] = p[k][2];
+    } else {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) ndc_z[k] = p[k][2] / p[k][3];
+    }
+    const float depth = fmaxf(fmaxf(ndc_z[0], ndc_z[1]), ndc_z[2]);
     const float occ = hiz_sample_min(hz, uv[0], uv[1], mip);
     if (depth < occ) return false;
     return true;
 }
+// FAST (k_triangle_cull's instantiations): packed transforms (device_math.h mul_point_pk) and the unit-w shortcut, decided per
+// wave slot over the lanes active at the call; NO_Z: `shadow` is known to be true, depth is never read and no z row is formed.
+template <bool FAST = false, bool NO_Z = false>
 R3N_DEV bool execute_culling(const float *__restrict__ mvp, const float v[3][3], uint32_t flags, bool shadow,
                              float res_x, float res_y, const HizView &hz) {
     float p[3][4];
+    if (FAST) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) mul_point_pk<!NO_Z>(mvp, v[k], p[k]);
+        return execute_culling_clip(p, flags, shadow, res_x, res_y, hz, wave_unit_w(p));
+    }
 #pragma unroll
     for (int k = 0; k < 3; ++k) mul_point(mvp, v[k], p[k]);
     return execute_culling_clip(p, flags, shadow, res_x, res_y, hz);
@@ -788,7 +817,15 @@ struct TriCullArgs {
 // Persistent kernel: block b processes chunks b, b+grid, ... ; within a chunk wavefront w owns
 // R3N_CHUNK_ITERS consecutive wave slots.  Per-iteration ballots are staged in LDS, then one thread per
 // (list, region) reserves output space for the whole 4096-slot chunk with a single global atomic.
+// MODE (r3n_cull picks; R3N_TUNE front_end_fast): R3N_CULL_PLAIN the code as the reference writes it; R3N_CULL_FAST_VIEW /
+// R3N_CULL_FAST_SHADOW execute_culling's FAST form for a viewport / a shadow camera -- the shadow form holds no z row, no z
+// quotient and no Hi-Z code.  Same result bits and lists, bit for bit and entry by entry.
+#define R3N_CULL_PLAIN 0
+#define R3N_CULL_FAST_VIEW 1
+#define R3N_CULL_FAST_SHADOW 2
+template <int MODE>
 __global__ __launch_bounds__(256) void k_triangle_cull(TriCullArgs a) {
+    constexpr bool FAST = MODE != R3N_CULL_PLAIN, NO_Z = MODE == R3N_CULL_FAST_SHADOW;
     __shared__ unsigned long long s_pass[4][R3N_CHUNK_ITERS];
     __shared__ unsigned long long s_resid[4][R3N_CHUNK_ITERS];
     __shared__ uint32_t s_obj[4][R3N_CHUNK_ITERS];
@@ -801,7 +838,8 @@ __global__ __launch_bounds__(256) void k_triangle_cull(TriCullArgs a) {
     const uint32_t total_waves = a.counts->total_waves;
     const uint32_t nchunks = (total_waves + R3N_CHUNK_WAVES - 1u) / R3N_CHUNK_WAVES;
     const uint32_t flags = a.hdr->flags;
-    const bool shadow = a.hdr->shadow_index != R3N_INVALID;
+    // (the host checks that a camera is a shadow view exactly when its header carries a shadow index: r3n_uniform_bake)
+    const bool shadow = MODE == R3N_CULL_PLAIN ? a.hdr->shadow_index != R3N_INVALID : NO_Z;
     const float res_x = a.hdr->resolution[0], res_y = a.hdr->resolution[1];
     const unsigned long long lane_lt = (1ull << lane) - 1ull;
 
@@ -884,8 +922,8 @@ __global__ __launch_bounds__(256) void k_triangle_cull(TriCullArgs a) {
                 for (int k = 0; k < 3; ++k) fetch_vec3(a.mesh, of.w, idxA[k], vA[k]);
 #pragma unroll
                 for (int k = 0; k < 3; ++k) fetch_vec3(a.mesh, of.w, idxB[k], vB[k]);
-                const bool passA = execute_culling(mvp, vA, flags, shadow, res_x, res_y, a.hiz) && triA < ntri;
-                const bool passB = execute_culling(mvp, vB, flags, shadow, res_x, res_y, a.hiz) && triB < ntri;
+                const bool passA = execute_culling<FAST, NO_Z>(mvp, vA, flags, shadow, res_x, res_y, a.hiz) && triA < ntri;
+                const bool passB = execute_culling<FAST, NO_Z>(mvp, vB, flags, shadow, res_x, res_y, a.hiz) && triB < ntri;
                 const unsigned long long bA = __ballot(passA), bB = __ballot(passB);
                 finish(w, it, obj, wrel, key, bA);
                 finish(w + 1u, it + 1u, obj, wrel + 1u, key, bB);
@@ -898,7 +936,7 @@ __global__ __launch_bounds__(256) void k_triangle_cull(TriCullArgs a) {
                     fetch_indices3(a.mesh, of.x + triA * 3u, idx);
 #pragma unroll
                     for (int k = 0; k < 3; ++k) fetch_vec3(a.mesh, of.w, idx[k], v[k]);
-                    pass = execute_culling(mvp, v, flags, shadow, res_x, res_y, a.hiz);
+                    pass = execute_culling<FAST, NO_Z>(mvp, v, flags, shadow, res_x, res_y, a.hiz);
                 }
                 finish(w, it, obj, wrel, key, __ballot(pass));
                 ++it;

@@ -80,6 +80,7 @@ struct RasterArgs {
     uint32_t *status;                      // host-visible: bit 0 set when nodes / work items ran out (reported by a later call)
     uint32_t row_begin, row_end;           // rows of the viewport this launch may touch: everything ([0, 0xFFFFFFFF)) unless the rank is sharded by rows
     OcclusionArgs occ;                     // shadow views of r3n_render_frame with the two-phase draw on; zero otherwise
+    uint32_t front_end_fast;               // prepare_triangle: packed transforms and the unit-w setup (R3N_TUNE front_end_fast)
 };
 
 // opaque.wgsl:214-235 / depth.wgsl:98-125 (untextured paths): alpha the cutout test compares with the threshold
@@ -179,16 +180,32 @@ R3N_DEV bool prepare_triangle(const RasterArgs &a, uint32_t obj, uint32_t tri, b
     uint32_t idx[3];
     float p[3][4];
     fetch_indices3(a.mesh, first, idx);
+    // the three positions and the matrix's four columns: seven loads issued together and waited for once, in front of the
+    // launch-uniform choice of the transform (a.front_end_fast; R3N_TUNE front_end_fast) -- with the choice between them the
+    // compiler waited for one vertex before it asked for the next (+1.2 us per launch of this latency-bound kernel)
+    float v[3][3], m[16];
 #pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        float v[3];
-        fetch_vec3(a.mesh, pos_off, idx[k], v);
-        mul_point(a.baked[obj].model_view_proj, v, p[k]);
+    for (int k = 0; k < 3; ++k) fetch_vec3(a.mesh, pos_off, idx[k], v[k]);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        const float4 col = reinterpret_cast<const float4 *>(a.baked[obj].model_view_proj)[c];
+        m[4 * c] = col.x; m[4 * c + 1] = col.y; m[4 * c + 2] = col.z; m[4 * c + 3] = col.w;
+    }
+    asm volatile("" : : "v"(v[0][0]), "v"(v[1][0]), "v"(v[2][0]), "v"(m[0]), "v"(m[4]), "v"(m[8]), "v"(m[12]));
+    if (a.front_end_fast != 0u) {  // the packed transform, same values (device_math.h mul_point_pk)
+#pragma unroll
+        for (int k = 0; k < 3; ++k) mul_point_pk(m, v[k], p[k]);
+    } else {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) mul_point(m, v[k], p[k]);
     }
     const float half_w = (float)a.vp_w / 2.0f, half_h = (float)a.vp_h / 2.0f;
-    setup_triangle(p, half_w, half_h, positive_visible, tw.ts);
+    // ... and, when every lane still here has three w of exactly 1.0f (an orthographic shadow view's casters), the setup without
+    // its divisions by w and reciprocals of w: same bits (setup_triangle, tri_bounds)
+    const bool unit_w = a.front_end_fast != 0u && wave_unit_w(p);
+    setup_triangle(p, half_w, half_h, positive_visible, tw.ts, unit_w);
     if (!tw.ts.valid) return false;
-    if (!tri_bounds(p, half_w, half_h, (int)a.vp_w, (int)a.vp_h, tw.x0, tw.y0, tw.x1, tw.y1)) return false;
+    if (!tri_bounds(p, half_w, half_h, (int)a.vp_w, (int)a.vp_h, tw.x0, tw.y0, tw.x1, tw.y1, unit_w)) return false;
     // sort-first sharding (R3N_SHARD_ROWS): this rank scans rows [row_begin, row_end) only.  The box only limits the scan
     // (coverage and depth are decided per pixel), so the rows inside come out exactly as in the unsharded frame.
     tw.y0 = max(tw.y0, (int)a.row_begin);

@@ -207,6 +207,8 @@ struct r3n_ctx {
         uint32_t big_grid = R3N_BIG_GRID, small_grid = R3N_SMALL_GRID;
         uint32_t comm_serial = 1;  // r3n_comm_init: the three communicators' collectives in ONE total order per device (comm_order_*)
         uint32_t shadow_occlusion = 1;  // r3n_render_frame: two-phase depth draw of the shadow views (0: everything drawn in one phase)
+        uint32_t front_end_fast = 1;    // triangle cull and raster setup: packed transforms, no divisions where every w of a wave is 1, no depth
+                                        // in a shadow view's cull (kernels_cull.h, kernels_raster.h; 0: the plain forms, same results)
     } tune;
     bool cutout_short_dirty = true, cutout_short = false;  // cutout_alpha_short(): census of the cutout materials' albedo maps
     bool key_census_dirty = true;
@@ -806,7 +808,7 @@ int apply_tuning(r3n_ctx *c, const char *kv) {
             {"cut_small_lds", &t.cut_small_lds, 0, 65536, 1}, {"vp_cut_small_lds", &t.vp_cut_small_lds, 0, 65536, 1}, {"cull_lds", &t.cull_lds, 0, 65000, 1}, {"vp_cull_lds", &t.vp_cull_lds, 0, 65000, 1},
             {"resolve_lds", &t.resolve_lds, 0, 61440, 1}, {"big_grid", &t.big_grid, 256, 65536, 1},
             {"small_grid", &t.small_grid, R3N_SUBQ, 32768, R3N_SUBQ}, {"timed_pipeline", &t.timed_pipeline, 0, 1, 1},
-            {"comm_serial", &t.comm_serial, 0, 1, 1}, {"shadow_occlusion", &t.shadow_occlusion, 0, 1, 1}, {"prio_main", &t.prio_main, 0, 2, 1}, {"prio_shade", &t.prio_shade, 0, 2, 1}, {"prio_aux", &t.prio_aux, 0, 2, 1}};  // (read at r3n_create only)  // (a multiple of R3N_SUBQ: whole blocks per sub-list)
+            {"comm_serial", &t.comm_serial, 0, 1, 1}, {"shadow_occlusion", &t.shadow_occlusion, 0, 1, 1}, {"front_end_fast", &t.front_end_fast, 0, 1, 1}, {"prio_main", &t.prio_main, 0, 2, 1}, {"prio_shade", &t.prio_shade, 0, 2, 1}, {"prio_aux", &t.prio_aux, 0, 2, 1}};  // (read at r3n_create only)  // (a multiple of R3N_SUBQ: whole blocks per sub-list)
         bool known = false;
         for (auto &k : keys)
             if (key == k.name) {
@@ -2732,7 +2734,10 @@ int r3n_cull(r3n_ctx *c, r3n_camera cam) {
     const uint32_t grid = std::max(1u, std::min(chunks, 4096u));
     {
         Timed t(c, R3N_STAGE_TRIANGLE_CULL, stream);
-        hipLaunchKernelGGL(k_triangle_cull, dim3(grid), dim3(256), viewport ? c->tune.vp_cull_lds : c->tune.cull_lds, stream, a);
+        const uint32_t lds = viewport ? c->tune.vp_cull_lds : c->tune.cull_lds;
+        if (c->tune.front_end_fast == 0u) hipLaunchKernelGGL(k_triangle_cull<R3N_CULL_PLAIN>, dim3(grid), dim3(256), lds, stream, a);
+        else if (viewport) hipLaunchKernelGGL(k_triangle_cull<R3N_CULL_FAST_VIEW>, dim3(grid), dim3(256), lds, stream, a);
+        else hipLaunchKernelGGL(k_triangle_cull<R3N_CULL_FAST_SHADOW>, dim3(grid), dim3(256), lds, stream, a);
     }
     TRY(check_launch(c, "k_triangle_cull"));
     s->culled = true;
@@ -2936,6 +2941,7 @@ int r3n_forward(r3n_ctx *c, r3n_camera cam, uint32_t pass, uint32_t source, uint
     a.material_keys = c->material_keys.as<uint8_t>();
     a.n_materials = c->n_materials;
     a.tri_base = c->tri_base.as<uint32_t>();
+    a.front_end_fast = c->tune.front_end_fast;
     a.list = list;
     a.sub_counts = sub_counts;
     a.subcap = s->subcap[idx];
@@ -3480,6 +3486,7 @@ static int forward_blend(r3n_ctx *c) {
     a.material_keys = c->material_keys.as<uint8_t>();
     a.n_materials = c->n_materials;
     a.tri_base = c->tri_base.as<uint32_t>();
+    a.front_end_fast = c->tune.front_end_fast;
     a.key = R3N_KEY_BLEND;
     a.vp_x = 0; a.vp_y = 0; a.vp_w = c->width; a.vp_h = c->height; a.target_pitch = c->width;
     a.vis = c->vis.as<unsigned long long>();
