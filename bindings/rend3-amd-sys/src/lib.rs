@@ -75,6 +75,11 @@ pub const R3N_OUTPUT_RGBA8_UNORM: u32 = 2;
 pub const R3N_OUTPUT_BGRA8_UNORM: u32 = 3;
 pub const R3N_SKIN_EXACT: u32 = 0;
 pub const R3N_SKIN_MFMA: u32 = 1;
+pub const R3N_TONEMAP_OP_BLIT: u32 = 0;
+pub const R3N_TONEMAP_OP_REINHARD: u32 = 1;
+pub const R3N_TONEMAP_OP_ACES: u32 = 2;
+pub const R3N_EXPOSURE_MANUAL: u32 = 0;
+pub const R3N_EXPOSURE_AUTO: u32 = 1;
 pub const R3N_EXCHANGE_SHADOW: u32 = 0;
 pub const R3N_EXCHANGE_PASS1: u32 = 1;
 pub const R3N_EXCHANGE_PASS2: u32 = 2;
@@ -446,6 +451,35 @@ pub struct r3n_sample_result52 {
 
 #[repr(C)]
 #[derive(Clone, Copy)]
+pub struct r3n_tonemap_opts {
+    pub op: u32,
+    pub exposure_mode: u32,
+    pub exposure_ev: f32,
+    pub white: f32,
+    pub key_log2: f32,
+    pub min_ev: f32,
+    pub max_ev: f32,
+    pub adapt: f32,
+    pub low_permille: u32,
+    pub high_permille: u32,
+    pub _pad: [u32; 2],
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct r3n_exposure_state {
+    pub histogram: [u32; 256],
+    pub excluded: u32,
+    pub valid: u32,
+    pub mean_log2: f32,
+    pub target_ev: f32,
+    pub current_ev: f32,
+    pub scale: f32,
+    pub _pad: [u32; 2],
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
 pub struct r3n_shadow_view272 {
     pub header: r3n_camera_header240,
     pub x: u32,
@@ -589,6 +623,8 @@ extern "C" {
     pub fn r3n_skybox(ctx: *mut r3n_ctx) -> c_int;
     pub fn r3n_tonemap(ctx: *mut r3n_ctx, host_rgba8: *mut c_void, pitch_bytes: u64) -> c_int;
     pub fn r3n_hdr_write(ctx: *mut r3n_ctx, rgba16f: *const u16, first_pixel: u64, n_pixels: u64) -> c_int;
+    pub fn r3n_tonemap_set(ctx: *mut r3n_ctx, opts: *const r3n_tonemap_opts) -> c_int;
+    pub fn r3n_readback_exposure(ctx: *mut r3n_ctx, out: *mut r3n_exposure_state) -> c_int;
     pub fn r3n_frame_end(ctx: *mut r3n_ctx) -> c_int;
     pub fn r3n_render_frame(ctx: *mut r3n_ctx, desc: *const r3n_frame_desc) -> c_int;
     pub fn r3n_shadow_occlusion_stats(ctx: *mut r3n_ctx, camera: u32, out: *mut r3n_shadow_occlusion_counters) -> c_int;

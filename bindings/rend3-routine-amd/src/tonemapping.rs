@@ -33,6 +33,20 @@ impl TonemappingRoutine {
         Self { amd }
     }
 
+    /// Not in the reference: the operators and the auto-exposure its tonemapping.rs:1-10 announces (`r3n_tonemap_set`).  `None`
+    /// restores the reference's blit.  Between frames only; restarts the adaptation.
+    pub fn set_tonemapping(&self, opts: Option<&sys::r3n_tonemap_opts>) {
+        let p = opts.map_or(std::ptr::null(), |o| o as *const sys::r3n_tonemap_opts);
+        self.amd.check(unsafe { sys::r3n_tonemap_set(self.amd.ctx, p) }, "r3n_tonemap_set");
+    }
+
+    /// What the last tonemapping node metered (`r3n_readback_exposure`); waits for it.
+    pub fn readback_exposure(&self) -> sys::r3n_exposure_state {
+        let mut st: sys::r3n_exposure_state = unsafe { std::mem::zeroed() };
+        self.amd.check(unsafe { sys::r3n_readback_exposure(self.amd.ctx, &mut st) }, "r3n_readback_exposure");
+        st
+    }
+
     /// tonemapping.rs:108-147 -- same signature.  `src` is the frame's HDR target, which the context owns; `dst` is the surface
     /// texture: the presentation layer copies `r3n_output_buffer` into it (or maps it), tests read it back with
     /// `r3n_readback_output`.

@@ -721,6 +721,42 @@ int r3n_tonemap(r3n_ctx *ctx, void *host_rgba8, uint64_t pitch_bytes);
  * one r3n_resolve_opaque fills: this writes `n_pixels` RGBA half texels starting at `first_pixel` into the frame's HDR
  * target.  A following r3n_tonemap then runs the stand-alone blit kernel over the whole target. */
 int r3n_hdr_write(r3n_ctx *ctx, const uint16_t *rgba16f, uint64_t first_pixel, uint64_t n_pixels);
+/* ---- tonemapping operators and auto-exposure: what rend3-routine/src/tonemapping.rs:1-10 announces and does not have ("As of
+ * right now there is no tonemapping applied as we don't have auto-exposure yet. Once we have auto-exposure, we can do proper
+ * tonemapping, and will offer a variety of tonemapping operators").  Not in the reference; opt-in.  With nothing set every frame
+ * is the reference's blit, fused into the resolve as before.  Arithmetic: DESIGN.md section 2 "Exposure and tonemapping
+ * operators" (f32, one rounding per operation, table-driven 2^x, integer metering). */
+#define R3N_TONEMAP_OP_BLIT 0u      /* no operator: exposure only (completes tonemapping.rs:1-10) */
+#define R3N_TONEMAP_OP_REINHARD 1u  /* extended Reinhard per channel, white point (completes tonemapping.rs:1-10) */
+#define R3N_TONEMAP_OP_ACES 2u      /* Narkowicz's rational ACES fit per channel (completes tonemapping.rs:1-10) */
+#define R3N_EXPOSURE_MANUAL 0u      /* the exposure is exposure_ev (completes tonemapping.rs:1-10) */
+#define R3N_EXPOSURE_AUTO 1u        /* metered from a luminance histogram of the HDR target (completes tonemapping.rs:1-10) */
+typedef struct r3n_tonemap_opts {   /* 48 B */
+    uint32_t op, exposure_mode;
+    float exposure_ev;   /* MANUAL: the exposure in stops; AUTO: compensation added to the metered value */
+    float white;         /* REINHARD: in (0, 65504] */
+    float key_log2;      /* AUTO: log2 of the grey the mean luminance is brought to */
+    float min_ev, max_ev;/* AUTO: clamp of the target; all three ev fields within [-32, 32] */
+    float adapt;         /* AUTO: share of the distance to the target covered per frame, in (0, 1]; 1 = instant */
+    uint32_t low_permille, high_permille; /* AUTO: ranks [low, high) of the sorted luminances are averaged; 0 <= low < high <= 1000 */
+    uint32_t _pad[2];
+} r3n_tonemap_opts;
+/* Completes tonemapping.rs:1-10.  NULL, or {BLIT, MANUAL, exposure_ev = 0}: the reference's behaviour (default), r3n_tonemap
+ * launches nothing after a resolve.  Otherwise r3n_tonemap runs [histogram, metering step,] operator over the HDR target behind
+ * the resolve, whatever the resolve fused, every launch timed under R3N_STAGE_TONEMAP.  Every field is validated whatever the
+ * mode (NaN anywhere, an unknown op or mode, white outside (0, 65504], an ev field outside [-32, 32], min_ev > max_ev, a
+ * key_log2 that is not finite, adapt outside (0, 1], low >= high or high > 1000 -> R3N_ERR_INVALID_ARG, nothing changed).
+ * Outside a frame only (R3N_ERR_STATE inside one).  Invalidates the adaptation state: the next metered frame adapts instantly.
+ * Never waits for the GPU.  AUTO needs the whole target: r3n_tonemap returns R3N_ERR_UNSUPPORTED with nothing launched while
+ * r3n_set_row_range leaves rows out (a rank that meters its own rows alone would expose differently); MANUAL works under any split. */
+int r3n_tonemap_set(r3n_ctx *ctx, const r3n_tonemap_opts *opts);
+typedef struct r3n_exposure_state {
+    uint32_t histogram[256]; uint32_t excluded; uint32_t valid;
+    float mean_log2, target_ev, current_ev, scale; uint32_t _pad[2];
+} r3n_exposure_state;
+/* Completes tonemapping.rs:1-10.  What the last r3n_tonemap that ran produced; waits for it.  MANUAL (or nothing set, or AUTO
+ * before its first r3n_tonemap): an empty histogram, valid = 0, current_ev = target_ev = the exposure in use, its scale. */
+int r3n_readback_exposure(r3n_ctx *ctx, r3n_exposure_state *out);
 /* Marks the end of the frame: swaps the temporal state (InputOutputBuffer::swap, culling/suballoc.rs:164-214). */
 int r3n_frame_end(r3n_ctx *ctx);
 

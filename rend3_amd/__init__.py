@@ -7,6 +7,6 @@ interface used by the standalone harness, bench.py and the tests.  There is no C
 """
 from . import host  # noqa: F401
 from ._ffi import R3nError, lib, library_path  # noqa: F401
-from .renderer import (BLEND, CUTOUT, OPAQUE, BaseRenderGraph, BaseRenderGraphInputs,  # noqa: F401
+from .renderer import (BLEND, CUTOUT, OPAQUE, AutoExposure, BaseRenderGraph, BaseRenderGraphInputs,  # noqa: F401
                        BaseRenderGraphRoutines, BaseRenderGraphSettings, CameraSpecifier, ForwardRoutine, GpuCuller,
                        HiZRoutine, PbrRoutine, RenderGraph, Renderer, TonemappingRoutine, material_record)

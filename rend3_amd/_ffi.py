@@ -78,6 +78,8 @@ SIGNATURES = {
     "r3n_skybox": (cint, [vp]),
     "r3n_tonemap": (cint, [vp, vp, u64]),
     "r3n_hdr_write": (cint, [vp, vp, u64, u64]),
+    "r3n_tonemap_set": (cint, [vp, vp]),
+    "r3n_readback_exposure": (cint, [vp, vp]),
     "r3n_frame_end": (cint, [vp]),
     "r3n_render_frame": (cint, [vp, vp]),
     "r3n_shadow_occlusion_stats": (cint, [vp, u32, vp]),
@@ -238,6 +240,22 @@ class TextureTailResult(ctypes.Structure):
     _fields_ = [(name, u64) for name in ("textures", "words_copied", "kernel_launches", "full_syncs", "pool_words_after")]
 
 
+TONEMAP_OPS = {"blit": 0, "reinhard": 1, "aces": 2}  # R3N_TONEMAP_OP_*
+EXPOSURE_MANUAL, EXPOSURE_AUTO = 0, 1              # R3N_EXPOSURE_*
+
+
+class TonemapOpts(ctypes.Structure):
+    """r3n_tonemap_opts"""
+    _fields_ = [("op", u32), ("exposure_mode", u32), ("exposure_ev", cfloat), ("white", cfloat), ("key_log2", cfloat), ("min_ev", cfloat),
+                ("max_ev", cfloat), ("adapt", cfloat), ("low_permille", u32), ("high_permille", u32), ("_pad", u32 * 2)]
+
+
+class ExposureState(ctypes.Structure):
+    """r3n_exposure_state"""
+    _fields_ = [("histogram", u32 * 256), ("excluded", u32), ("valid", u32), ("mean_log2", cfloat), ("target_ev", cfloat),
+                ("current_ev", cfloat), ("scale", cfloat), ("_pad", u32 * 2)]
+
+
 class Config(ctypes.Structure):
     """r3n_config"""
     _fields_ = [("struct_size", u32), ("max_big_items", u32), ("shade_mode", u32), ("_pad", u32), ("reserved", u64 * 2)]
@@ -246,6 +264,7 @@ class Config(ctypes.Structure):
 # sizes the C side pins with static_asserts (rend3_amd/csrc/layouts.h)
 assert ctypes.sizeof(ShadowView272) == 272 and ctypes.sizeof(HostCamera144) == 144 and ctypes.sizeof(FrameDesc) == 152
 assert ctypes.sizeof(HostFrame) == 26712 and ctypes.sizeof(Config) == 32
+assert ctypes.sizeof(TonemapOpts) == 48 and ctypes.sizeof(ExposureState) == 1056
 assert ctypes.sizeof(MeshBlock24) == 24 and ctypes.sizeof(MeshMove24) == 24 and ctypes.sizeof(MeshCounters) == 96
 
 _LIB = None

@@ -16,6 +16,7 @@
 
 #include "comm.h"
 #include "hip_owned.h"
+#include "exposure.h"
 #include "kernels_cull.h"
 #include "kernels_raster.h"
 #define R3N_SHADE_DECL_ONLY
@@ -301,6 +302,16 @@ struct r3n_ctx {
     DeviceBuffer srgb_lut;  // 8-bit output code of every half in [0, 1): kernels_raster.h k_build_srgb_lut (or r3n_set_output_format)
     uint32_t output_format = R3N_OUTPUT_RGBA8_UNORM_SRGB;
     uint32_t shade_mode = R3N_SHADE_EXACT;
+    // r3n_tonemap_set (exposure.h): tm_on = options other than the reference's blit are set.  The exposure state lives on the device
+    // and is never read on the frame path: k_exposure_update steps from state[exp_committed] into the other one, close_frame commits
+    // by flipping the index -- so a second r3n_tonemap of a frame repeats the step instead of taking another, and frames in flight
+    // step in stream order.  exp_shown: the state the last r3n_tonemap produced (-1: none since the options were set).
+    bool tm_on = false;
+    exposure_rule::Params tm_params{};
+    float tm_manual_scale = 1.0f;
+    DeviceBuffer exposure_block;
+    int exp_committed = 0, exp_shown = -1;
+    bool exp_metered_this_frame = false, exp_reset = true;
     DeviceBuffer big_items[1 + R3N_QLANES];
     DeviceSpan big_count[1 + R3N_QLANES];  // work queues: [0] the viewport's, 1.. one per concurrently drawn shadow view
     uint32_t forward_index_lane[1 + R3N_QLANES] = {};
@@ -3548,13 +3559,107 @@ static int forward_blend(r3n_ctx *c) {
     return check_launch(c, "blend apply");
 }
 
-static int launch_tonemap(r3n_ctx *c, float4 *f32_out) {
+// The blit over the context's rows.  With options set (r3n_tonemap_set) the operator kernel takes its place: the exposure is the
+// manual one, or the scale word of the state the last r3n_tonemap produced -- the float tap of r3n_readback_output comes through
+// here too and never meters again.
+static int launch_tonemap(r3n_ctx *c, float4 *f32_out, hipStream_t stream = nullptr) {
     const uint32_t r0 = std::min(c->row_begin, c->height), r1 = std::min(c->row_end, c->height);
     if (r1 <= r0) return R3N_OK;
+    if (!stream) stream = c->stream;
     const size_t first = (size_t)r0 * c->width, n = (size_t)(r1 - r0) * c->width;
-    Timed t(c, R3N_STAGE_TONEMAP);
+    Timed t(c, R3N_STAGE_TONEMAP, stream);
+    if (c->tm_on) {
+        const bool metered = c->tm_params.exposure_mode == R3N_EXPOSURE_AUTO && c->exp_shown >= 0 && c->exposure_block.p;
+        const float *scale_ptr = metered ? &c->exposure_block.as<ExposureBlock>()->state[c->exp_shown].scale : nullptr;
+        HIP_TRY(c, (hipError_t)r3n_internal_tonemap_op(c->hdr16.as<ushort4>(), c->out8.as<uchar4>(), f32_out, first, n, c->srgb_lut.as<unsigned char>(),
+                                                       c->output_format, c->tm_params.op, scale_ptr, c->tm_manual_scale, c->tm_params.white_sq, stream));
+        return R3N_OK;
+    }
     HIP_TRY(c, (hipError_t)r3n_internal_tonemap(c->hdr16.as<ushort4>(), c->out8.as<uchar4>(), f32_out, first, n, c->srgb_lut.as<unsigned char>(),
-                                                c->output_format, c->stream));
+                                                c->output_format, stream));
+    return R3N_OK;
+}
+
+// 2^(k/256) and the bins' log2 values: built once per process on the host (exposure_rule.h)
+static const ExposureBlock &exposure_tables() {
+    static const ExposureBlock tables = [] {
+        ExposureBlock b{};
+        exposure_rule::build_tables(b.lq, b.e);
+        return b;
+    }();
+    return tables;
+}
+
+int r3n_tonemap_set(r3n_ctx *c, const r3n_tonemap_opts *o) {
+    if (!c) return R3N_ERR_INVALID_ARG;
+    if (c->in_frame) return fail(c, R3N_ERR_STATE, "tonemap_set: inside a frame");
+    exposure_rule::Params p{};
+    bool on = false;
+    if (o) {
+        const float fields[] = {o->exposure_ev, o->white, o->key_log2, o->min_ev, o->max_ev, o->adapt};
+        for (float f : fields)
+            if (f != f) return fail(c, R3N_ERR_INVALID_ARG, "tonemap_set: NaN");
+        if (o->op > R3N_TONEMAP_OP_ACES) return fail(c, R3N_ERR_INVALID_ARG, "tonemap_set: unknown operator");
+        if (o->exposure_mode > R3N_EXPOSURE_AUTO) return fail(c, R3N_ERR_INVALID_ARG, "tonemap_set: unknown exposure mode");
+        if (!(o->white > 0.0f && o->white <= R3N_EXP_MAX_HALF)) return fail(c, R3N_ERR_INVALID_ARG, "tonemap_set: white outside (0, 65504]");
+        for (float ev : {o->exposure_ev, o->min_ev, o->max_ev})
+            if (!(ev >= -32.0f && ev <= 32.0f)) return fail(c, R3N_ERR_INVALID_ARG, "tonemap_set: exposure_ev, min_ev and max_ev lie within [-32, 32]");
+        if (o->min_ev > o->max_ev) return fail(c, R3N_ERR_INVALID_ARG, "tonemap_set: min_ev > max_ev");
+        if (!std::isfinite(o->key_log2)) return fail(c, R3N_ERR_INVALID_ARG, "tonemap_set: key_log2 is not finite");
+        if (!(o->adapt > 0.0f && o->adapt <= 1.0f)) return fail(c, R3N_ERR_INVALID_ARG, "tonemap_set: adapt outside (0, 1]");
+        if (!(o->low_permille < o->high_permille && o->high_permille <= 1000u))
+            return fail(c, R3N_ERR_INVALID_ARG, "tonemap_set: the ranks want 0 <= low_permille < high_permille <= 1000");
+        p.op = o->op; p.exposure_mode = o->exposure_mode;
+        p.exposure_ev = o->exposure_ev; p.white_sq = o->white * o->white; p.key_log2 = o->key_log2;
+        p.min_ev = o->min_ev; p.max_ev = o->max_ev; p.adapt = o->adapt;
+        p.low_permille = o->low_permille; p.high_permille = o->high_permille;
+        on = !(o->op == R3N_TONEMAP_OP_BLIT && o->exposure_mode == R3N_EXPOSURE_MANUAL && o->exposure_ev == 0.0f);
+    }
+    c->tm_on = on;
+    c->tm_params = p;
+    // MANUAL: the exposure as given; AUTO before anything is metered: clamp(exposure_ev)
+    const float ev = !on ? 0.0f : (p.exposure_mode == R3N_EXPOSURE_AUTO ? exposure_rule::clamp_ev(p.exposure_ev, p.min_ev, p.max_ev) : p.exposure_ev);
+    c->tm_manual_scale = exposure_rule::exp2_lin(ev, exposure_tables().e);
+    c->exp_reset = true;  // the next k_exposure_update ignores the committed state's valid word
+    c->exp_shown = -1;
+    return R3N_OK;
+}
+
+// [histogram, metering step,] operator over the HDR target, behind the resolve ON ITS STREAM: while frames are in flight that is the
+// shade stream (as for the skybox), so the main stream goes on with the next frame; the state steps in frame order either way,
+// because whichever stream a later frame uses is ordered behind this one (join_shade / the resolve's own stream order).
+static int tonemap_with_options(r3n_ctx *c) {
+    const uint32_t r0 = std::min(c->row_begin, c->height), r1 = std::min(c->row_end, c->height);
+    const bool automatic = c->tm_params.exposure_mode == R3N_EXPOSURE_AUTO;
+    if (automatic && !(r0 == 0u && r1 == c->height))
+        return fail(c, R3N_ERR_UNSUPPORTED, "tonemap: auto-exposure meters the whole target; this context's row range leaves rows out");
+    const bool fresh = automatic && !c->exposure_block.p;  // the block's fill and tables go through the main stream
+    const bool on_shade = c->resolve_on_shade && c->shade_unjoined && c->shade_last == c->slot && !fresh;
+    hipStream_t stream = on_shade ? (hipStream_t)c->shade : (hipStream_t)c->stream;
+    if (!on_shade) TRY(join_shade(c));
+    if (automatic) {
+        if (fresh) {
+            TRY(ensure(c, c->exposure_block, sizeof(ExposureBlock), false, 0));
+            const ExposureBlock &tab = exposure_tables();
+            static_assert(sizeof tab.lq + sizeof tab.e + sizeof tab._pad2 <= r3n_ctx::kStageSlotBytes, "one staged copy");
+            TRY(upload_small(c, c->exposure_block.as<ExposureBlock>()->lq, tab.lq, sizeof tab.lq + sizeof tab.e));
+        }
+        ExposureBlock *blk = c->exposure_block.as<ExposureBlock>();
+        const size_t n = (size_t)c->width * c->height;
+        {
+            Timed t(c, R3N_STAGE_TONEMAP, stream);
+            HIP_TRY(c, (hipError_t)r3n_internal_luminance_histogram(c->hdr16.as<ushort4>(), 0, n, blk->counters, stream));
+        }
+        {
+            Timed t(c, R3N_STAGE_TONEMAP, stream);
+            HIP_TRY(c, (hipError_t)r3n_internal_exposure_update(blk, c->exp_committed, 1 - c->exp_committed, &c->tm_params, c->exp_reset ? 1 : 0, stream));
+        }
+        c->exp_shown = 1 - c->exp_committed;
+        c->exp_metered_this_frame = true;
+    }
+    TRY(launch_tonemap(c, nullptr, stream));
+    // whatever waits for the resolve -- the frame that reuses these targets, the read-backs -- waits for this as well
+    if (on_shade) HIP_TRY(c, hipEventRecord(c->shade_done[c->slot], c->shade));
     return R3N_OK;
 }
 
@@ -3616,7 +3721,9 @@ int r3n_tonemap(r3n_ctx *c, void *host_rgba8, uint64_t pitch) {
     HIP_TRY(c, hipSetDevice(c->device));
     // the blit is fused into r3n_resolve_opaque (same arithmetic on the Rgba16Float-rounded value); the separate
     // kernel only runs when the HDR buffer was produced some other way
-    if (!c->resolved_this_frame) {
+    if (c->tm_on) {  // r3n_tonemap_set: whatever the resolve fused is overwritten
+        TRY(tonemap_with_options(c));
+    } else if (!c->resolved_this_frame) {
         TRY(join_shade(c));
         TRY(launch_tonemap(c, nullptr));
     }
@@ -3651,6 +3758,11 @@ static int close_frame(r3n_ctx *c) {
     };
     flip(c->viewport);
     for (auto &kv : c->shadows) flip(kv.second);
+    if (c->exp_metered_this_frame) {  // commit the exposure step: the next frame steps from the state this one produced
+        c->exp_committed = 1 - c->exp_committed;
+        c->exp_metered_this_frame = false;
+        c->exp_reset = false;
+    }
     c->in_frame = false;
     return R3N_OK;
 }
@@ -4361,6 +4473,18 @@ int r3n_readback_output(r3n_ctx *c, uint8_t *rgba8, float *rgba_f32) {
     }
     if (rgba8) TRY(copy_d2h(c, rgba8, c->out8.p, n * 4));
     return check_async_status(c);
+}
+
+int r3n_readback_exposure(r3n_ctx *c, r3n_exposure_state *out) {
+    if (!c || !out) return fail(c, R3N_ERR_INVALID_ARG, "readback_exposure: NULL");
+    if (c->tm_on && c->tm_params.exposure_mode == R3N_EXPOSURE_AUTO && c->exp_shown >= 0 && c->exposure_block.p)
+        return d2h(c, out, &c->exposure_block.as<ExposureBlock>()->state[c->exp_shown], sizeof *out);
+    std::memset(out, 0, sizeof *out);
+    const exposure_rule::Params &p = c->tm_params;
+    out->current_ev = !c->tm_on ? 0.0f : (p.exposure_mode == R3N_EXPOSURE_AUTO ? exposure_rule::clamp_ev(p.exposure_ev, p.min_ev, p.max_ev) : p.exposure_ev);
+    out->target_ev = out->current_ev;
+    out->scale = c->tm_manual_scale;
+    return R3N_OK;
 }
 
 // ------------------------------------------------------------------------------------------------ timing

@@ -16,7 +16,8 @@ out of scope); nodes are closures executed in declaration order by RenderGraph.e
 This module never imports the oracle; without the native library it raises.
 """
 import ctypes
-
+import dataclasses
+import math
 import os
 
 import numpy as np
@@ -172,6 +173,44 @@ def morph_radius(radius, weights, reach):
         if w != 0.0:
             r = f32(r + f32(f32(abs(w)) * rc))
     return r
+
+
+@dataclasses.dataclass
+class AutoExposure:
+    """Renderer.set_tonemapping(auto_exposure=...): the mean log-luminance of ranks [low, high) of the frame's sorted luminances is
+    brought to `key`; the exposure stays within [min_ev, max_ev] stops and approaches its target at `speed` per second (inf:
+    instantly)."""
+    key: float = 0.18
+    min_ev: float = -16.0
+    max_ev: float = 16.0
+    low: float = 0.5
+    high: float = 0.95
+    speed: float = 3.0
+
+
+def tonemap_opts(operator="blit", exposure_ev=0.0, white=4.0, auto_exposure=None, dt=1.0 / 60.0):
+    """Renderer.set_tonemapping's arguments as an r3n_tonemap_opts (every field valid whatever the mode, as r3n_tonemap_set
+    wants it); what cannot be expressed raises here."""
+    if operator not in _ffi.TONEMAP_OPS:
+        raise ValueError(f"set_tonemapping: unknown operator {operator!r} (one of {sorted(_ffi.TONEMAP_OPS)})")
+    o = _ffi.TonemapOpts()
+    o.op, o.exposure_mode = _ffi.TONEMAP_OPS[operator], _ffi.EXPOSURE_MANUAL
+    o.exposure_ev, o.white = float(exposure_ev), float(white)
+    ae = auto_exposure if auto_exposure is not None else AutoExposure()
+    if not isinstance(ae, AutoExposure):
+        raise TypeError("set_tonemapping: auto_exposure is an AutoExposure or None")
+    if not ae.key > 0.0 or not math.isfinite(ae.key):
+        raise ValueError("set_tonemapping: AutoExposure.key is a positive luminance")
+    if not (dt > 0.0 and ae.speed > 0.0):
+        raise ValueError("set_tonemapping: dt and AutoExposure.speed are positive")
+    o.key_log2, o.min_ev, o.max_ev = math.log2(ae.key), float(ae.min_ev), float(ae.max_ev)
+    o.adapt = 1.0 if math.isinf(ae.speed) else min(1.0, max(-math.expm1(-float(dt) * float(ae.speed)), 2.0 ** -24))
+    if not 0.0 <= ae.low < ae.high <= 1.0:
+        raise ValueError("set_tonemapping: AutoExposure wants 0 <= low < high <= 1")
+    o.low_permille, o.high_permille = int(round(ae.low * 1000)), int(round(ae.high * 1000))
+    if auto_exposure is not None:
+        o.exposure_mode = _ffi.EXPOSURE_AUTO
+    return o
 
 
 class CameraSpecifier:
@@ -1708,6 +1747,24 @@ class Renderer:
         self._check(self.lib.r3n_set_output_format(self.ctx, int(fmt)), "r3n_set_output_format")
         self.output_format = int(fmt)
 
+    def set_tonemapping(self, operator="blit", exposure_ev=0.0, white=4.0, auto_exposure=None, dt=1.0 / 60.0):
+        """What rend3-routine/src/tonemapping.rs:1-10 announces: an exposure and an operator ("blit" | "reinhard" | "aces") in front
+        of the blit's transfer (r3n_tonemap_set).  exposure_ev: stops (with auto_exposure: compensation added to the metered value);
+        white: Reinhard's white point; auto_exposure: an AutoExposure, metered on the GPU from a luminance histogram of the HDR
+        target -- its `speed` per second and the frame interval `dt` give the share of the distance to the target covered per
+        frame, adapt = 1 - exp(-dt * speed).  Between frames only; setting anything restarts the adaptation (the next frame adapts
+        instantly).  set_tonemapping() with the defaults is the reference's behaviour: the blit stays fused into the resolve."""
+        o = tonemap_opts(operator, exposure_ev, white, auto_exposure, dt)
+        self._check(self.lib.r3n_tonemap_set(self.ctx, ctypes.byref(o)), "r3n_tonemap_set")
+
+    def readback_exposure(self):
+        """What the last tonemapping node produced (waits for it): dict(histogram (256,) uint32, excluded, valid, mean_log2,
+        target_ev, current_ev, scale)."""
+        st = _ffi.ExposureState()
+        self._check(self.lib.r3n_readback_exposure(self.ctx, ctypes.byref(st)), "r3n_readback_exposure")
+        return dict(histogram=np.array(st.histogram[:], dtype=np.uint32), excluded=int(st.excluded), valid=int(st.valid),
+                    mean_log2=f32(st.mean_log2), target_ev=f32(st.target_ev), current_ev=f32(st.current_ev), scale=f32(st.scale))
+
     def set_skinning_mode(self, mode):
         """0 = R3N_SKIN_EXACT (vector ALU, default), 1 = R3N_SKIN_MFMA (matrix cores; rigs of at most four joints)."""
         self._check(self.lib.r3n_set_skinning_mode(self.ctx, int(mode)), "r3n_set_skinning_mode")
@@ -1919,6 +1976,10 @@ class PbrRoutine:
 
 class TonemappingRoutine:
     """rend3-routine/src/tonemapping.rs:29-148"""
+
+    def set_tonemapping(self, renderer, *args, **kwargs):
+        """Renderer.set_tonemapping through the routine (the operators tonemapping.rs:1-10 announces)."""
+        renderer.set_tonemapping(*args, **kwargs)
 
     def add_to_graph(self, graph):
         def body(r, ev):

@@ -109,6 +109,13 @@ def add_arguments(ap):
     ap.add_argument("--morph-tangents", choices=("base", "recompute"), default="base",
                     help="generated tangents of morphed primitives: base = those of the bind shape under any weights, "
                          "recompute = regenerated from the morphed positions and normals on the GPU (r3n_vertex_tangents)")
+    ap.add_argument("--tonemap", choices=("blit", "reinhard", "aces"), default="blit",
+                    help="tonemapping operator in front of the output transfer (r3n_tonemap_set; blit = none, as the reference)")
+    ap.add_argument("--exposure", type=float, default=0.0, metavar="EV",
+                    help="exposure in stops; with --auto-exposure: compensation added to the metered value")
+    ap.add_argument("--auto-exposure", action="store_true",
+                    help="meter the exposure on the GPU from a luminance histogram of the HDR target (the auto-exposure the reference's "
+                         "tonemapping.rs:1-10 waits for)")
     return ap
 
 
@@ -130,7 +137,9 @@ def settings_from(args):
                 build_tangents=getattr(args, "build_tangents", False), morph_tangents=getattr(args, "morph_tangents", "base"),
                 texture_upload=getattr(args, "texture_upload", "whole"), texture_compact=getattr(args, "texture_compact", None),
                 texture_skip_mips=getattr(args, "texture_skip_mips", 0),
-                mesh_upload=getattr(args, "mesh_upload", "append"), mesh_compact=getattr(args, "mesh_compact", None))
+                mesh_upload=getattr(args, "mesh_upload", "append"), mesh_compact=getattr(args, "mesh_compact", None),
+                tonemap=getattr(args, "tonemap", "blit"), exposure=getattr(args, "exposure", 0.0),
+                auto_exposure=getattr(args, "auto_exposure", False))
 
 
 def default_settings(**over):
@@ -199,6 +208,12 @@ def build(r, hm, mk, settings):
     assert r.handedness == RIGHT, "scene_viewer is right-handed (App::HANDEDNESS, mod.rs:434)"
     if settings.get("skybox"):  # load_skybox (mod.rs:34-57); a renderer without cube textures fails here, it does not skip the sky
         add_skybox(r, settings["skybox"])
+    if settings.get("tonemap", "blit") != "blit" or settings.get("exposure", 0.0) != 0.0 or settings.get("auto_exposure"):
+        if not hasattr(r, "set_tonemapping"):  # (a renderer that only has the reference's blit fails here)
+            raise ValueError("--tonemap / --exposure / --auto-exposure: this renderer has the blit alone")
+        from .renderer import AutoExposure
+        r.set_tonemapping(settings.get("tonemap", "blit"), exposure_ev=settings.get("exposure", 0.0),
+                          auto_exposure=AutoExposure() if settings.get("auto_exposure") else None)
     if settings.get("blend_sort", "host") != "host":  # (a renderer that cannot sort on the device fails here)
         if not hasattr(r, "blend_sort"):
             raise ValueError("--blend-sort gpu: this renderer has no device sort")
