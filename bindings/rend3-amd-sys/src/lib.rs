@@ -80,6 +80,7 @@ pub const R3N_TONEMAP_OP_REINHARD: u32 = 1;
 pub const R3N_TONEMAP_OP_ACES: u32 = 2;
 pub const R3N_EXPOSURE_MANUAL: u32 = 0;
 pub const R3N_EXPOSURE_AUTO: u32 = 1;
+pub const R3N_BLOOM_MAX_LEVELS: u32 = 16;
 pub const R3N_EXCHANGE_SHADOW: u32 = 0;
 pub const R3N_EXCHANGE_PASS1: u32 = 1;
 pub const R3N_EXCHANGE_PASS2: u32 = 2;
@@ -480,6 +481,17 @@ pub struct r3n_exposure_state {
 
 #[repr(C)]
 #[derive(Clone, Copy)]
+pub struct r3n_bloom_opts {
+    pub intensity: f32,
+    pub threshold: f32,
+    pub knee: f32,
+    pub scatter: f32,
+    pub max_levels: u32,
+    pub _pad: [u32; 3],
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
 pub struct r3n_shadow_view272 {
     pub header: r3n_camera_header240,
     pub x: u32,
@@ -625,6 +637,8 @@ extern "C" {
     pub fn r3n_hdr_write(ctx: *mut r3n_ctx, rgba16f: *const u16, first_pixel: u64, n_pixels: u64) -> c_int;
     pub fn r3n_tonemap_set(ctx: *mut r3n_ctx, opts: *const r3n_tonemap_opts) -> c_int;
     pub fn r3n_readback_exposure(ctx: *mut r3n_ctx, out: *mut r3n_exposure_state) -> c_int;
+    pub fn r3n_bloom_set(ctx: *mut r3n_ctx, opts: *const r3n_bloom_opts) -> c_int;
+    pub fn r3n_readback_bloom(ctx: *mut r3n_ctx, level: u32, rgb16f: *mut u16, capacity_texels: u64, width: *mut u32, height: *mut u32, levels: *mut u32) -> c_int;
     pub fn r3n_frame_end(ctx: *mut r3n_ctx) -> c_int;
     pub fn r3n_render_frame(ctx: *mut r3n_ctx, desc: *const r3n_frame_desc) -> c_int;
     pub fn r3n_shadow_occlusion_stats(ctx: *mut r3n_ctx, camera: u32, out: *mut r3n_shadow_occlusion_counters) -> c_int;

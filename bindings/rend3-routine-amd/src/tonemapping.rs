@@ -40,6 +40,15 @@ impl TonemappingRoutine {
         self.amd.check(unsafe { sys::r3n_tonemap_set(self.amd.ctx, p) }, "r3n_tonemap_set");
     }
 
+    /// Not in the reference: bloom in front of the operator (`r3n_bloom_set`; hangs on tonemapping.rs:1-10 like the operators).
+    /// `None`, or an intensity of 0, switches it off: the node then launches what it launches without it.  Between frames only;
+    /// independent of `set_tonemapping`, in either order.  `max_levels` is at most `sys::R3N_BLOOM_MAX_LEVELS`.
+    pub fn set_bloom(&self, opts: Option<&sys::r3n_bloom_opts>) {
+        debug_assert!(opts.map_or(true, |o| o.max_levels <= sys::R3N_BLOOM_MAX_LEVELS));
+        let p = opts.map_or(std::ptr::null(), |o| o as *const sys::r3n_bloom_opts);
+        self.amd.check(unsafe { sys::r3n_bloom_set(self.amd.ctx, p) }, "r3n_bloom_set");
+    }
+
     /// What the last tonemapping node metered (`r3n_readback_exposure`); waits for it.
     pub fn readback_exposure(&self) -> sys::r3n_exposure_state {
         let mut st: sys::r3n_exposure_state = unsafe { std::mem::zeroed() };

@@ -757,6 +757,33 @@ typedef struct r3n_exposure_state {
 /* Completes tonemapping.rs:1-10.  What the last r3n_tonemap that ran produced; waits for it.  MANUAL (or nothing set, or AUTO
  * before its first r3n_tonemap): an empty histogram, valid = 0, current_ev = target_ev = the exposure in use, its scale. */
 int r3n_readback_exposure(r3n_ctx *ctx, r3n_exposure_state *out);
+/* ---- bloom: a pyramid of the HDR target's highlights, composited in front of the operator.  Not in the reference (it hangs on
+ * the same note, rend3-routine/src/tonemapping.rs:1-10); opt-in.  With nothing set every frame is what it is without this entry,
+ * bit for bit and launch for launch.  Arithmetic: DESIGN.md section 2 "Bloom" (exposed units, soft-knee bright pass, 4x4 tent
+ * down, 2x tent up with scatter, halves stored, f32 in a pinned order). */
+#define R3N_BLOOM_MAX_LEVELS 16u     /* most levels of a bloom pyramid (extends tonemapping.rs:1-10) */
+typedef struct r3n_bloom_opts {   /* 32 B */
+    float intensity;      /* [0, 1024]; 0 = off */
+    float threshold;      /* [0, 65504], exposed units: 1 = display white, under auto-exposure too */
+    float knee;           /* [0, threshold]: the bright pass rises quadratically over [threshold - knee, threshold + knee] */
+    float scatter;        /* [0, 1]: share of each coarser level added on the way up */
+    uint32_t max_levels;  /* [1, 16] */
+    uint32_t _pad[3];
+} r3n_bloom_opts;
+/* Extends tonemapping.rs:1-10.  NULL, or intensity == 0: off (default), r3n_tonemap launches exactly what it launches without
+ * this entry.  Otherwise r3n_tonemap runs [histogram, metering step,] the bloom chain, then the operator with the composite, all
+ * on one stream and timed under R3N_STAGE_TONEMAP; without r3n_tonemap_set options the operator is BLIT at scale 1.  Every field
+ * is validated (a NaN anywhere or a field outside its range -> R3N_ERR_INVALID_ARG, nothing changed).  Outside a frame only
+ * (R3N_ERR_STATE inside one).  Never waits for the GPU.  Independent of r3n_tonemap_set, in either order.  The HDR target is never
+ * written.  Bloom needs neighbouring rows: r3n_tonemap returns R3N_ERR_UNSUPPORTED with nothing launched while r3n_set_row_range
+ * leaves rows out. */
+int r3n_bloom_set(r3n_ctx *ctx, const r3n_bloom_opts *opts);
+/* Extends tonemapping.rs:1-10.  Test and diagnostic entry: level `level` of the up chain (a_level) as the last r3n_tonemap left
+ * it, three halves per texel; waits for that call.  Under R3N_TUNE bloom_keep_down=1 the levels of the down chain are kept too:
+ * `*levels + k` reads d_k.  rgb16f may be NULL (sizes only); otherwise capacity_texels >= width * height of the level.
+ * R3N_ERR_STATE if the last r3n_tonemap ran no bloom, R3N_ERR_INVALID_ARG for a level that does not exist. */
+int r3n_readback_bloom(r3n_ctx *ctx, uint32_t level, uint16_t *rgb16f, uint64_t capacity_texels,
+                       uint32_t *width, uint32_t *height, uint32_t *levels);
 /* Marks the end of the frame: swaps the temporal state (InputOutputBuffer::swap, culling/suballoc.rs:164-214). */
 int r3n_frame_end(r3n_ctx *ctx);
 

@@ -9,4 +9,4 @@ from . import host  # noqa: F401
 from ._ffi import R3nError, lib, library_path  # noqa: F401
 from .renderer import (BLEND, CUTOUT, OPAQUE, AutoExposure, BaseRenderGraph, BaseRenderGraphInputs,  # noqa: F401
                        BaseRenderGraphRoutines, BaseRenderGraphSettings, CameraSpecifier, ForwardRoutine, GpuCuller,
-                       HiZRoutine, PbrRoutine, RenderGraph, Renderer, TonemappingRoutine, material_record)
+                       HiZRoutine, PbrRoutine, RenderGraph, Renderer, TonemappingRoutine, bloom_opts, material_record)

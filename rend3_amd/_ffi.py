@@ -80,6 +80,8 @@ SIGNATURES = {
     "r3n_hdr_write": (cint, [vp, vp, u64, u64]),
     "r3n_tonemap_set": (cint, [vp, vp]),
     "r3n_readback_exposure": (cint, [vp, vp]),
+    "r3n_bloom_set": (cint, [vp, vp]),
+    "r3n_readback_bloom": (cint, [vp, u32, vp, u64, vp, vp, vp]),
     "r3n_frame_end": (cint, [vp]),
     "r3n_render_frame": (cint, [vp, vp]),
     "r3n_shadow_occlusion_stats": (cint, [vp, u32, vp]),
@@ -256,6 +258,14 @@ class ExposureState(ctypes.Structure):
                 ("current_ev", cfloat), ("scale", cfloat), ("_pad", u32 * 2)]
 
 
+BLOOM_MAX_LEVELS = 16  # R3N_BLOOM_MAX_LEVELS
+
+
+class BloomOpts(ctypes.Structure):
+    """r3n_bloom_opts"""
+    _fields_ = [("intensity", cfloat), ("threshold", cfloat), ("knee", cfloat), ("scatter", cfloat), ("max_levels", u32), ("_pad", u32 * 3)]
+
+
 class Config(ctypes.Structure):
     """r3n_config"""
     _fields_ = [("struct_size", u32), ("max_big_items", u32), ("shade_mode", u32), ("_pad", u32), ("reserved", u64 * 2)]
@@ -264,7 +274,7 @@ class Config(ctypes.Structure):
 # sizes the C side pins with static_asserts (rend3_amd/csrc/layouts.h)
 assert ctypes.sizeof(ShadowView272) == 272 and ctypes.sizeof(HostCamera144) == 144 and ctypes.sizeof(FrameDesc) == 152
 assert ctypes.sizeof(HostFrame) == 26712 and ctypes.sizeof(Config) == 32
-assert ctypes.sizeof(TonemapOpts) == 48 and ctypes.sizeof(ExposureState) == 1056
+assert ctypes.sizeof(TonemapOpts) == 48 and ctypes.sizeof(ExposureState) == 1056 and ctypes.sizeof(BloomOpts) == 32
 assert ctypes.sizeof(MeshBlock24) == 24 and ctypes.sizeof(MeshMove24) == 24 and ctypes.sizeof(MeshCounters) == 96
 
 _LIB = None

@@ -23,13 +23,23 @@ static_assert(sizeof(ExposureBlock) % 16 == 0, "state[] stays 16-byte aligned");
 
 #define R3N_EXP_HIST_GRID 1024u  // workgroups of k_luminance_histogram at most: four per CU, the rest of the target by grid stride
 
+// what the operator kernel composites (r3n_bloom_set): level 0 of the up chain's pyramid (bw x bh texels of three halves and a
+// pad) over a target `width` pixels wide
+struct R3nBloomComposite {
+    const ushort4 *a0;
+    uint32_t bw, bh, width;
+    float intensity;
+};
+
 // Each returns the hipError_t of the launch as an int; they only enqueue.
 extern "C" {
 // counters[bin] += pixels of [first_pixel, first_pixel + n_pixels) in that bin
 int r3n_internal_luminance_histogram(const ushort4 *hdr, size_t first_pixel, size_t n_pixels, uint32_t *counters, hipStream_t stream);
 // prev -> cur through exposure_rule::step; snapshots the histogram into cur and zeroes the counters.  prev_invalid: ignore prev.valid
 int r3n_internal_exposure_update(ExposureBlock *block, int prev, int cur, const exposure_rule::Params *p, int prev_invalid, hipStream_t stream);
-// k_tonemap with exposure and operator in front of the transfer; scale_ptr != NULL: the scale is loaded from there (AUTO)
+// k_tonemap with exposure and operator in front of the transfer; scale_ptr != NULL: the scale is loaded from there (AUTO);
+// bloom != NULL: the bloom pyramid is composited in front of the operator (pixel indices must fit 32 bits then)
 int r3n_internal_tonemap_op(const ushort4 *hdr, uchar4 *out, float4 *out_f32, size_t first_pixel, size_t n_pixels, const unsigned char *srgb_lut,
-                            uint32_t output_format, uint32_t op, const float *scale_ptr, float scale, float white_sq, hipStream_t stream);
+                            uint32_t output_format, uint32_t op, const float *scale_ptr, float scale, float white_sq, const R3nBloomComposite *bloom,
+                            hipStream_t stream);
 }

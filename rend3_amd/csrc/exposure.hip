@@ -6,6 +6,7 @@
 
 #include "kernels_shade.h"
 #include "exposure.h"
+#include "bloom_rule.h"
 
 namespace {
 
@@ -122,10 +123,16 @@ __global__ __launch_bounds__(64) void k_exposure_update(ExposureBlock *__restric
 
 // k_tonemap's shape (two pixels per thread) with exposure and operator in front of the transfer.  The exposed, operated value is
 // rounded to half and then takes exactly the blit's path: tonemap_half4 for the bytes, the float view's formulas for the tap.
-template <uint32_t OP>
+// BLOOM (r3n_bloom_set, DESIGN.md section 2 "Bloom"): the 2x tent up-sample of the pyramid's level 0 is added to the exposed value
+// in front of the operator.  Four taps per pixel; a thread whose two pixels lie side by side in one row (the first at an even x)
+// shares the two taps of their common nearer column.
+R3N_DEV float bloom_chan(ushort4 t, int c) { return half_f32(c == 0 ? t.x : (c == 1 ? t.y : t.z)); }
+
+template <uint32_t OP, bool BLOOM = false>
 __global__ __launch_bounds__(256) void k_tonemap_op(const ushort4 *__restrict__ hdr, uchar4 *__restrict__ out, float4 *__restrict__ out_f32,
                                                     size_t first_pixel, size_t n_pixels, const unsigned char *__restrict__ srgb_lut,
-                                                    uint32_t output_format, const float *__restrict__ scale_ptr, float scale_arg, float white_sq) {
+                                                    uint32_t output_format, const float *__restrict__ scale_ptr, float scale_arg, float white_sq,
+                                                    R3nBloomComposite bloom) {
     const bool bgr = (output_format & 1u) != 0u, manual = (output_format & 2u) != 0u;
     const size_t pair = (size_t)blockIdx.x * 256u + threadIdx.x;
     const size_t i0 = first_pixel + pair * 2u;
@@ -134,6 +141,34 @@ __global__ __launch_bounds__(256) void k_tonemap_op(const ushort4 *__restrict__ 
     const float scale = scale_ptr != nullptr ? *scale_ptr : scale_arg;  // uniform
     ushort4 h[2];
     load_pair(hdr, i0, two, h);
+    float glow[2][3] = {};
+    if (BLOOM) {
+        const ushort4 *__restrict__ a0 = bloom.a0;
+        const int bw = (int)bloom.bw, bh = (int)bloom.bh;
+        const uint32_t y0 = (uint32_t)i0 / bloom.width, x0 = (uint32_t)i0 - y0 * bloom.width;
+        if (two && (x0 & 1u) == 0u && x0 + 1u < bloom.width) {
+            const int X = (int)(x0 >> 1), yn = bloom_rule::up_near((int)y0), yf = bloom_rule::up_far((int)y0, bh);
+            const int xl = bloom_rule::clampi(X - 1, 0, bw - 1), xr = bloom_rule::clampi(X + 1, 0, bw - 1);
+            const ushort4 mn = a0[(size_t)yn * bw + X], mf = a0[(size_t)yf * bw + X];
+            const ushort4 ln = a0[(size_t)yn * bw + xl], lf = a0[(size_t)yf * bw + xl], rn = a0[(size_t)yn * bw + xr], rf = a0[(size_t)yf * bw + xr];
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                const float n = bloom_chan(mn, j), f = bloom_chan(mf, j);
+                glow[0][j] = bloom_rule::up_col(bloom_rule::up_row(n, bloom_chan(ln, j)), bloom_rule::up_row(f, bloom_chan(lf, j)));
+                glow[1][j] = bloom_rule::up_col(bloom_rule::up_row(n, bloom_chan(rn, j)), bloom_rule::up_row(f, bloom_chan(rf, j)));
+            }
+        } else {
+            const auto texel = [&](int sx, int sy, float rgb[3]) {
+                const ushort4 t = a0[(size_t)sy * bw + sx];
+                rgb[0] = half_f32(t.x); rgb[1] = half_f32(t.y); rgb[2] = half_f32(t.z);
+            };
+            bloom_rule::up_at(texel, bw, bh, (int)x0, (int)y0, glow[0]);
+            if (two) {
+                const uint32_t y1 = ((uint32_t)i0 + 1u) / bloom.width, x1 = (uint32_t)i0 + 1u - y1 * bloom.width;
+                bloom_rule::up_at(texel, bw, bh, (int)x1, (int)y1, glow[1]);
+            }
+        }
+    }
     uchar4 o8[2];
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
@@ -141,7 +176,8 @@ __global__ __launch_bounds__(256) void k_tonemap_op(const ushort4 *__restrict__ 
         unsigned short ch[3];
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
-            const float v = exposure_rule::exposed(half_f32(in[j]), scale);
+            float v = exposure_rule::exposed(half_f32(in[j]), scale);
+            if (BLOOM) v = bloom_rule::composite(v, glow[k][j], bloom.intensity);
             const float y = OP == R3N_TONEMAP_OP_REINHARD ? exposure_rule::op_reinhard(v, white_sq)
                           : OP == R3N_TONEMAP_OP_ACES   ? exposure_rule::op_aces(v) : v;
             ch[j] = __builtin_bit_cast(unsigned short, (_Float16)y);
@@ -179,18 +215,24 @@ int r3n_internal_exposure_update(ExposureBlock *block, int prev, int cur, const 
 }
 
 int r3n_internal_tonemap_op(const ushort4 *hdr, uchar4 *out, float4 *out_f32, size_t first_pixel, size_t n_pixels, const unsigned char *srgb_lut,
-                            uint32_t output_format, uint32_t op, const float *scale_ptr, float scale, float white_sq, hipStream_t stream) {
+                            uint32_t output_format, uint32_t op, const float *scale_ptr, float scale, float white_sq, const R3nBloomComposite *bloom,
+                            hipStream_t stream) {
     const size_t pairs = (n_pixels + 1) / 2;
     const dim3 grid((unsigned)((pairs + 255) / 256));
-    if (op == R3N_TONEMAP_OP_REINHARD)
-        hipLaunchKernelGGL(k_tonemap_op<R3N_TONEMAP_OP_REINHARD>, grid, dim3(256), 0, stream, hdr, out, out_f32, first_pixel, n_pixels, srgb_lut,
-                           output_format, scale_ptr, scale, white_sq);
-    else if (op == R3N_TONEMAP_OP_ACES)
-        hipLaunchKernelGGL(k_tonemap_op<R3N_TONEMAP_OP_ACES>, grid, dim3(256), 0, stream, hdr, out, out_f32, first_pixel, n_pixels, srgb_lut,
-                           output_format, scale_ptr, scale, white_sq);
-    else
-        hipLaunchKernelGGL(k_tonemap_op<R3N_TONEMAP_OP_BLIT>, grid, dim3(256), 0, stream, hdr, out, out_f32, first_pixel, n_pixels, srgb_lut,
-                           output_format, scale_ptr, scale, white_sq);
+    const R3nBloomComposite b = bloom ? *bloom : R3nBloomComposite{};
+#define R3N_LAUNCH_OP(OP, BLOOM)                                                                                                       \
+    hipLaunchKernelGGL((k_tonemap_op<OP, BLOOM>), grid, dim3(256), 0, stream, hdr, out, out_f32, first_pixel, n_pixels, srgb_lut, output_format, \
+                       scale_ptr, scale, white_sq, b)
+    if (bloom) {
+        if (op == R3N_TONEMAP_OP_REINHARD) R3N_LAUNCH_OP(R3N_TONEMAP_OP_REINHARD, true);
+        else if (op == R3N_TONEMAP_OP_ACES) R3N_LAUNCH_OP(R3N_TONEMAP_OP_ACES, true);
+        else R3N_LAUNCH_OP(R3N_TONEMAP_OP_BLIT, true);
+    } else {
+        if (op == R3N_TONEMAP_OP_REINHARD) R3N_LAUNCH_OP(R3N_TONEMAP_OP_REINHARD, false);
+        else if (op == R3N_TONEMAP_OP_ACES) R3N_LAUNCH_OP(R3N_TONEMAP_OP_ACES, false);
+        else R3N_LAUNCH_OP(R3N_TONEMAP_OP_BLIT, false);
+    }
+#undef R3N_LAUNCH_OP
     return launch_status();
 }
 

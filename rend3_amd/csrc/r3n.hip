@@ -17,6 +17,7 @@
 #include "comm.h"
 #include "hip_owned.h"
 #include "exposure.h"
+#include "bloom.h"
 #include "kernels_cull.h"
 #include "kernels_raster.h"
 #define R3N_SHADE_DECL_ONLY
@@ -208,6 +209,8 @@ struct r3n_ctx {
         uint32_t big_grid = R3N_BIG_GRID, small_grid = R3N_SMALL_GRID;
         uint32_t comm_serial = 1;  // r3n_comm_init: the three communicators' collectives in ONE total order per device (comm_order_*)
         uint32_t shadow_occlusion = 1;  // r3n_render_frame: two-phase depth draw of the shadow views (0: everything drawn in one phase)
+        uint32_t bloom_tail = R3N_BLOOM_TAIL_DEFAULT;  // bloom: levels of at most this many texels go down and up in ONE launch (0: never)
+        uint32_t bloom_keep_down = 0;   // bloom: the up chain writes a second pyramid, so r3n_readback_bloom can show the down chain too
         uint32_t front_end_fast = 1;    // triangle cull and raster setup: packed transforms, no divisions where every w of a wave is 1, no depth
                                         // in a shadow view's cull (kernels_cull.h, kernels_raster.h; 0: the plain forms, same results)
     } tune;
@@ -312,6 +315,15 @@ struct r3n_ctx {
     DeviceBuffer exposure_block;
     int exp_committed = 0, exp_shown = -1;
     bool exp_metered_this_frame = false, exp_reset = true;
+    // r3n_bloom_set (bloom.h).  One pyramid per context (two blocks of it under tune.bloom_keep_down): the chain that writes it and
+    // the operator that reads it are enqueued together on one stream, and whichever stream a later frame's chain uses is ordered
+    // behind that operator (the argument above tonemap_with_options), so frames in flight never share it.  bloom_shown: the last
+    // r3n_tonemap ran the chain -- what the float tap of r3n_readback_output composites and r3n_readback_bloom returns.
+    bool bloom_on = false, bloom_shown = false, bloom_shown_kept = false;
+    bloom_rule::Params bloom_params{}, bloom_shown_params{};
+    BloomPlan bloom_plan_shown{};
+    uint32_t bloom_w = 0, bloom_h = 0;
+    DeviceBuffer bloom_pyramid;
     DeviceBuffer big_items[1 + R3N_QLANES];
     DeviceSpan big_count[1 + R3N_QLANES];  // work queues: [0] the viewport's, 1.. one per concurrently drawn shadow view
     uint32_t forward_index_lane[1 + R3N_QLANES] = {};
@@ -819,7 +831,8 @@ int apply_tuning(r3n_ctx *c, const char *kv) {
             {"cut_small_lds", &t.cut_small_lds, 0, 65536, 1}, {"vp_cut_small_lds", &t.vp_cut_small_lds, 0, 65536, 1}, {"cull_lds", &t.cull_lds, 0, 65000, 1}, {"vp_cull_lds", &t.vp_cull_lds, 0, 65000, 1},
             {"resolve_lds", &t.resolve_lds, 0, 61440, 1}, {"big_grid", &t.big_grid, 256, 65536, 1},
             {"small_grid", &t.small_grid, R3N_SUBQ, 32768, R3N_SUBQ}, {"timed_pipeline", &t.timed_pipeline, 0, 1, 1},
-            {"comm_serial", &t.comm_serial, 0, 1, 1}, {"shadow_occlusion", &t.shadow_occlusion, 0, 1, 1}, {"front_end_fast", &t.front_end_fast, 0, 1, 1}, {"prio_main", &t.prio_main, 0, 2, 1}, {"prio_shade", &t.prio_shade, 0, 2, 1}, {"prio_aux", &t.prio_aux, 0, 2, 1}};  // (read at r3n_create only)  // (a multiple of R3N_SUBQ: whole blocks per sub-list)
+            {"comm_serial", &t.comm_serial, 0, 1, 1}, {"shadow_occlusion", &t.shadow_occlusion, 0, 1, 1}, {"front_end_fast", &t.front_end_fast, 0, 1, 1},
+            {"bloom_tail", &t.bloom_tail, 0, 1u << 24, 1}, {"bloom_keep_down", &t.bloom_keep_down, 0, 1, 1}, {"prio_main", &t.prio_main, 0, 2, 1}, {"prio_shade", &t.prio_shade, 0, 2, 1}, {"prio_aux", &t.prio_aux, 0, 2, 1}};  // (read at r3n_create only)  // (a multiple of R3N_SUBQ: whole blocks per sub-list)
         bool known = false;
         for (auto &k : keys)
             if (key == k.name) {
@@ -3568,11 +3581,21 @@ static int launch_tonemap(r3n_ctx *c, float4 *f32_out, hipStream_t stream = null
     if (!stream) stream = c->stream;
     const size_t first = (size_t)r0 * c->width, n = (size_t)(r1 - r0) * c->width;
     Timed t(c, R3N_STAGE_TONEMAP, stream);
-    if (c->tm_on) {
-        const bool metered = c->tm_params.exposure_mode == R3N_EXPOSURE_AUTO && c->exp_shown >= 0 && c->exposure_block.p;
+    const bool bloom = c->bloom_shown && c->bloom_w == c->width && c->bloom_h == c->height && c->bloom_pyramid.p;
+    if (c->tm_on || bloom) {
+        const bool metered = c->tm_on && c->tm_params.exposure_mode == R3N_EXPOSURE_AUTO && c->exp_shown >= 0 && c->exposure_block.p;
         const float *scale_ptr = metered ? &c->exposure_block.as<ExposureBlock>()->state[c->exp_shown].scale : nullptr;
+        R3nBloomComposite comp{};
+        if (bloom) {  // level 0 of the up chain: the second block where the down chain was kept
+            const BloomPlan &bp = c->bloom_plan_shown;
+            comp.a0 = c->bloom_pyramid.as<ushort4>() + (c->bloom_shown_kept ? bp.total : 0u) + bp.off[0];
+            comp.bw = bp.lv.w[0]; comp.bh = bp.lv.h[0]; comp.width = c->width;
+            comp.intensity = c->bloom_shown_params.intensity;
+        }
+        // (without r3n_tonemap_set options tm_params is BLIT / MANUAL and the manual scale 1)
         HIP_TRY(c, (hipError_t)r3n_internal_tonemap_op(c->hdr16.as<ushort4>(), c->out8.as<uchar4>(), f32_out, first, n, c->srgb_lut.as<unsigned char>(),
-                                                       c->output_format, c->tm_params.op, scale_ptr, c->tm_manual_scale, c->tm_params.white_sq, stream));
+                                                       c->output_format, c->tm_params.op, scale_ptr, c->tm_manual_scale, c->tm_params.white_sq,
+                                                       bloom ? &comp : nullptr, stream));
         return R3N_OK;
     }
     HIP_TRY(c, (hipError_t)r3n_internal_tonemap(c->hdr16.as<ushort4>(), c->out8.as<uchar4>(), f32_out, first, n, c->srgb_lut.as<unsigned char>(),
@@ -3625,14 +3648,71 @@ int r3n_tonemap_set(r3n_ctx *c, const r3n_tonemap_opts *o) {
     return R3N_OK;
 }
 
-// [histogram, metering step,] operator over the HDR target, behind the resolve ON ITS STREAM: while frames are in flight that is the
+int r3n_bloom_set(r3n_ctx *c, const r3n_bloom_opts *o) {
+    if (!c) return R3N_ERR_INVALID_ARG;
+    if (c->in_frame) return fail(c, R3N_ERR_STATE, "bloom_set: inside a frame");
+    bloom_rule::Params p{};
+    bool on = false;
+    if (o) {
+        for (float f : {o->intensity, o->threshold, o->knee, o->scatter})
+            if (f != f) return fail(c, R3N_ERR_INVALID_ARG, "bloom_set: NaN");
+        if (!(o->intensity >= 0.0f && o->intensity <= 1024.0f)) return fail(c, R3N_ERR_INVALID_ARG, "bloom_set: intensity outside [0, 1024]");
+        if (!(o->threshold >= 0.0f && o->threshold <= R3N_EXP_MAX_HALF)) return fail(c, R3N_ERR_INVALID_ARG, "bloom_set: threshold outside [0, 65504]");
+        if (!(o->knee >= 0.0f && o->knee <= o->threshold)) return fail(c, R3N_ERR_INVALID_ARG, "bloom_set: knee outside [0, threshold]");
+        if (!(o->scatter >= 0.0f && o->scatter <= 1.0f)) return fail(c, R3N_ERR_INVALID_ARG, "bloom_set: scatter outside [0, 1]");
+        if (o->max_levels < 1u || o->max_levels > R3N_BLOOM_MAX_LEVELS) return fail(c, R3N_ERR_INVALID_ARG, "bloom_set: max_levels outside [1, 16]");
+        p = bloom_rule::make_params(o->intensity, o->threshold, o->knee, o->scatter, o->max_levels);
+        on = o->intensity != 0.0f;
+    }
+    c->bloom_on = on;
+    c->bloom_params = p;
+    return R3N_OK;
+}
+
+// The bloom chain on `stream`, in front of the operator: the levels above the tail one launch each going down, the tail in one
+// launch down and up, then the remaining levels one launch each going up.  scale_ptr: the scale word this call's metering step
+// produced (AUTO), else the manual scale.
+static int bloom_chain(r3n_ctx *c, const float *scale_ptr, hipStream_t stream) {
+    const bool keep = c->tune.bloom_keep_down != 0u;
+    const BloomPlan plan = bloom_plan(c->width, c->height, c->bloom_params.max_levels, c->tune.bloom_tail);
+    TRY(ensure(c, c->bloom_pyramid, (size_t)plan.total * 8u * (keep ? 2u : 1u), false, -1));
+    ushort4 *d = c->bloom_pyramid.as<ushort4>(), *a = keep ? d + plan.total : d;
+    const bloom_rule::Params &p = c->bloom_params;
+    const ushort4 *hdr = c->hdr16.as<ushort4>();
+    const uint32_t L = plan.lv.n, T = plan.tail;
+    for (uint32_t k = 0; k < T; ++k) {
+        Timed t(c, R3N_STAGE_TONEMAP, stream);
+        HIP_TRY(c, (hipError_t)r3n_internal_bloom_down(hdr, c->width, c->height, d, &plan, k, &p, scale_ptr, c->tm_manual_scale, stream));
+    }
+    if (T < L) {
+        Timed t(c, R3N_STAGE_TONEMAP, stream);
+        HIP_TRY(c, (hipError_t)r3n_internal_bloom_tail(hdr, c->width, c->height, d, a, &plan, &p, scale_ptr, c->tm_manual_scale, stream));
+    } else if (keep) {  // a_{L-1} = d_{L-1} (the diagnostic mode alone copies it)
+        HIP_TRY(c, hipMemcpyAsync(a + plan.off[L - 1u], d + plan.off[L - 1u], (size_t)plan.lv.w[L - 1u] * plan.lv.h[L - 1u] * 8u, hipMemcpyDeviceToDevice, stream));
+    }
+    for (uint32_t k = std::min(T, L - 1u); k-- > 0u;) {
+        Timed t(c, R3N_STAGE_TONEMAP, stream);
+        HIP_TRY(c, (hipError_t)r3n_internal_bloom_up(d, a, &plan, k, &p, stream));
+    }
+    c->bloom_plan_shown = plan;
+    c->bloom_shown_params = p;
+    c->bloom_shown_kept = keep;
+    c->bloom_w = c->width; c->bloom_h = c->height;
+    c->bloom_shown = true;
+    return R3N_OK;
+}
+
+// [histogram, metering step,] [bloom chain,] operator over the HDR target, behind the resolve ON ITS STREAM: while frames are in flight that is the
 // shade stream (as for the skybox), so the main stream goes on with the next frame; the state steps in frame order either way,
 // because whichever stream a later frame uses is ordered behind this one (join_shade / the resolve's own stream order).
 static int tonemap_with_options(r3n_ctx *c) {
     const uint32_t r0 = std::min(c->row_begin, c->height), r1 = std::min(c->row_end, c->height);
-    const bool automatic = c->tm_params.exposure_mode == R3N_EXPOSURE_AUTO;
+    const bool automatic = c->tm_on && c->tm_params.exposure_mode == R3N_EXPOSURE_AUTO;
     if (automatic && !(r0 == 0u && r1 == c->height))
         return fail(c, R3N_ERR_UNSUPPORTED, "tonemap: auto-exposure meters the whole target; this context's row range leaves rows out");
+    if (c->bloom_on && !(r0 == 0u && r1 == c->height))
+        return fail(c, R3N_ERR_UNSUPPORTED, "tonemap: bloom needs neighbouring rows; this context's row range leaves rows out");
+    if (c->bloom_on && (uint64_t)c->width * c->height > 0xFFFFFFFFull) return fail(c, R3N_ERR_UNSUPPORTED, "tonemap: bloom indexes pixels in 32 bits");
     const bool fresh = automatic && !c->exposure_block.p;  // the block's fill and tables go through the main stream
     const bool on_shade = c->resolve_on_shade && c->shade_unjoined && c->shade_last == c->slot && !fresh;
     hipStream_t stream = on_shade ? (hipStream_t)c->shade : (hipStream_t)c->stream;
@@ -3656,6 +3736,11 @@ static int tonemap_with_options(r3n_ctx *c) {
         }
         c->exp_shown = 1 - c->exp_committed;
         c->exp_metered_this_frame = true;
+    }
+    c->bloom_shown = false;
+    if (c->bloom_on && c->width && c->height) {
+        const bool metered = automatic && c->exp_shown >= 0;
+        TRY(bloom_chain(c, metered ? &c->exposure_block.as<ExposureBlock>()->state[c->exp_shown].scale : nullptr, stream));
     }
     TRY(launch_tonemap(c, nullptr, stream));
     // whatever waits for the resolve -- the frame that reuses these targets, the read-backs -- waits for this as well
@@ -3721,7 +3806,8 @@ int r3n_tonemap(r3n_ctx *c, void *host_rgba8, uint64_t pitch) {
     HIP_TRY(c, hipSetDevice(c->device));
     // the blit is fused into r3n_resolve_opaque (same arithmetic on the Rgba16Float-rounded value); the separate
     // kernel only runs when the HDR buffer was produced some other way
-    if (c->tm_on) {  // r3n_tonemap_set: whatever the resolve fused is overwritten
+    if (!c->bloom_on) c->bloom_shown = false;  // no bloom in what this frame shows: the float tap composites none
+    if (c->tm_on || c->bloom_on) {  // r3n_tonemap_set / r3n_bloom_set: whatever the resolve fused is overwritten
         TRY(tonemap_with_options(c));
     } else if (!c->resolved_this_frame) {
         TRY(join_shade(c));
@@ -4473,6 +4559,29 @@ int r3n_readback_output(r3n_ctx *c, uint8_t *rgba8, float *rgba_f32) {
     }
     if (rgba8) TRY(copy_d2h(c, rgba8, c->out8.p, n * 4));
     return check_async_status(c);
+}
+
+int r3n_readback_bloom(r3n_ctx *c, uint32_t level, uint16_t *rgb16f, uint64_t capacity_texels, uint32_t *width, uint32_t *height, uint32_t *levels) {
+    if (!c) return R3N_ERR_INVALID_ARG;
+    if (!c->bloom_shown || !c->bloom_pyramid.p) return fail(c, R3N_ERR_STATE, "readback_bloom: the last r3n_tonemap ran no bloom");
+    const BloomPlan &bp = c->bloom_plan_shown;
+    const uint32_t L = bp.lv.n;
+    if (levels) *levels = L;
+    const bool down = level >= L;
+    const uint32_t k = down ? level - L : level;
+    if (k >= L || (down && !c->bloom_shown_kept)) return fail(c, R3N_ERR_INVALID_ARG, "readback_bloom: no such level (the down chain is kept under bloom_keep_down=1 only)");
+    if (width) *width = bp.lv.w[k];
+    if (height) *height = bp.lv.h[k];
+    if (!rgb16f) return R3N_OK;
+    const size_t n = (size_t)bp.lv.w[k] * bp.lv.h[k];
+    if (capacity_texels < n) return fail(c, R3N_ERR_INVALID_ARG, "readback_bloom: buffer too small");
+    // the up chain lies in the second block where the down chain was kept, else in the only one
+    const ushort4 *src = c->bloom_pyramid.as<ushort4>() + ((c->bloom_shown_kept && !down) ? bp.total : 0u) + bp.off[k];
+    std::vector<uint16_t> texels(n * 4u);
+    TRY(d2h(c, texels.data(), src, n * 8u));
+    for (size_t i = 0; i < n; ++i)
+        for (int ch = 0; ch < 3; ++ch) rgb16f[i * 3u + ch] = texels[i * 4u + ch];
+    return R3N_OK;
 }
 
 int r3n_readback_exposure(r3n_ctx *c, r3n_exposure_state *out) {

@@ -213,6 +213,29 @@ def tonemap_opts(operator="blit", exposure_ev=0.0, white=4.0, auto_exposure=None
     return o
 
 
+def bloom_opts(intensity=0.04, threshold=1.0, knee=0.5, scatter=0.7, max_levels=8):
+    """Renderer.set_bloom's arguments as an r3n_bloom_opts; what r3n_bloom_set would refuse raises here."""
+    vals = dict(intensity=intensity, threshold=threshold, knee=knee, scatter=scatter)
+    for name, v in vals.items():
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.floating, np.integer)) or math.isnan(v):
+            raise ValueError(f"set_bloom: {name} is a number, not {v!r}")
+    if not 0.0 <= intensity <= 1024.0:
+        raise ValueError("set_bloom: intensity lies within [0, 1024]")
+    if not 0.0 <= threshold <= 65504.0:
+        raise ValueError("set_bloom: threshold lies within [0, 65504] (exposed units: 1 is display white)")
+    if not 0.0 <= knee <= threshold:
+        raise ValueError("set_bloom: knee lies within [0, threshold]")
+    if not 0.0 <= scatter <= 1.0:
+        raise ValueError("set_bloom: scatter lies within [0, 1]")
+    if isinstance(max_levels, bool) or int(max_levels) != max_levels or not 1 <= max_levels <= _ffi.BLOOM_MAX_LEVELS:
+        raise ValueError(f"set_bloom: max_levels is an integer within [1, {_ffi.BLOOM_MAX_LEVELS}]")
+    o = _ffi.BloomOpts()
+    o.intensity, o.threshold, o.knee, o.scatter, o.max_levels = float(intensity), float(threshold), float(knee), float(scatter), int(max_levels)
+    if not (0.0 <= o.knee <= o.threshold):  # (as the ABI compares them: after the rounding to f32)
+        raise ValueError("set_bloom: knee lies within [0, threshold]")
+    return o
+
+
 class CameraSpecifier:
     """rend3-routine/src/common/camera.rs:3-35"""
     VIEWPORT = _ffi.CAMERA_VIEWPORT
@@ -1765,6 +1788,34 @@ class Renderer:
         return dict(histogram=np.array(st.histogram[:], dtype=np.uint32), excluded=int(st.excluded), valid=int(st.valid),
                     mean_log2=f32(st.mean_log2), target_ev=f32(st.target_ev), current_ev=f32(st.current_ev), scale=f32(st.scale))
 
+    def set_bloom(self, intensity=0.04, threshold=1.0, knee=0.5, scatter=0.7, max_levels=8):
+        """Bloom in front of the tonemapping operator (r3n_bloom_set; hangs on rend3-routine/src/tonemapping.rs:1-10 like the
+        operators): what is brighter than `threshold` in exposed units (1 = display white, under auto-exposure too), with a soft
+        `knee` around it, is spread through a pyramid of at most `max_levels` levels -- `scatter` is the share of each coarser level
+        added on the way up -- and added back times `intensity`.  set_bloom(None), or an intensity of 0, switches it off: the
+        frame is then what it is without it, launch for launch.  Between frames only; independent of set_tonemapping."""
+        if intensity is None:
+            self._check(self.lib.r3n_bloom_set(self.ctx, None), "r3n_bloom_set")
+            return
+        o = bloom_opts(intensity, threshold, knee, scatter, max_levels)
+        self._check(self.lib.r3n_bloom_set(self.ctx, ctypes.byref(o)), "r3n_bloom_set")
+
+    def readback_bloom(self, level):
+        """Level `level` of the bloom pyramid as the last tonemapping node left it (waits for it): (h, w, 3) uint16 half bits.
+        Levels past the last one read the down chain, which is kept under R3N_TUNE bloom_keep_down=1 only."""
+        w, h, n = _ffi.u32(0), _ffi.u32(0), _ffi.u32(0)
+        self._check(self.lib.r3n_readback_bloom(self.ctx, int(level), None, 0, ctypes.byref(w), ctypes.byref(h), ctypes.byref(n)), "r3n_readback_bloom")
+        out = np.zeros((h.value, w.value, 3), dtype=np.uint16)
+        self._check(self.lib.r3n_readback_bloom(self.ctx, int(level), _ffi.ptr(out), out.size // 3, ctypes.byref(w), ctypes.byref(h), ctypes.byref(n)),
+                    "r3n_readback_bloom")
+        return out
+
+    def bloom_levels(self):
+        """Number of levels of the pyramid the last tonemapping node built."""
+        n = _ffi.u32(0)
+        self._check(self.lib.r3n_readback_bloom(self.ctx, 0, None, 0, None, None, ctypes.byref(n)), "r3n_readback_bloom")
+        return int(n.value)
+
     def set_skinning_mode(self, mode):
         """0 = R3N_SKIN_EXACT (vector ALU, default), 1 = R3N_SKIN_MFMA (matrix cores; rigs of at most four joints)."""
         self._check(self.lib.r3n_set_skinning_mode(self.ctx, int(mode)), "r3n_set_skinning_mode")
@@ -1980,6 +2031,10 @@ class TonemappingRoutine:
     def set_tonemapping(self, renderer, *args, **kwargs):
         """Renderer.set_tonemapping through the routine (the operators tonemapping.rs:1-10 announces)."""
         renderer.set_tonemapping(*args, **kwargs)
+
+    def set_bloom(self, renderer, *args, **kwargs):
+        """Renderer.set_bloom through the routine."""
+        renderer.set_bloom(*args, **kwargs)
 
     def add_to_graph(self, graph):
         def body(r, ev):

@@ -116,6 +116,13 @@ def add_arguments(ap):
     ap.add_argument("--auto-exposure", action="store_true",
                     help="meter the exposure on the GPU from a luminance histogram of the HDR target (the auto-exposure the reference's "
                          "tonemapping.rs:1-10 waits for)")
+    ap.add_argument("--bloom", type=float, default=0.0, metavar="INTENSITY",
+                    help="bloom in front of the tonemapping operator (r3n_bloom_set): the share of the blurred highlights added back; 0 = off")
+    ap.add_argument("--bloom-threshold", type=float, default=1.0, metavar="T",
+                    help="with --bloom: what is brighter than T after the exposure blooms (1 = display white)")
+    ap.add_argument("--bloom-knee", type=float, default=0.5, metavar="K", help="with --bloom: half width of the soft knee around the threshold")
+    ap.add_argument("--bloom-scatter", type=float, default=0.7, metavar="S", help="with --bloom: share of each coarser level added on the way up, in [0, 1]")
+    ap.add_argument("--bloom-levels", type=int, default=8, metavar="N", help="with --bloom: most levels of the pyramid, 1..16")
     return ap
 
 
@@ -139,7 +146,9 @@ def settings_from(args):
                 texture_skip_mips=getattr(args, "texture_skip_mips", 0),
                 mesh_upload=getattr(args, "mesh_upload", "append"), mesh_compact=getattr(args, "mesh_compact", None),
                 tonemap=getattr(args, "tonemap", "blit"), exposure=getattr(args, "exposure", 0.0),
-                auto_exposure=getattr(args, "auto_exposure", False))
+                auto_exposure=getattr(args, "auto_exposure", False),
+                bloom=getattr(args, "bloom", 0.0), bloom_threshold=getattr(args, "bloom_threshold", 1.0), bloom_knee=getattr(args, "bloom_knee", 0.5),
+                bloom_scatter=getattr(args, "bloom_scatter", 0.7), bloom_levels=getattr(args, "bloom_levels", 8))
 
 
 def default_settings(**over):
@@ -214,6 +223,11 @@ def build(r, hm, mk, settings):
         from .renderer import AutoExposure
         r.set_tonemapping(settings.get("tonemap", "blit"), exposure_ev=settings.get("exposure", 0.0),
                           auto_exposure=AutoExposure() if settings.get("auto_exposure") else None)
+    if settings.get("bloom", 0.0) != 0.0:
+        if not hasattr(r, "set_bloom"):  # (a renderer that only has the reference's blit fails here)
+            raise ValueError("--bloom: this renderer has the blit alone")
+        r.set_bloom(settings["bloom"], threshold=settings.get("bloom_threshold", 1.0), knee=settings.get("bloom_knee", 0.5),
+                    scatter=settings.get("bloom_scatter", 0.7), max_levels=settings.get("bloom_levels", 8))
     if settings.get("blend_sort", "host") != "host":  # (a renderer that cannot sort on the device fails here)
         if not hasattr(r, "blend_sort"):
             raise ValueError("--blend-sort gpu: this renderer has no device sort")
