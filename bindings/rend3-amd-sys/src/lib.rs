@@ -69,6 +69,9 @@ pub const R3N_PROBE_ALPHA: i32 = 5;
 pub const R3N_PROBE_ALPHA_SHORT: i32 = 6;
 pub const R3N_PROBE_BATCHED: i32 = 7;
 pub const R3N_PROBE_FORM_COUNT: i32 = 8;
+pub const R3N_CUBE_SOURCE_CUBE: u32 = 0;
+pub const R3N_CUBE_SOURCE_EQUIRECT: u32 = 1;
+pub const R3N_CUBE_ENCODING_RGBE8: u32 = 0x100;
 pub const R3N_OUTPUT_RGBA8_UNORM_SRGB: u32 = 0;
 pub const R3N_OUTPUT_BGRA8_UNORM_SRGB: u32 = 1;
 pub const R3N_OUTPUT_RGBA8_UNORM: u32 = 2;
@@ -452,6 +455,18 @@ pub struct r3n_sample_result52 {
 
 #[repr(C)]
 #[derive(Clone, Copy)]
+pub struct r3n_cube_source {
+    pub kind: u32,
+    pub format: u32,
+    pub width: u32,
+    pub height: u32,
+    pub face_extent: u32,
+    pub mips: u32,
+    pub offset: u64,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
 pub struct r3n_tonemap_opts {
     pub op: u32,
     pub exposure_mode: u32,
@@ -611,6 +626,7 @@ extern "C" {
     pub fn r3n_sample_probe(ctx: *mut r3n_ctx, form: u32, queries: *const r3n_sample_query40, n: u32, out: *mut r3n_sample_result52) -> c_int;
     pub fn r3n_texture_cubes_write(ctx: *mut r3n_ctx, descs: *const r3n_texture_desc32, n_cubes: u32, texels: *const u32, n_texels: u64) -> c_int;
     pub fn r3n_texture_cubes_write_encoded(ctx: *mut r3n_ctx, descs: *const r3n_texture_desc32, n_cubes: u32, payload: *const c_void, payload_bytes: u64) -> c_int;
+    pub fn r3n_texture_cubes_write_sources(ctx: *mut r3n_ctx, sources: *const r3n_cube_source, n_cubes: u32, payload: *const c_void, payload_bytes: u64) -> c_int;
     pub fn r3n_skybox_set(ctx: *mut r3n_ctx, cube_id: u32) -> c_int;
     pub fn r3n_blend_order_write(ctx: *mut r3n_ctx, objects_back_to_front: *const u32, n: u32) -> c_int;
     pub fn r3n_blend_objects_write(ctx: *mut r3n_ctx, slots: *const u32, locations: *const f32, n: u32) -> c_int;

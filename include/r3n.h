@@ -551,6 +551,33 @@ int r3n_texture_cubes_write(r3n_ctx *ctx, const r3n_texture_desc32 *descs, uint3
  *      a one-level RGBA8 cube gives the same device words and frames through either entry. */
 int r3n_texture_cubes_write_encoded(r3n_ctx *ctx, const r3n_texture_desc32 *descs, uint32_t n_cubes, const void *payload,
                                     uint64_t payload_bytes);
+/*      The same array from SOURCES of two kinds, so that an HDR environment can be uploaded as the file it ships as: one
+ *      equirectangular (latitude / longitude) panorama.  Replaces the whole cube array like the two entries above.
+ *      R3N_CUBE_SOURCE_CUBE: what r3n_texture_cubes_write_encoded takes -- width == height == face_extent == N, `mips` stored levels,
+ *      LayerMajor from `offset`; the same refusals; an array of such sources gives the same pool words and descriptors as that entry.
+ *      R3N_CUBE_SOURCE_EQUIRECT: ONE stored level of width x height texels at `offset` (4-byte aligned; any width, height in
+ *      1 .. 65535, 2 : 1 is not required; row 0 is +Y, the panorama's centre column looks along +X), in R3N_CUBE_ENCODING_RGBE8
+ *      (Radiance RGBE, four bytes r g b e per texel: a source encoding of this entry only, not a texture format) or in any format
+ *      r3n_textures_write_encoded accepts.  The device resamples it into six faces of face_extent = N in 1 .. 16384 texels and builds
+ *      `mips` in 1 .. floor(log2 N) + 1 levels of every face (DESIGN.md section 2 "Cubes from panoramas"; csrc/equirect_rule.h is the
+ *      rule).  The cube lands in the f32 class, 16 bytes per texel, whatever the source format.
+ *      Refused before anything changes: an unknown kind or format, a zero extent, a source extent above 65535, N above 16384, more
+ *      mips than N has, data outside `payload`, a misaligned offset -> R3N_ERR_INVALID_ARG; a cube pool or scratch block beyond 2^32
+ *      words, or more than 2^31 wave slots in one launch -> R3N_ERR_CAPACITY; inside a frame -> R3N_ERR_STATE.
+ *      Synchronises; its scratch block is freed before it returns.  A skybox bound to a cube that no longer exists is unbound. */
+#define R3N_CUBE_SOURCE_CUBE 0u
+#define R3N_CUBE_SOURCE_EQUIRECT 1u
+#define R3N_CUBE_ENCODING_RGBE8 0x100u /* `format` of an EQUIRECT source: Radiance RGBE8 */
+typedef struct r3n_cube_source {   /* 32 B */
+    uint32_t kind;          /* R3N_CUBE_SOURCE_* */
+    uint32_t format;        /* R3N_TEXTURE_*, or R3N_CUBE_ENCODING_RGBE8 (EQUIRECT only) */
+    uint32_t width, height; /* the stored level 0: N x N for CUBE, the panorama for EQUIRECT */
+    uint32_t face_extent;   /* N */
+    uint32_t mips;          /* levels of the cube */
+    uint64_t offset;        /* bytes into payload */
+} r3n_cube_source;
+int r3n_texture_cubes_write_sources(r3n_ctx *ctx, const r3n_cube_source *sources, uint32_t n_cubes, const void *payload,
+                                    uint64_t payload_bytes);
 /*      SkyboxRoutine::set_background_texture (rend3-routine/src/skybox.rs): cube_id 0 = no skybox, i + 1 = cube i of the array
  *      above; an id past the array -> R3N_ERR_INVALID_ARG.  Between frames only (R3N_ERR_STATE inside one). */
 int r3n_skybox_set(r3n_ctx *ctx, uint32_t cube_id);

@@ -54,6 +54,7 @@ SIGNATURES = {
     "r3n_sample_probe": (cint, [vp, u32, vp, u32, vp]),
     "r3n_texture_cubes_write": (cint, [vp, vp, u32, vp, u64]),
     "r3n_texture_cubes_write_encoded": (cint, [vp, vp, u32, vp, u64]),
+    "r3n_texture_cubes_write_sources": (cint, [vp, vp, u32, vp, u64]),
     "r3n_skybox_set": (cint, [vp, u32]),
     "r3n_animation_write": (cint, [vp, vp, u32, vp, u32, vp, u32, vp, u32, vp, u32, vp, u32]),
     "r3n_pose_skeletons": (cint, [vp, vp, u32]),
@@ -264,6 +265,15 @@ BLOOM_MAX_LEVELS = 16  # R3N_BLOOM_MAX_LEVELS
 class BloomOpts(ctypes.Structure):
     """r3n_bloom_opts"""
     _fields_ = [("intensity", cfloat), ("threshold", cfloat), ("knee", cfloat), ("scatter", cfloat), ("max_levels", u32), ("_pad", u32 * 3)]
+
+
+CUBE_SOURCE_CUBE, CUBE_SOURCE_EQUIRECT = 0, 1  # R3N_CUBE_SOURCE_*
+CUBE_ENCODING_RGBE8 = 0x100                     # R3N_CUBE_ENCODING_RGBE8
+
+
+class CubeSource(ctypes.Structure):
+    """r3n_cube_source"""
+    _fields_ = [("kind", u32), ("format", u32), ("width", u32), ("height", u32), ("face_extent", u32), ("mips", u32), ("offset", u64)]
 
 
 class Config(ctypes.Structure):

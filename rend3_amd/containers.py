@@ -11,6 +11,9 @@ Host-side parsing only; decoding happens on the GPU (r3n_textures_write_encoded,
 
 Cube maps: parse_ktx2 / parse_dds refuse them (a material cannot use one); parse_ktx2_cube / parse_dds_cube read them for
 Renderer.add_texture_cube_encoded (the skybox), with the same format maps and error kinds.
+
+Radiance .hdr panoramas: parse_hdr reads the RGBE bytes for Renderer.add_texture_cube_equirect; they are decoded on the GPU too
+(r3n_texture_cubes_write_sources, csrc/equirect_rule.h).
 """
 import struct
 
@@ -349,3 +352,90 @@ def generate_mips_allowed(fmt):
     formats, R16Float / Rg16Float / Rgba16Float and Rgb10a2Unorm; not BCn, snorm, 32-bit float (not filterable), 16-bit norm,
     Rg11b10Float or Rgb9e5Ufloat (not render attachments)."""
     return (not is_block_format(fmt) and not is_float_format(fmt)) or fmt in (R16F, RG16F, RGBA16F, RGB10A2)
+
+
+# ---------------------------------------------------------------------------------------------- Radiance RGBE (.hdr)
+RGBE8 = 0x100  # R3N_CUBE_ENCODING_RGBE8: a source encoding of r3n_texture_cubes_write_sources, not a texture format
+
+
+def parse_hdr(data):
+    """A Radiance picture (Ward's rgbe.c): magic `#?RADIANCE` or `#?RGBE`, FORMAT=32-bit_rle_rgbe, resolution `-Y H +X W`, flat or
+    new-style run-length scanlines.  Returns {"width", "height", "rgbe": uint8[H, W, 4]}: the bytes as stored (r, g, b, e), row 0 the
+    top row -- nothing is decoded here.  Other orientations and XYZE -> TextureUnsupported; anything malformed, a truncated or an
+    overlong run -> TextureLoadError.  None when `data` does not start with a Radiance magic."""
+    import numpy as np
+    data = bytes(data)
+    if not (data.startswith(b"#?RADIANCE") or data.startswith(b"#?RGBE")):
+        return None
+    at = data.find(b"\n")
+    fmt = None
+    while True:  # header lines up to the empty one
+        if at < 0:
+            raise TextureLoadError("TextureLoad", "hdr: the header does not end")
+        end = data.find(b"\n", at + 1)
+        if end < 0:
+            raise TextureLoadError("TextureLoad", "hdr: the header does not end")
+        line = data[at + 1:end].strip()
+        at = end
+        if not line:
+            break
+        if line.startswith(b"FORMAT="):
+            fmt = line[7:].strip()
+    if fmt == b"32-bit_rle_xyze":
+        raise TextureUnsupported("hdr: FORMAT=32-bit_rle_xyze (XYZE)")
+    if fmt != b"32-bit_rle_rgbe":
+        raise TextureLoadError("TextureLoad", f"hdr: FORMAT is {fmt!r}, not 32-bit_rle_rgbe")
+    end = data.find(b"\n", at + 1)
+    if end < 0:
+        raise TextureLoadError("TextureLoad", "hdr: no resolution line")
+    res = data[at + 1:end].split()
+    if len(res) != 4 or res[0][1:] not in (b"Y", b"X") or res[2][1:] not in (b"Y", b"X") or res[0][:1] not in b"+-" or res[2][:1] not in b"+-":
+        raise TextureLoadError("TextureLoad", f"hdr: bad resolution line {data[at + 1:end]!r}")
+    if res[0] != b"-Y" or res[2] != b"+X":
+        raise TextureUnsupported(f"hdr: orientation {res[0].decode()} {res[2].decode()} (only -Y H +X W)")
+    try:
+        h, w = int(res[1]), int(res[3])
+    except ValueError:
+        raise TextureLoadError("TextureLoad", f"hdr: bad resolution line {data[at + 1:end]!r}") from None
+    if w <= 0 or h <= 0:
+        raise TextureLoadError("TextureLoad", "hdr: zero extent")
+    at = end + 1
+    out = np.empty((h, w, 4), dtype=np.uint8)
+    buf = np.frombuffer(data, dtype=np.uint8)
+    for y in range(h):
+        head = data[at:at + 4]
+        if 8 <= w <= 32767 and len(head) == 4 and head[0] == 2 and head[1] == 2 and not head[2] & 0x80:
+            if (head[2] << 8 | head[3]) != w:
+                raise TextureLoadError("TextureLoad", f"hdr: scanline {y} is {head[2] << 8 | head[3]} wide, the picture {w}")
+            at += 4
+            for ch in range(4):  # new-style: the four channels one after the other, each run-length encoded
+                x = 0
+                while x < w:
+                    if at >= len(data):
+                        raise TextureLoadError("TextureLoad", f"hdr: scanline {y} is truncated")
+                    n = data[at]
+                    at += 1
+                    if n > 128:  # a run
+                        n -= 128
+                        if at >= len(data):
+                            raise TextureLoadError("TextureLoad", f"hdr: scanline {y} is truncated")
+                        if x + n > w:
+                            raise TextureLoadError("TextureLoad", f"hdr: a run of scanline {y} passes its end")
+                        out[y, x:x + n, ch] = data[at]
+                        at += 1
+                    else:  # literals
+                        if n == 0:
+                            raise TextureLoadError("TextureLoad", f"hdr: an empty literal run in scanline {y}")
+                        if x + n > w:
+                            raise TextureLoadError("TextureLoad", f"hdr: a run of scanline {y} passes its end")
+                        if at + n > len(data):
+                            raise TextureLoadError("TextureLoad", f"hdr: scanline {y} is truncated")
+                        out[y, x:x + n, ch] = buf[at:at + n]
+                        at += n
+                    x += n
+        else:  # flat
+            if at + 4 * w > len(data):
+                raise TextureLoadError("TextureLoad", f"hdr: scanline {y} is truncated")
+            out[y] = buf[at:at + 4 * w].reshape(w, 4)
+            at += 4 * w
+    return {"width": w, "height": h, "rgbe": out}

@@ -18,6 +18,7 @@
 #include "hip_owned.h"
 #include "exposure.h"
 #include "bloom.h"
+#include "equirect.h"
 #include "kernels_cull.h"
 #include "kernels_raster.h"
 #define R3N_SHADE_DECL_ONLY
@@ -370,6 +371,10 @@ struct r3n_ctx {
     double stage_ms[R3N_STAGE_COUNT] = {0};
     int hbm_best_variant = -1;
     uint64_t stage_launches[R3N_STAGE_COUNT] = {0};
+    // cubes from panoramas (r3n_texture_cubes_write_sources; behind everything a frame touches)
+    uint32_t equirect_tail = R3N_EQUIRECT_TAIL_DEFAULT;  // R3N_TUNE equirect_tail: a face of at most this extent builds the rest of its chain in ONE launch (0: never)
+    uint64_t cube_source_launches = 0;  // kernels of the last call (r3n_internal_cube_source_launches)
+    float cube_source_ms[4] = {0, 0, 0, 0};  // with r3n_timing_enable: its copies + decode jobs, k_equirect_faces, the chain, k_cube_assemble
 };
 
 namespace {
@@ -815,6 +820,7 @@ int read_timeline(r3n_ctx *c, float *out, int max) {
 // "key=value key=value ..." -> ctx.tune (unknown keys and out-of-range values are refused: nothing is applied then)
 int apply_tuning(r3n_ctx *c, const char *kv) {
     r3n_ctx::Tune t = c->tune;
+    uint32_t equirect_tail = c->equirect_tail;
     std::string text(kv ? kv : "");
     for (size_t at = 0; at < text.size();) {
         while (at < text.size() && (text[at] == ' ' || text[at] == ',')) ++at;
@@ -832,7 +838,7 @@ int apply_tuning(r3n_ctx *c, const char *kv) {
             {"resolve_lds", &t.resolve_lds, 0, 61440, 1}, {"big_grid", &t.big_grid, 256, 65536, 1},
             {"small_grid", &t.small_grid, R3N_SUBQ, 32768, R3N_SUBQ}, {"timed_pipeline", &t.timed_pipeline, 0, 1, 1},
             {"comm_serial", &t.comm_serial, 0, 1, 1}, {"shadow_occlusion", &t.shadow_occlusion, 0, 1, 1}, {"front_end_fast", &t.front_end_fast, 0, 1, 1},
-            {"bloom_tail", &t.bloom_tail, 0, 1u << 24, 1}, {"bloom_keep_down", &t.bloom_keep_down, 0, 1, 1}, {"prio_main", &t.prio_main, 0, 2, 1}, {"prio_shade", &t.prio_shade, 0, 2, 1}, {"prio_aux", &t.prio_aux, 0, 2, 1}};  // (read at r3n_create only)  // (a multiple of R3N_SUBQ: whole blocks per sub-list)
+            {"bloom_tail", &t.bloom_tail, 0, 1u << 24, 1}, {"bloom_keep_down", &t.bloom_keep_down, 0, 1, 1}, {"equirect_tail", &equirect_tail, 0, equirect_rule::TAIL_CAP, 1}, {"prio_main", &t.prio_main, 0, 2, 1}, {"prio_shade", &t.prio_shade, 0, 2, 1}, {"prio_aux", &t.prio_aux, 0, 2, 1}};  // (read at r3n_create only)  // (a multiple of R3N_SUBQ: whole blocks per sub-list)
         bool known = false;
         for (auto &k : keys)
             if (key == k.name) {
@@ -844,6 +850,7 @@ int apply_tuning(r3n_ctx *c, const char *kv) {
         at = end == std::string::npos ? text.size() : end;
     }
     c->tune = t;
+    c->equirect_tail = equirect_tail;
     return R3N_OK;
 }
 
@@ -3361,6 +3368,204 @@ int r3n_texture_cubes_write_encoded(r3n_ctx *c, const r3n_texture_desc32 *descs,
         if (e != hipSuccess) return fail(c, R3N_ERR_HIP, what + ": " + hipGetErrorString(e));
         if (e2 != hipSuccess) return fail(c, R3N_ERR_HIP, what + ": " + hipGetErrorString(e2));
     }
+    c->cubes = std::move(cubes);
+    if (c->sky_cube > n) c->sky_cube = 0;
+    return R3N_OK;
+}
+
+extern "C" int r3n_internal_equirect_faces(const uint32_t *block, uint64_t o_first, uint64_t o_inst, uint32_t total_waves, const void *staged,
+                                           uint32_t *dense, const float *srgb_decode, hipStream_t stream);
+extern "C" int r3n_internal_equirect_level(const uint32_t *block, uint64_t o_first, uint64_t o_inst, uint32_t total_waves, uint32_t *dense,
+                                           hipStream_t stream);
+extern "C" int r3n_internal_equirect_tail(const uint32_t *recs, uint32_t n_recs, uint32_t *dense, hipStream_t stream);
+// kernels the last r3n_texture_cubes_write_sources enqueued: decode families, k_equirect_faces, the chain, k_cube_assemble
+extern "C" uint64_t r3n_internal_cube_source_launches(const r3n_ctx *c) { return c ? c->cube_source_launches : 0; }
+// with r3n_timing_enable, the phases of that call between device events, in ms (tools/equirect_cost.py)
+extern "C" int r3n_internal_cube_source_times(const r3n_ctx *c, float out[4]) {
+    if (!c || !out) return R3N_ERR_INVALID_ARG;
+    std::memcpy(out, c->cube_source_ms, sizeof c->cube_source_ms);
+    return R3N_OK;
+}
+
+// Cubes from stored faces (as r3n_texture_cubes_write_encoded) and from equirectangular panoramas, in one array.  A panorama is
+// resampled into dense level-0 faces (k_equirect_faces, one launch for the call), its chain is built face by face (equirect_rule.h:
+// the plan), and k_cube_assemble borders everything exactly as for stored faces.
+int r3n_texture_cubes_write_sources(r3n_ctx *c, const r3n_cube_source *sources, uint32_t n, const void *payload, uint64_t payload_bytes) {
+    const std::string what = "texture cubes write (sources)";
+    if (!c || (n && (!sources || !payload))) return fail(c, R3N_ERR_INVALID_ARG, what + ": null");
+    if (c->in_frame) return fail(c, R3N_ERR_STATE, what + ": inside a frame");
+    // ---- plan on the host; nothing changes before every cube has been accepted
+    struct Launch { size_t at; vertex_block::layout layout; uint64_t waves; };  // one wave-mapped table inside eq_block
+    std::vector<r3n_ctx::Cube> cubes(n);
+    std::vector<cube_faces::Record> recs;
+    std::vector<equirect::FaceRec> face_recs;
+    std::vector<std::vector<equirect::ChainRec>> level_recs;  // [k - 1]: level launch k
+    std::vector<equirect::ChainRec> tail_recs;
+    TextureWork work;
+    uint64_t pool_words = 0, dense_words = 0, asm_waves = 0;
+    const uint32_t T = c->equirect_tail;
+    for (uint32_t ci = 0; ci < n; ++ci) {
+        const r3n_cube_source &s = sources[ci];
+        if (s.kind != R3N_CUBE_SOURCE_CUBE && s.kind != R3N_CUBE_SOURCE_EQUIRECT) return fail(c, R3N_ERR_INVALID_ARG, what + ": unknown source kind");
+        const bool equi = s.kind == R3N_CUBE_SOURCE_EQUIRECT, rgbe = equi && s.format == R3N_CUBE_ENCODING_RGBE8;
+        if (!rgbe && s.format >= R3N_TEXTURE_FORMAT_COUNT) return fail(c, R3N_ERR_INVALID_ARG, what + ": unknown format id");
+        if (!s.width || !s.height || !s.face_extent) return fail(c, R3N_ERR_INVALID_ARG, what + ": zero extent");
+        if (s.width > equirect_rule::MAX_SOURCE_EXTENT || s.height > equirect_rule::MAX_SOURCE_EXTENT) return fail(c, R3N_ERR_INVALID_ARG, what + ": a source extent above 65535");
+        if (s.face_extent > equirect_rule::MAX_FACE_EXTENT) return fail(c, R3N_ERR_INVALID_ARG, what + ": a face extent above 16384");
+        if (!equi && (s.width != s.height || s.width != s.face_extent)) return fail(c, R3N_ERR_INVALID_ARG, what + ": a cube's faces are square, of the face extent");
+        const uint32_t N = s.face_extent;
+        if (!s.mips || s.mips > equirect_rule::max_mips(N)) return fail(c, R3N_ERR_INVALID_ARG, what + ": more mips than the extent has");
+        if ((s.offset & 3u) != 0u) return fail(c, R3N_ERR_INVALID_ARG, what + ": a source must start on a 4-byte boundary");
+        const uint32_t per_texel = equi || texture_jobs::is_float(s.format) ? 4u : 1u;
+        uint64_t source_bytes = 0, face_bytes = 0;
+        if (equi) {
+            source_bytes = rgbe ? (uint64_t)s.width * s.height * 4u : r3n_internal_level_bytes(s.format, s.width, s.height);
+        } else {
+            for (uint32_t k = 0; k < s.mips; ++k) face_bytes += r3n_internal_level_bytes(s.format, cube_faces::level_extent(N, k), cube_faces::level_extent(N, k));
+            source_bytes = 6u * face_bytes;
+        }
+        if (s.offset > payload_bytes || source_bytes > payload_bytes - s.offset) return fail(c, R3N_ERR_INVALID_ARG, what + ": data outside the payload");
+        const uint64_t words = cube_faces::cube_words(N, s.mips, per_texel);
+        if (pool_words + words > 0xFFFFFFFFull) return fail(c, R3N_ERR_CAPACITY, what + ": the cube pool exceeds 2^32 words");
+        const bool srgb = !equi && format_is_srgb(s.format);
+        cubes[ci] = {(size_t)pool_words, N, srgb ? 1u : 0u, s.mips, per_texel == 4u ? 2u : (srgb ? 1u : 0u)};
+        // an equirect source that is not RGBE is decoded by the 2D job tables into the scratch block, in front of the cube's faces
+        uint64_t decoded_at = 0;
+        uint32_t mode = equirect::SOURCE_RGBE8;
+        if (equi && !rgbe) {
+            const bool f32 = texture_jobs::is_float(s.format);
+            mode = f32 ? equirect::SOURCE_F32 : (format_is_srgb(s.format) ? equirect::SOURCE_RGBA8_SRGB : equirect::SOURCE_RGBA8);
+            decoded_at = dense_words;
+            dense_words += ((uint64_t)s.width * s.height * (f32 ? 4u : 1u) + 3u) & ~3ull;
+            if (dense_words > 0xFFFFFFFFull) return fail(c, R3N_ERR_CAPACITY, what + ": the scratch block exceeds 2^32 words");
+            texture_jobs::add_level(work.tables, s.format, s.width, s.height, s.offset, (uint32_t)decoded_at);
+        }
+        const uint32_t from = equi ? equirect_rule::tail_from(N, s.mips, T) : 0u;
+        uint64_t level_at = pool_words, above_at = 0;
+        for (uint32_t k = 0; k < s.mips; ++k) {
+            const uint32_t nk = cube_faces::level_extent(N, k);
+            const uint64_t stride = cube_faces::dense_face_words(nk, per_texel), units = (uint64_t)(nk + 2u) * (nk + 2u);
+            if (dense_words + 6u * stride > 0xFFFFFFFFull) return fail(c, R3N_ERR_CAPACITY, what + ": the scratch block exceeds 2^32 words");
+            for (uint32_t f = 0; f < 6u; ++f) {
+                if (!equi) {
+                    // LayerMajor: face f's levels lie back to back
+                    uint64_t src = s.offset + f * face_bytes;
+                    for (uint32_t l = 0; l < k; ++l) src += r3n_internal_level_bytes(s.format, cube_faces::level_extent(N, l), cube_faces::level_extent(N, l));
+                    texture_jobs::add_level(work.tables, s.format, nk, nk, src, (uint32_t)(dense_words + f * stride));
+                } else if (k == 0u) {
+                    equirect::FaceRec r{};
+                    r.n = N; r.face = f; r.mode = mode; r.W = s.width; r.H = s.height;
+                    r.src_lo = rgbe ? (uint32_t)s.offset : (uint32_t)decoded_at;
+                    r.src_hi = rgbe ? (uint32_t)(s.offset >> 32) : 0u;
+                    r.dst = (uint32_t)(dense_words + f * stride);
+                    r.units = N * N;
+                    face_recs.push_back(r);
+                } else if (k <= from) {
+                    const uint32_t sk = cube_faces::level_extent(N, k - 1u);
+                    if (level_recs.size() < k) level_recs.resize(k);
+                    level_recs[k - 1u].push_back(equirect::ChainRec{sk, nk, (uint32_t)(above_at + f * cube_faces::dense_face_words(sk, 4u)),
+                                                                    (uint32_t)(dense_words + f * stride), nk * nk, f, 1u, 0u});
+                } else if (k == from + 1u) {
+                    tail_recs.push_back(equirect::ChainRec{cube_faces::level_extent(N, from), nk, (uint32_t)above_at, (uint32_t)dense_words, 0u, f, s.mips - 1u - from, 0u});
+                }
+                recs.push_back(cube_faces::Record{nk, f, per_texel, (uint32_t)units, (uint32_t)dense_words, (uint32_t)stride,
+                                                  (uint32_t)(level_at + f * cube_faces::face_words(nk, per_texel)), 0u});
+                asm_waves += vertex_block::waves(units, cube_faces::UNITS_PER_WAVE);
+            }
+            above_at = dense_words;
+            dense_words += 6u * stride;
+            level_at += cube_faces::level_words(nk, per_texel);
+        }
+        pool_words += words;
+    }
+    if (!finish_texture_work(work) || asm_waves > vertex_block::MAX_WAVES)
+        return fail(c, R3N_ERR_CAPACITY, what + ": more than 2^31 wave slots of decode or assemble work in one call");
+    std::vector<uint32_t> asm_block;
+    const vertex_block::layout asm_layout = vertex_block::lay_out(asm_block, (uint32_t)recs.size(), cube_faces::REC_WORDS, asm_waves, [&](uint32_t i) {
+        return vertex_block::waves(recs[i].units, cube_faces::UNITS_PER_WAVE);
+    });
+    if (!recs.empty()) std::memcpy(asm_block.data(), recs.data(), recs.size() * sizeof(cube_faces::Record));
+    // the equirect tables as ONE block: faces | level 1 | level 2 | ... | tail records, each on a 16-word boundary
+    std::vector<uint32_t> eq_block;
+    std::vector<Launch> eq_launches;  // [0]: the faces, then the level launches
+    auto add_table = [&](const void *records, uint32_t count, size_t rec_words, auto units_of) {
+        uint64_t waves = 0;
+        for (uint32_t i = 0; i < count; ++i) waves += vertex_block::waves(units_of(i), equirect::UNITS_PER_WAVE);
+        if (waves > vertex_block::MAX_WAVES) return false;
+        std::vector<uint32_t> block;
+        const vertex_block::layout l = vertex_block::lay_out(block, count, rec_words, waves, [&](uint32_t i) { return vertex_block::waves(units_of(i), equirect::UNITS_PER_WAVE); });
+        std::memcpy(block.data(), records, (size_t)count * rec_words * 4u);
+        eq_launches.push_back(Launch{eq_block.size(), l, waves});
+        eq_block.insert(eq_block.end(), block.begin(), block.end());
+        eq_block.resize((eq_block.size() + 15u) & ~(size_t)15u, 0u);
+        return true;
+    };
+    bool fits = true;
+    if (!face_recs.empty()) {
+        fits = add_table(face_recs.data(), (uint32_t)face_recs.size(), equirect::FACE_REC_WORDS, [&](uint32_t i) { return (uint64_t)face_recs[i].units; });
+        for (size_t k = 0; k < level_recs.size() && fits; ++k)
+            fits = add_table(level_recs[k].data(), (uint32_t)level_recs[k].size(), equirect::CHAIN_REC_WORDS, [&](uint32_t i) { return (uint64_t)level_recs[k][i].units; });
+    }
+    if (!fits) return fail(c, R3N_ERR_CAPACITY, what + ": more than 2^31 wave slots of resampling work in one call");
+    const size_t tail_words_at = eq_block.size();
+    eq_block.resize(tail_words_at + tail_recs.size() * equirect::CHAIN_REC_WORDS, 0u);
+    if (!tail_recs.empty()) std::memcpy(eq_block.data() + tail_words_at, tail_recs.data(), tail_recs.size() * sizeof(equirect::ChainRec));
+    // ---- device side
+    HIP_TRY(c, hipSetDevice(c->device));
+    TRY(sync_all(c));  // no frame may still sample the old array
+    TRY(ensure(c, c->cube_texels, std::max<uint64_t>(pool_words, 1) * 4, false, -1));
+    uint64_t launches = 0;
+    if (n) {
+        // a block of the call's own, payload | job tables | assemble table | equirect tables | decoded sources and dense faces, freed
+        // before the call returns
+        const uint64_t jobs_at = (std::max<uint64_t>(payload_bytes, 4) + 255u) & ~255ull;
+        const uint64_t asm_at = (jobs_at + work.job_block.size() * 4u + 255u) & ~255ull;
+        const uint64_t eq_at = (asm_at + asm_block.size() * 4u + 255u) & ~255ull;
+        const uint64_t dense_at = (eq_at + eq_block.size() * 4u + 255u) & ~255ull;
+        DeviceBuffer scratch;
+        HIP_TRY(c, scratch.alloc(dense_at + std::max<uint64_t>(dense_words, 4) * 4u));
+        uint32_t *dense = reinterpret_cast<uint32_t *>(scratch.as<char>() + dense_at);
+        uint32_t *asm_dev = reinterpret_cast<uint32_t *>(scratch.as<char>() + asm_at);
+        uint32_t *eq_dev = reinterpret_cast<uint32_t *>(scratch.as<char>() + eq_at);
+        Event taps[5];  // phase boundaries, with r3n_timing_enable only
+        auto tap = [&](int k) {
+            if (c->timing && taps[k].create() == hipSuccess) (void)hipEventRecord(taps[k], c->stream);
+        };
+        tap(0);
+        hipError_t e = hipMemcpyAsync(asm_dev, asm_block.data(), asm_block.size() * 4u, hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess && !eq_block.empty()) e = hipMemcpyAsync(eq_dev, eq_block.data(), eq_block.size() * 4u, hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess)
+            e = enqueue_texture_work(c, work, payload, payload_bytes, c->stream, scratch.p, reinterpret_cast<uint32_t *>(scratch.as<char>() + jobs_at), launches, dense);
+        tap(1);
+        for (size_t i = 0; i < eq_launches.size() && e == hipSuccess; ++i) {
+            const Launch &l = eq_launches[i];
+            if (i == 1u) tap(2);
+            if (i == 0u)
+                e = (hipError_t)r3n_internal_equirect_faces(eq_dev + l.at, l.layout.o_first, l.layout.o_inst, (uint32_t)l.waves, scratch.p, dense, c->srgb8_decode.as<float>() + 256,  // (the table's sRGB half)
+                                                           c->stream);
+            else
+                e = (hipError_t)r3n_internal_equirect_level(eq_dev + l.at, l.layout.o_first, l.layout.o_inst, (uint32_t)l.waves, dense, c->stream);
+            ++launches;
+        }
+        if (eq_launches.size() <= 1u) tap(2);
+        if (e == hipSuccess && !tail_recs.empty()) {
+            e = (hipError_t)r3n_internal_equirect_tail(eq_dev + tail_words_at, (uint32_t)tail_recs.size(), dense, c->stream);
+            ++launches;
+        }
+        tap(3);
+        if (e == hipSuccess) {
+            e = (hipError_t)r3n_internal_cube_assemble(asm_dev, asm_layout.o_first, asm_layout.o_inst, (uint32_t)asm_waves, dense, c->cube_texels.as<uint32_t>(), c->stream);
+            ++launches;
+        }
+        tap(4);
+        const hipError_t e2 = hipStreamSynchronize(c->stream);  // the caller owns the sources only for the duration of the call
+        for (int k = 0; k < 4; ++k)
+            if (!c->timing || e != hipSuccess || e2 != hipSuccess || hipEventElapsedTime(&c->cube_source_ms[k], taps[k], taps[k + 1]) != hipSuccess) c->cube_source_ms[k] = 0.0f;
+        (void)scratch.reset();
+        if (e != hipSuccess) return fail(c, R3N_ERR_HIP, what + ": " + hipGetErrorString(e));
+        if (e2 != hipSuccess) return fail(c, R3N_ERR_HIP, what + ": " + hipGetErrorString(e2));
+    }
+    c->cube_source_launches = launches;
     c->cubes = std::move(cubes);
     if (c->sky_cube > n) c->sky_cube = 0;
     return R3N_OK;

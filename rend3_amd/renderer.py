@@ -1183,6 +1183,80 @@ class Renderer:
         self._cubes_dirty = True
         return len(self.cubes) - 1
 
+    def add_texture_cube_equirect(self, data, width, height, fmt="rgbe8", face_extent=None, mips="maximum"):
+        """A cube built on the GPU from ONE equirectangular (latitude / longitude) panorama of width x height texels: `data` = its
+        bytes (or a uint8 array), fmt = "rgbe8" (Radiance RGBE as containers.parse_hdr returns it: add_texture_cube_equirect(p["rgbe"],
+        p["width"], p["height"])) or an R3N_TEXTURE_* id (one level, as a 2D container stores it).  face_extent = the cube's N
+        (default max(1, height // 2)), mips = "maximum" or a level count in 1 .. floor(log2 N) + 1.  The cube holds f32 texels
+        whatever the source format.  The cube array is re-sent when the next frame is evaluated
+        (r3n_texture_cubes_write_sources).  Returns the cube handle."""
+        from . import containers
+        width, height = int(width), int(height)
+        if not (1 <= width <= 65535 and 1 <= height <= 65535):
+            raise ValueError("add_texture_cube_equirect: a panorama's sides are 1 .. 65535")
+        if isinstance(fmt, str):
+            if fmt != "rgbe8":
+                raise ValueError(f"add_texture_cube_equirect: unknown encoding {fmt!r}")
+            fmt, need = _ffi.CUBE_ENCODING_RGBE8, width * height * 4
+        else:
+            fmt = int(fmt)
+            if not 0 <= fmt < containers.FORMAT_COUNT:
+                raise ValueError(f"add_texture_cube_equirect: unknown format id {fmt}")
+            need = containers.level_bytes(fmt, width, height)
+        n = max(1, height // 2) if face_extent is None else int(face_extent)
+        if not 1 <= n <= 16384:
+            raise ValueError("add_texture_cube_equirect: a cube's extent is 1 .. 16384")
+        mips = n.bit_length() if mips == "maximum" else int(mips)
+        if not 1 <= mips <= n.bit_length():
+            raise ValueError(f"add_texture_cube_equirect: {mips} levels, an extent of {n} has 1 .. {n.bit_length()}")
+        data = data.tobytes() if isinstance(data, np.ndarray) else bytes(data)
+        if len(data) != need:
+            raise ValueError(f"add_texture_cube_equirect: {len(data)} bytes, a {width} x {height} panorama of this format has {need}")
+        self.cubes.append(_EquirectCube(fmt, width, height, data, n, mips))
+        self._cubes_dirty = True
+        return len(self.cubes) - 1
+
+    def environment_mean(self, cube):
+        """The mean colour of a cube: the mean of the six 1 x 1 faces of its LAST level (r3n_readback_cube_face), which a cube with a
+        full chain has box-filtered down from every texel.  It weighs every texel of a face alike: the box-filtered mean, NOT a
+        solid-angle integral (texels near a face's corners cover less of the sphere).  Needs a cube whose last level is 1 x 1."""
+        self._flush_cubes()
+        if not 0 <= cube < len(self.cubes):
+            raise ValueError("environment_mean: no such cube")
+        c = self.cubes[cube]
+        width, mips = (c.width, c.mips) if isinstance(c, (_EncodedCube, _EquirectCube)) else (c[0].shape[1], 1)
+        if max(1, width >> (mips - 1)) != 1:
+            raise ValueError("environment_mean: the cube's last level is not 1 x 1")
+        faces = [self.readback_cube_face(cube, mips - 1, f) for f in range(6)]
+        if faces[0].dtype != np.float32:
+            raise ValueError("environment_mean: a cube of float texels (an HDR environment)")
+        total = np.zeros(4, dtype=np.float32)
+        for f in faces:
+            total = total + f[1, 1]
+        return total / np.float32(6.0)
+
+    def _flush_cubes_sources(self):
+        """the whole array through r3n_texture_cubes_write_sources: stored cubes LayerMajor, panoramas as one level"""
+        src = (_ffi.CubeSource * max(len(self.cubes), 1))()
+        payload = bytearray()
+        for i, cube in enumerate(self.cubes):
+            payload += bytes(-len(payload) % 4)
+            if isinstance(cube, _EquirectCube):
+                src[i] = _ffi.CubeSource(_ffi.CUBE_SOURCE_EQUIRECT, cube.fmt, cube.src_width, cube.src_height, cube.width, cube.mips, len(payload))
+                payload += cube.data
+            elif isinstance(cube, _EncodedCube):
+                src[i] = _ffi.CubeSource(_ffi.CUBE_SOURCE_CUBE, cube.fmt, cube.width, cube.width, cube.width, cube.mips, len(payload))
+                for levels in cube.faces:
+                    for level in levels:
+                        payload += level
+            else:
+                faces, srgb = cube
+                src[i] = _ffi.CubeSource(_ffi.CUBE_SOURCE_CUBE, 1 if srgb else 0, faces.shape[2], faces.shape[1], faces.shape[1], 1, len(payload))
+                payload += faces.tobytes()
+        data = np.frombuffer(bytes(payload) + bytes(4), dtype=np.uint8)
+        self._check(self.lib.r3n_texture_cubes_write_sources(self.ctx, ctypes.addressof(src), len(self.cubes), _ffi.ptr(data), len(payload)),
+                    "r3n_texture_cubes_write_sources")
+
     def replace_texture_cubes(self, cubes):
         """Replaces the whole cube array: `cubes` = [(faces, srgb), ...]; handles are indices into it."""
         self.cubes = []
@@ -1216,6 +1290,10 @@ class Renderer:
                     "r3n_texture_cubes_write_encoded")
 
     def _flush_cubes(self):
+        if self._cubes_dirty and any(isinstance(cube, _EquirectCube) for cube in self.cubes):
+            self._flush_cubes_sources()
+            self._cubes_dirty = False
+            self._background_sent = None
         if self._cubes_dirty and any(isinstance(cube, _EncodedCube) for cube in self.cubes):
             self._flush_cubes_encoded()
             self._cubes_dirty = False
@@ -1841,7 +1919,7 @@ class Renderer:
         if not 0 <= cube < len(self.cubes):
             raise ValueError("readback_cube_face: no such cube")
         c = self.cubes[cube]
-        width = c.width if isinstance(c, _EncodedCube) else c[0].shape[1]
+        width = c.width if isinstance(c, (_EncodedCube, _EquirectCube)) else c[0].shape[1]
         p = max(1, width >> level) + 2
         words = np.zeros(p * p * 4, dtype=np.uint32)
         cls = np.zeros(1, dtype=np.uint32)
@@ -2048,6 +2126,13 @@ class _EncodedCube:
 
     def __init__(self, fmt, width, mips, faces):
         self.fmt, self.width, self.mips, self.faces = fmt, width, mips, faces
+
+
+class _EquirectCube:
+    """a cube of add_texture_cube_equirect: one panorama of src_width x src_height texels, built into `width`^2 faces on the GPU"""
+
+    def __init__(self, fmt, src_width, src_height, data, width, mips):
+        self.fmt, self.src_width, self.src_height, self.data, self.width, self.mips = fmt, src_width, src_height, data, width, mips
 
 
 class SkyboxRoutine:

@@ -81,7 +81,14 @@ def add_arguments(ap):
     ap.add_argument("--skybox", default=None, metavar="PATH",
                     help="the background cube (default: none): a directory holding right|left|top|bottom|front|back .jpg or .png, "
                          "or a .ktx2 / .dds cube map in any supported format with its mip chain (not in the reference, whose "
-                         "example loads the six images)")
+                         "example loads the six images), or a Radiance .hdr equirectangular panorama, turned into a cube on the GPU")
+    ap.add_argument("--skybox-extent", type=int, default=None, metavar="N",
+                    help="with a panorama: the extent of the cube's faces (default: half the panorama's height)")
+    ap.add_argument("--skybox-equirect", default=None, metavar="FILE",
+                    help="the background cube from a 2D .ktx2 / .dds file that holds an equirectangular panorama (its first level)")
+    ap.add_argument("--ambient-from-skybox", type=float, default=None, metavar="SCALE",
+                    help="ambient colour = SCALE x the mean colour of the panorama's cube (the box-filtered mean of its texels, not a "
+                         "solid-angle integral) instead of --ambient")
     ap.add_argument("--blend-sort", choices=("host", "gpu"), default="host",
                     help="where the transparent pass's back-to-front order is sorted (not in the reference, whose CPU batcher sorts): "
                          "host = every frame on the CPU, gpu = r3n_blend_sort")
@@ -140,6 +147,8 @@ def settings_from(args):
                 ambient=args.ambient, scale=args.scale, shadow_distance=args.shadow_distance,
                 shadow_resolution=args.shadow_resolution, enable_directional=not args.gltf_disable_directional_lights,
                 camera=args.camera or DEFAULT_CAMERA, skybox=getattr(args, "skybox", None),
+                skybox_extent=getattr(args, "skybox_extent", None), skybox_equirect=getattr(args, "skybox_equirect", None),
+                ambient_from_skybox=getattr(args, "ambient_from_skybox", None),
                 blend_sort=getattr(args, "blend_sort", "host"), morph_normals=getattr(args, "morph_normals", "base"),
                 build_tangents=getattr(args, "build_tangents", False), morph_tangents=getattr(args, "morph_tangents", "base"),
                 texture_upload=getattr(args, "texture_upload", "whole"), texture_compact=getattr(args, "texture_compact", None),
@@ -193,9 +202,32 @@ def load_skybox_file(path):
     return cube
 
 
-def add_skybox(r, path):
-    """binds the cube of --skybox PATH: a directory of six images, or a cube-map file"""
-    if os.path.isdir(path):
+def load_panorama(path, container=False):
+    """An equirectangular panorama -> (data, width, height, fmt) for Renderer.add_texture_cube_equirect: a Radiance .hdr file, or
+    (container=True) the first level of a 2D .ktx2 / .dds file, linear (an HDR environment is not sRGB-encoded)."""
+    from . import containers
+    with open(path, "rb") as f:
+        data = f.read()
+    if not container:
+        p = containers.parse_hdr(data)
+        if p is None:
+            raise ValueError(f"skybox: {path} is not a Radiance .hdr file")
+        return p["rgbe"], p["width"], p["height"], "rgbe8"
+    t = containers.parse_ktx2(data, False) or containers.parse_dds(data, False)
+    if t is None:
+        raise ValueError(f"skybox: {path} is neither a KTX2 nor a DDS file")
+    return t["levels"][0], t["width"], t["height"], t["format"]
+
+
+def add_skybox(r, path, extent=None, equirect=False):
+    """binds the cube of --skybox PATH: a directory of six images, a cube-map file, or (a .hdr file, or equirect=True: --skybox-equirect)
+    a panorama"""
+    if equirect or (not os.path.isdir(path) and path.lower().endswith(".hdr")):
+        if not hasattr(r, "add_texture_cube_equirect"):  # (a renderer that cannot build the cube fails here)
+            raise ValueError("--skybox with a panorama: this renderer takes stored cube faces only")
+        data, w, h, fmt = load_panorama(path, container=equirect)
+        handle = r.add_texture_cube_equirect(data, w, h, fmt=fmt, face_extent=extent)
+    elif os.path.isdir(path):
         handle = r.add_texture_cube(load_skybox(path), srgb=True)
     else:
         cube = load_skybox_file(path)
@@ -215,8 +247,15 @@ def build(r, hm, mk, settings):
     objects, triangles)."""
     from . import gltf
     assert r.handedness == RIGHT, "scene_viewer is right-handed (App::HANDEDNESS, mod.rs:434)"
+    if settings.get("skybox") and settings.get("skybox_equirect"):
+        raise ValueError("--skybox and --skybox-equirect: one background")
+    sky = None
     if settings.get("skybox"):  # load_skybox (mod.rs:34-57); a renderer without cube textures fails here, it does not skip the sky
-        add_skybox(r, settings["skybox"])
+        sky = add_skybox(r, settings["skybox"], extent=settings.get("skybox_extent"))
+    elif settings.get("skybox_equirect"):
+        sky = add_skybox(r, settings["skybox_equirect"], extent=settings.get("skybox_extent"), equirect=True)
+    if settings.get("ambient_from_skybox") is not None and (sky is None or not hasattr(r, "environment_mean")):
+        raise ValueError("--ambient-from-skybox needs a skybox on a renderer that can read its mean")
     if settings.get("tonemap", "blit") != "blit" or settings.get("exposure", 0.0) != 0.0 or settings.get("auto_exposure"):
         if not hasattr(r, "set_tonemapping"):  # (a renderer that only has the reference's blit fails here)
             raise ValueError("--tonemap / --exposure / --auto-exposure: this renderer has the blit alone")
@@ -273,7 +312,11 @@ def build(r, hm, mk, settings):
     view = camera_view(hm, settings["camera"])
     r.set_camera_data(view, PROJECTION)
     a = settings["ambient"]
+    ambient = (a, a, a, 1.0)
+    if settings.get("ambient_from_skybox") is not None:
+        mean = r.environment_mean(sky)
+        ambient = tuple(float(settings["ambient_from_skybox"]) * float(v) for v in mean[:3]) + (1.0,)
     meshes = r.meshes
     tris = int(sum(meshes[m["mesh"]].index_count // 3 for m in r.object_meta.values() if m["enabled"]))
-    return dict(instance=inst, gltf=g, light=light, camera=(view, PROJECTION), ambient=(a, a, a, 1.0), clear=CLEAR,
+    return dict(instance=inst, gltf=g, light=light, camera=(view, PROJECTION), ambient=ambient, clear=CLEAR,
                 samples=settings["samples"], objects=len(inst["objects"]), triangles=tris, file=os.path.basename(settings["file"]))
