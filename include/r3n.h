@@ -530,6 +530,10 @@ int r3n_sample_probe(r3n_ctx *ctx, uint32_t form, const r3n_sample_query40 *quer
  *      uploads as right, left, top, bottom, front, back).  width != height, width == 0 or > 16384, faces outside `texels`
  *      -> R3N_ERR_INVALID_ARG; formats other than R3N_TEXTURE_RGBA8_UNORM / _SRGB, or mips != 1 -> R3N_ERR_UNSUPPORTED (a cube's mip
  *      level would follow from the derivatives of the direction; scene_viewer uploads MipmapCount::ONE).  stored_mips is ignored.
+ *      An array whose pool of bordered faces would pass 2^32 words -> R3N_ERR_CAPACITY; every refusal comes before anything changes.
+ *      The call is r3n_texture_cubes_write_encoded of the same cubes as one-level RGBA8 faces, `texels` being the payload: the
+ *      device expands the faces and k_cube_assemble builds their borders, as for every entry (csrc/skybox.h), in a scratch block
+ *      that is freed before the call returns.
  *      Synchronises.  A skybox bound to a cube that no longer exists (r3n_skybox_set) is unbound. */
 int r3n_texture_cubes_write(r3n_ctx *ctx, const r3n_texture_desc32 *descs, uint32_t n_cubes, const uint32_t *texels,
                             uint64_t n_texels);

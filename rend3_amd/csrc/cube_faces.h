@@ -1,11 +1,13 @@
 // cube_faces.h -- the bordered faces of the cube-texture pool (skybox.h): which texel a border position holds, where a level of a
-// cube lies in the pool, and the table of the launch that assembles the faces (cube_faces.hip, r3n_texture_cubes_write_encoded).
-// Plain C++17, no HIP, no context, shared by host and kernel: tests/cube_faces_check.cpp compiles it alone.
+// cube lies in the pool, and the table of the launch that assembles the faces of every cube upload (cube_faces.hip; cube_plan.h
+// fills the table for r3n_texture_cubes_write, _encoded and _sources alike).  Plain C++17, no HIP, no context, shared by host and
+// kernel: tests/cube_faces_check.cpp compiles it alone.
 //
 // A face of extent n is stored WITH A ONE-TEXEL BORDER: (n + 2) x (n + 2) texels, row-major, interior texel (i, j) at bordered
 // position (i + 1, j + 1).  A border position of an edge holds the adjacent face's texel across that edge, OF THE SAME LEVEL: the
 // texel the centre of the missing texel, extended on the face's plane and re-projected, falls into (tests/skybox_reference.py
-// resolve_texel finds it geometrically; the table below is that function's result, checked against it for every n the tests name).
+// resolve_texel finds it geometrically; the table below is that function's result, checked against it for every n the tests name,
+// and the library's only statement of the rule: no entry builds a border on the host).
 // The four corner positions have no texel: they are written as zero and never read (the sampler forms a corner from three texels).
 //
 // Pool layout of ONE cube of extent N with `mips` levels, in words (per_texel = 1: an RGBA8 word, 4: four f32):

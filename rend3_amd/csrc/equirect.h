@@ -1,8 +1,9 @@
 // equirect.h -- the records of the launches that build cubes from equirectangular panoramas (equirect.hip,
-// r3n_texture_cubes_write_sources).  The rule and the launch plan: equirect_rule.h.  Plain C++17, no HIP, no context.
+// r3n_texture_cubes_write_sources).  The rule and the launch plan: equirect_rule.h; cube_plan.h fills the records.  Plain C++17, no
+// HIP, no context.
 //
 // Everything is indexed in 32-bit words of the call's scratch block ("dense": decoded sources, then the dense faces of every level,
-// laid out as r3n_texture_cubes_write_encoded lays them out: a level's six faces back to back, n * n * 4 words each), except an
+// laid out as cube_plan.h lays them out for every entry: a level's six faces back to back, n * n * 4 words each), except an
 // RGBE8 source, which is read where it lies in the staged payload (a 64-bit byte offset).
 #pragma once
 #include <stdint.h>

@@ -25,6 +25,7 @@
 #include "kernels_shade.h"
 #include "skybox.h"
 #include "cube_faces.h"
+#include "cube_plan.h"
 #include "blend_sort.h"
 #include "mesh_reloc.h"
 #include "morph.h"
@@ -287,7 +288,7 @@ struct r3n_ctx {
     Event mesh_reloc_ev[2];  // around the relocation kernel (r3n_mesh_compact_result::relocate_ns)
     // cube textures + the skybox node (skybox.h): the bordered faces of every cube, where each cube starts, which one is bound
     // (cls: 0 Rgba8Unorm words, 1 Rgba8UnormSrgb words, 2 four f32 per texel; the levels lie as cube_faces.h lays them out)
-    struct Cube { size_t first_word; uint32_t n, srgb, mips = 1, cls = 0; };
+    using Cube = cube_plan::Cube;
     DeviceBuffer cube_texels;
     std::vector<Cube> cubes;
     uint32_t sky_cube = 0;            // r3n_skybox_set: 0 = none, i + 1 = cubes[i]
@@ -1292,8 +1293,6 @@ extern "C" int r3n_internal_skinning_mfma(uint32_t *mesh, const void *inputs, co
                                           const uint32_t *wave_first, const uint32_t *skeleton_joints, uint32_t total_waves, hipStream_t stream);
 extern "C" int r3n_internal_generate_mip(uint32_t srgb, uint32_t sw, uint32_t sh, uint32_t dw, uint32_t dh, const uint32_t *src,
                                          uint32_t *dst, const float *decode, const float *thr, hipStream_t stream);
-extern "C" uint64_t r3n_internal_level_bytes(uint32_t format, uint32_t w, uint32_t h);
-extern "C" int r3n_internal_format_is_float(uint32_t format);
 extern "C" uint32_t r3n_internal_format_align(uint32_t format);
 extern "C" int r3n_internal_format_generates_mips_f32(uint32_t format);
 extern "C" int r3n_internal_generate_mip_f32(uint32_t format, uint32_t sw, uint32_t sh, uint32_t dw, uint32_t dh, const float *src, float *dst,
@@ -1301,17 +1300,12 @@ extern "C" int r3n_internal_generate_mip_f32(uint32_t format, uint32_t sw, uint3
 extern "C" int r3n_internal_decode_jobs(uint32_t family, const uint32_t *block, uint64_t o_first, uint64_t o_inst, uint32_t total_waves,
                                         const void *staged, uint32_t *pool, hipStream_t stream);
 
-// the RGBA8-decoded formats whose pool words are sRGB-encoded
-static bool format_is_srgb(uint32_t format) {
-    return format == R3N_TEXTURE_RGBA8_UNORM_SRGB || format == R3N_TEXTURE_BGRA8_UNORM_SRGB || format == R3N_TEXTURE_BC1_RGBA_UNORM_SRGB ||
-           format == R3N_TEXTURE_BC2_RGBA_UNORM_SRGB || format == R3N_TEXTURE_BC3_RGBA_UNORM_SRGB || format == R3N_TEXTURE_BC7_RGBA_UNORM_SRGB;
-}
 // One descriptor of r3n_textures_write_encoded / r3n_textures_update (`what` names the call in the message): validates it against
 // the payload and gives the descriptor the device holds (pool format class, offset still to be placed) and its pool words.
 static int check_encoded_desc(r3n_ctx *c, const std::string &what, const r3n_texture_desc32 &d, uint64_t payload_bytes, r3n_texture_desc32 &internal,
                               uint64_t &words) {
     if (d.format >= R3N_TEXTURE_FORMAT_COUNT) return fail(c, R3N_ERR_UNSUPPORTED, what + ": unknown format id");
-    const bool is_float = r3n_internal_format_is_float(d.format) != 0;
+    const bool is_float = texture_jobs::is_float(d.format);
     TRY(check_chain(c, what, d));
     if (d.stored_mips > d.mips) return fail(c, R3N_ERR_INVALID_ARG, what + ": more stored levels than mips");
     const uint32_t stored = d.stored_mips ? d.stored_mips : d.mips;
@@ -1321,12 +1315,12 @@ static int check_encoded_desc(r3n_ctx *c, const std::string &what, const r3n_tex
     uint64_t end = d.offset;
     for (uint32_t k = 0; k < stored; ++k) {
         const texture_jobs::Level l = texture_jobs::level_of(d.width, d.height, k, 1u);
-        end += r3n_internal_level_bytes(d.format, l.w, l.h);
+        end += texture_jobs::level_bytes(d.format, l.w, l.h);
     }
     words = texture_jobs::chain_words(d.width, d.height, d.mips, is_float ? 4u : 1u);
     if (end > payload_bytes) return fail(c, R3N_ERR_INVALID_ARG, what + ": levels outside the payload");
     if ((d.offset & 3u) != 0u) return fail(c, R3N_ERR_INVALID_ARG, what + ": level 0 must start on a 4-byte boundary");
-    const bool srgb = format_is_srgb(d.format);
+    const bool srgb = texture_jobs::is_srgb(d.format);
     internal = d;
     internal.stored_mips = 0;
     internal.format = is_float ? R3N_POOL_FLOAT : (srgb ? R3N_TEXTURE_RGBA8_UNORM_SRGB : R3N_TEXTURE_RGBA8_UNORM);
@@ -1342,26 +1336,11 @@ struct GeneratedLevel {
     uint32_t sw, sh, w, h;
     uint64_t src, dst;
 };
-// one job record per stored level, per kernel family (texture_jobs.h), the four tables as ONE block with every table on an 8-word
-// boundary; the generated levels in launch order
-struct TextureWork {
-    texture_jobs::Table tables[texture_jobs::FAMILIES];
-    size_t job_at[texture_jobs::FAMILIES];
-    std::vector<uint32_t> job_block;
+// one job record per stored level, per kernel family, the four tables as ONE block (texture_jobs::Work); the generated levels in
+// launch order
+struct TextureWork : texture_jobs::Work {
     std::vector<GeneratedLevel> generated;
 };
-// lays the filled tables out as the ONE block: false when a family has more wave slots than its kernel counts
-static bool finish_texture_work(TextureWork &work) {
-    if (!texture_jobs::finish(work.tables)) return false;
-    size_t words = 0;
-    for (int f = 0; f < texture_jobs::FAMILIES; ++f) {
-        work.job_at[f] = words;
-        words += (work.tables[f].block.size() + 7u) & ~(size_t)7u;
-    }
-    work.job_block.assign(std::max<size_t>(words, 1), 0u);
-    for (int f = 0; f < texture_jobs::FAMILIES; ++f) std::copy(work.tables[f].block.begin(), work.tables[f].block.end(), work.job_block.begin() + work.job_at[f]);
-    return true;
-}
 // descs: the caller's (source format, byte offset in the payload); internal: what the device holds, placed.  false: a family has
 // more wave slots than its kernel counts.
 static bool plan_texture_work(const r3n_texture_desc32 *descs, const r3n_texture_desc32 *internal, uint32_t n, TextureWork &work) {
@@ -1374,7 +1353,7 @@ static bool plan_texture_work(const r3n_texture_desc32 *descs, const r3n_texture
             const texture_jobs::Level l = texture_jobs::level_of(d.width, d.height, k, words_per_texel(internal[i]));
             if (k < stored) {
                 texture_jobs::add_level(work.tables, d.format, l.w, l.h, src, (uint32_t)dst);
-                src += r3n_internal_level_bytes(d.format, l.w, l.h);
+                src += texture_jobs::level_bytes(d.format, l.w, l.h);
             } else {
                 work.generated.push_back(GeneratedLevel{d.format, internal[i].format, above.w, above.h, l.w, l.h, dst - above.words, dst});
             }
@@ -1382,14 +1361,13 @@ static bool plan_texture_work(const r3n_texture_desc32 *descs, const r3n_texture
             above = l;
         }
     }
-    return finish_texture_work(work);
+    return texture_jobs::finish_work(work);
 }
 // Copy, decode: the payload once into `stage`, the tables into `job_dev` (the caller's blocks: payload_bytes, job_block.size() words
-// on a 32-byte boundary), at most four launches for every stored level of the call, the generated levels level by level behind
-// them.  Only enqueues, counting its kernels into `launches`; `payload` and `work` must outlive the caller's wait for `stream`.
-static hipError_t enqueue_texture_work(r3n_ctx *c, const TextureWork &work, const void *payload, uint64_t payload_bytes, hipStream_t stream, void *stage,
-                                       uint32_t *job_dev, uint64_t &launches, uint32_t *into = nullptr) {
-    uint32_t *pool = into ? into : c->tex_texels.as<uint32_t>();  // (into: the cube path decodes into a block of its own)
+// on a 32-byte boundary), at most four launches for every stored level of the call, writing words of `pool`.  Only enqueues,
+// counting its kernels into `launches`; `payload` and `work` must outlive the caller's wait for `stream`.
+static hipError_t enqueue_decode_jobs(const texture_jobs::Work &work, const void *payload, uint64_t payload_bytes, hipStream_t stream, void *stage,
+                                      uint32_t *job_dev, uint64_t &launches, uint32_t *pool) {
     hipError_t e = hipMemcpyAsync(stage, payload, payload_bytes, hipMemcpyHostToDevice, stream);
     if (e == hipSuccess) e = hipMemcpyAsync(job_dev, work.job_block.data(), work.job_block.size() * 4u, hipMemcpyHostToDevice, stream);
     for (int f = 0; f < texture_jobs::FAMILIES && e == hipSuccess; ++f) {
@@ -1398,6 +1376,13 @@ static hipError_t enqueue_texture_work(r3n_ctx *c, const TextureWork &work, cons
         e = (hipError_t)r3n_internal_decode_jobs((uint32_t)f, job_dev + work.job_at[f], t.layout.o_first, t.layout.o_inst, (uint32_t)t.total_waves, stage, pool, stream);
         ++launches;
     }
+    return e;
+}
+// the same into the texel pool, and the generated levels level by level behind the stored ones
+static hipError_t enqueue_texture_work(r3n_ctx *c, const TextureWork &work, const void *payload, uint64_t payload_bytes, hipStream_t stream, void *stage,
+                                       uint32_t *job_dev, uint64_t &launches) {
+    uint32_t *pool = c->tex_texels.as<uint32_t>();
+    hipError_t e = enqueue_decode_jobs(work, payload, payload_bytes, stream, stage, job_dev, launches, pool);
     for (size_t i = 0; i < work.generated.size() && e == hipSuccess; ++i) {
         const GeneratedLevel &g = work.generated[i];
         if (g.pool_format == R3N_POOL_FLOAT) {
@@ -3218,167 +3203,16 @@ int r3n_resolve_opaque(r3n_ctx *c) {
 }
 
 // ------------------------------------------------------------------------------------------------ cube textures + skybox node
-namespace {
-// The direction through the point (sc, tc) of face `f`'s plane (|sc|, |tc| may pass 1: a point beyond the face's edge), and back:
-// the face and texel a direction selects.  The Vulkan / WebGPU cube table of skybox.hip, in double: used once per border texel
-// at upload, where the adjacent face's texel across an edge is found by re-projecting the texel centre extended on the face's plane.
-void cube_face_point(uint32_t f, double sc, double tc, double d[3]) {
-    switch (f) {
-        case 0: d[0] = 1.0; d[1] = -tc; d[2] = -sc; break;   // +X: (sc, tc) = (-z, -y)
-        case 1: d[0] = -1.0; d[1] = -tc; d[2] = sc; break;   // -X: (z, -y)
-        case 2: d[0] = sc; d[1] = 1.0; d[2] = tc; break;     // +Y: (x, z)
-        case 3: d[0] = sc; d[1] = -1.0; d[2] = -tc; break;   // -Y: (x, -z)
-        case 4: d[0] = sc; d[1] = -tc; d[2] = 1.0; break;    // +Z: (x, -y)
-        default: d[0] = -sc; d[1] = -tc; d[2] = -1.0; break; // -Z: (-x, -y)
-    }
-}
-void cube_nearest_texel(const double d[3], uint32_t n, uint32_t &f, uint32_t &i, uint32_t &j) {
-    const double ax = std::fabs(d[0]), ay = std::fabs(d[1]), az = std::fabs(d[2]);
-    double sc, tc, ma;
-    if (az >= ax && az >= ay) { f = d[2] < 0.0 ? 5u : 4u; sc = d[2] < 0.0 ? -d[0] : d[0]; tc = -d[1]; ma = az; }
-    else if (ay >= ax) { f = d[1] < 0.0 ? 3u : 2u; sc = d[0]; tc = d[1] < 0.0 ? -d[2] : d[2]; ma = ay; }
-    else { f = d[0] < 0.0 ? 1u : 0u; sc = d[0] < 0.0 ? d[2] : -d[2]; tc = -d[1]; ma = ax; }
-    const double s = 0.5 * (sc / ma) + 0.5, t = 0.5 * (tc / ma) + 0.5;
-    i = (uint32_t)std::min<double>(std::max(std::floor(s * n), 0.0), (double)n - 1.0);
-    j = (uint32_t)std::min<double>(std::max(std::floor(t * n), 0.0), (double)n - 1.0);
-}
-}  // namespace
-
-int r3n_texture_cubes_write(r3n_ctx *c, const r3n_texture_desc32 *descs, uint32_t n, const uint32_t *texels, uint64_t n_texels) {
-    if (!c || (n && (!descs || !texels))) return fail(c, R3N_ERR_INVALID_ARG, "texture cubes write: null");
-    if (c->in_frame) return fail(c, R3N_ERR_STATE, "texture cubes write: inside a frame");
-    size_t words = 0;
-    for (uint32_t i = 0; i < n; ++i) {
-        const r3n_texture_desc32 &d = descs[i];
-        if (d.width != d.height) return fail(c, R3N_ERR_INVALID_ARG, "texture cubes write: a cube's faces are square");
-        if (!d.width || d.width > 16384u) return fail(c, R3N_ERR_INVALID_ARG, "texture cubes write: bad extent");
-        if (d.format > R3N_TEXTURE_RGBA8_UNORM_SRGB) return fail(c, R3N_ERR_UNSUPPORTED, "texture cubes write: Rgba8Unorm / Rgba8UnormSrgb cubes only");
-        if (d.mips != 1u) return fail(c, R3N_ERR_UNSUPPORTED, "texture cubes write: single-level cubes only (no level selection from cube-direction derivatives)");
-        if ((uint64_t)d.offset + 6ull * d.width * d.width > n_texels) return fail(c, R3N_ERR_INVALID_ARG, "texture cubes write: faces outside the texel array");
-        words += 6u * (size_t)(d.width + 2u) * (d.width + 2u);
-    }
-    HIP_TRY(c, hipSetDevice(c->device));
-    TRY(sync_all(c));  // no frame may still sample the old array
-    std::vector<uint32_t> pool(std::max<size_t>(words, 1), 0u);
-    std::vector<r3n_ctx::Cube> cubes(n);
-    size_t at = 0;
-    for (uint32_t ci = 0; ci < n; ++ci) {
-        const uint32_t N = descs[ci].width, P = N + 2u;
-        const uint32_t *src = texels + descs[ci].offset;
-        cubes[ci] = {at, N, descs[ci].format == R3N_TEXTURE_RGBA8_UNORM_SRGB ? 1u : 0u, 1u, descs[ci].format == R3N_TEXTURE_RGBA8_UNORM_SRGB ? 1u : 0u};
-        for (uint32_t f = 0; f < 6u; ++f) {
-            uint32_t *dst = pool.data() + at + (size_t)f * P * P;
-            for (uint32_t j = 0; j < N; ++j) std::memcpy(dst + (size_t)(j + 1u) * P + 1u, src + ((size_t)f * N + j) * N, (size_t)N * 4);
-            // the border: texel centre (i + 0.5, j + 0.5) one step outside the face, extended on the face's plane
-            auto border = [&](int i, int j) {
-                double d[3];
-                cube_face_point(f, (2.0 * (i + 0.5)) / N - 1.0, (2.0 * (j + 0.5)) / N - 1.0, d);
-                uint32_t nf, ni, nj;
-                cube_nearest_texel(d, N, nf, ni, nj);
-                dst[(size_t)(j + 1) * P + (size_t)(i + 1)] = src[((size_t)nf * N + nj) * N + ni];
-            };
-            for (int k = 0; k < (int)N; ++k) { border(-1, k); border((int)N, k); border(k, -1); border(k, (int)N); }
-        }
-        at += 6u * (size_t)P * P;
-    }
-    TRY(ensure(c, c->cube_texels, pool.size() * 4, false, -1));
-    HIP_TRY(c, hipMemcpyAsync(c->cube_texels.p, pool.data(), pool.size() * 4, hipMemcpyHostToDevice, c->stream));
-    HIP_WAIT(c, hipStreamSynchronize(c->stream));  // `pool` is a temporary
-    c->cubes = std::move(cubes);
-    if (c->sky_cube > n) c->sky_cube = 0;
-    return R3N_OK;
-}
-
+// The three upload entries are adapters over ONE plan (cube_plan.h: the refusals, the pool and scratch layout, every table) and ONE
+// execution (write_cube_plan below).
 extern "C" int r3n_internal_cube_assemble(const uint32_t *block, uint64_t o_first, uint64_t o_inst, uint32_t total_waves, const uint32_t *dense,
                                           uint32_t *pool, hipStream_t stream);
-
-// Cubes of any format with their stored chains.  Every (cube, face, level) is one decode job into a DENSE face of the call's scratch
-// block (at most four launches, the 2D path's kernels); k_cube_assemble then builds every bordered face of the call in one launch.
-int r3n_texture_cubes_write_encoded(r3n_ctx *c, const r3n_texture_desc32 *descs, uint32_t n, const void *payload, uint64_t payload_bytes) {
-    const std::string what = "texture cubes write (encoded)";
-    if (!c || (n && (!descs || !payload))) return fail(c, R3N_ERR_INVALID_ARG, what + ": null");
-    if (c->in_frame) return fail(c, R3N_ERR_STATE, what + ": inside a frame");
-    // ---- plan on the host; nothing changes before every cube has been accepted
-    std::vector<r3n_ctx::Cube> cubes(n);
-    std::vector<cube_faces::Record> recs;
-    TextureWork work;
-    uint64_t pool_words = 0, dense_words = 0, asm_waves = 0;
-    for (uint32_t ci = 0; ci < n; ++ci) {
-        const r3n_texture_desc32 &d = descs[ci];
-        if (d.format >= R3N_TEXTURE_FORMAT_COUNT) return fail(c, R3N_ERR_INVALID_ARG, what + ": unknown format id");
-        if (d.width != d.height) return fail(c, R3N_ERR_INVALID_ARG, what + ": a cube's faces are square");
-        if (!d.width || d.width > 16384u) return fail(c, R3N_ERR_INVALID_ARG, what + ": bad extent");
-        TRY(check_chain(c, what, d));
-        if (d.stored_mips && d.stored_mips != d.mips)
-            return fail(c, R3N_ERR_UNSUPPORTED, what + ": a cube carries all its levels (no MipmapSource::Generated for cubes, rend3/src/managers/texture.rs:147)");
-        if ((d.offset & 3u) != 0u) return fail(c, R3N_ERR_INVALID_ARG, what + ": face +X level 0 must start on a 4-byte boundary");
-        const uint32_t N = d.width, per_texel = texture_jobs::is_float(d.format) ? 4u : 1u;
-        uint64_t face_bytes = 0;
-        for (uint32_t k = 0; k < d.mips; ++k) face_bytes += r3n_internal_level_bytes(d.format, cube_faces::level_extent(N, k), cube_faces::level_extent(N, k));
-        if ((uint64_t)d.offset + 6u * face_bytes > payload_bytes) return fail(c, R3N_ERR_INVALID_ARG, what + ": faces outside the payload");
-        const uint64_t words = cube_faces::cube_words(N, d.mips, per_texel);
-        if (pool_words + words > 0xFFFFFFFFull) return fail(c, R3N_ERR_CAPACITY, what + ": the cube pool exceeds 2^32 words");
-        cubes[ci] = {(size_t)pool_words, N, format_is_srgb(d.format) ? 1u : 0u, d.mips, per_texel == 4u ? 2u : (format_is_srgb(d.format) ? 1u : 0u)};
-        uint64_t level_at = pool_words;
-        for (uint32_t k = 0; k < d.mips; ++k) {
-            const uint32_t nk = cube_faces::level_extent(N, k);
-            const uint64_t stride = cube_faces::dense_face_words(nk, per_texel), units = (uint64_t)(nk + 2u) * (nk + 2u);
-            for (uint32_t f = 0; f < 6u; ++f) {
-                // LayerMajor: face f's levels lie back to back
-                uint64_t src = (uint64_t)d.offset + f * face_bytes;
-                for (uint32_t l = 0; l < k; ++l) src += r3n_internal_level_bytes(d.format, cube_faces::level_extent(N, l), cube_faces::level_extent(N, l));
-                texture_jobs::add_level(work.tables, d.format, nk, nk, src, (uint32_t)(dense_words + f * stride));
-                recs.push_back(cube_faces::Record{nk, f, per_texel, (uint32_t)units, (uint32_t)dense_words, (uint32_t)stride,
-                                                  (uint32_t)(level_at + f * cube_faces::face_words(nk, per_texel)), 0u});
-                asm_waves += vertex_block::waves(units, cube_faces::UNITS_PER_WAVE);
-            }
-            dense_words += 6u * stride;  // (below the pool's words: a dense face is smaller than its bordered face)
-            level_at += cube_faces::level_words(nk, per_texel);
-        }
-        pool_words += words;
-    }
-    if (!finish_texture_work(work) || asm_waves > vertex_block::MAX_WAVES)
-        return fail(c, R3N_ERR_CAPACITY, what + ": more than 2^31 wave slots of decode or assemble work in one call");
-    std::vector<uint32_t> asm_block;
-    const vertex_block::layout asm_layout = vertex_block::lay_out(asm_block, (uint32_t)recs.size(), cube_faces::REC_WORDS, asm_waves, [&](uint32_t i) {
-        return vertex_block::waves(recs[i].units, cube_faces::UNITS_PER_WAVE);
-    });
-    if (!recs.empty()) std::memcpy(asm_block.data(), recs.data(), recs.size() * sizeof(cube_faces::Record));
-    // ---- device side
-    HIP_TRY(c, hipSetDevice(c->device));
-    TRY(sync_all(c));  // no frame may still sample the old array
-    TRY(ensure(c, c->cube_texels, std::max<uint64_t>(pool_words, 1) * 4, false, -1));
-    if (n) {
-        // a block of the call's own, payload | job tables | assemble table | dense faces, freed before the call returns
-        const uint64_t jobs_at = (std::max<uint64_t>(payload_bytes, 4) + 255u) & ~255ull;
-        const uint64_t asm_at = (jobs_at + work.job_block.size() * 4u + 255u) & ~255ull;
-        const uint64_t dense_at = (asm_at + asm_block.size() * 4u + 255u) & ~255ull;
-        DeviceBuffer scratch;
-        HIP_TRY(c, scratch.alloc(dense_at + std::max<uint64_t>(dense_words, 4) * 4u));
-        uint32_t *dense = reinterpret_cast<uint32_t *>(scratch.as<char>() + dense_at);
-        uint32_t *asm_dev = reinterpret_cast<uint32_t *>(scratch.as<char>() + asm_at);
-        uint64_t launches = 0;
-        hipError_t e = hipMemcpyAsync(asm_dev, asm_block.data(), asm_block.size() * 4u, hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess)
-            e = enqueue_texture_work(c, work, payload, payload_bytes, c->stream, scratch.p, reinterpret_cast<uint32_t *>(scratch.as<char>() + jobs_at), launches, dense);
-        if (e == hipSuccess)
-            e = (hipError_t)r3n_internal_cube_assemble(asm_dev, asm_layout.o_first, asm_layout.o_inst, (uint32_t)asm_waves, dense, c->cube_texels.as<uint32_t>(), c->stream);
-        const hipError_t e2 = hipStreamSynchronize(c->stream);  // the caller owns the sources only for the duration of the call
-        (void)scratch.reset();
-        if (e != hipSuccess) return fail(c, R3N_ERR_HIP, what + ": " + hipGetErrorString(e));
-        if (e2 != hipSuccess) return fail(c, R3N_ERR_HIP, what + ": " + hipGetErrorString(e2));
-    }
-    c->cubes = std::move(cubes);
-    if (c->sky_cube > n) c->sky_cube = 0;
-    return R3N_OK;
-}
-
 extern "C" int r3n_internal_equirect_faces(const uint32_t *block, uint64_t o_first, uint64_t o_inst, uint32_t total_waves, const void *staged,
                                            uint32_t *dense, const float *srgb_decode, hipStream_t stream);
 extern "C" int r3n_internal_equirect_level(const uint32_t *block, uint64_t o_first, uint64_t o_inst, uint32_t total_waves, uint32_t *dense,
                                            hipStream_t stream);
 extern "C" int r3n_internal_equirect_tail(const uint32_t *recs, uint32_t n_recs, uint32_t *dense, hipStream_t stream);
-// kernels the last r3n_texture_cubes_write_sources enqueued: decode families, k_equirect_faces, the chain, k_cube_assemble
+// kernels the last cube upload enqueued: decode families, k_equirect_faces, the chain, k_cube_assemble
 extern "C" uint64_t r3n_internal_cube_source_launches(const r3n_ctx *c) { return c ? c->cube_source_launches : 0; }
 // with r3n_timing_enable, the phases of that call between device events, in ms (tools/equirect_cost.py)
 extern "C" int r3n_internal_cube_source_times(const r3n_ctx *c, float out[4]) {
@@ -3387,158 +3221,32 @@ extern "C" int r3n_internal_cube_source_times(const r3n_ctx *c, float out[4]) {
     return R3N_OK;
 }
 
-// Cubes from stored faces (as r3n_texture_cubes_write_encoded) and from equirectangular panoramas, in one array.  A panorama is
-// resampled into dense level-0 faces (k_equirect_faces, one launch for the call), its chain is built face by face (equirect_rule.h:
-// the plan), and k_cube_assemble borders everything exactly as for stored faces.
-int r3n_texture_cubes_write_sources(r3n_ctx *c, const r3n_cube_source *sources, uint32_t n, const void *payload, uint64_t payload_bytes) {
-    const std::string what = "texture cubes write (sources)";
-    if (!c || (n && (!sources || !payload))) return fail(c, R3N_ERR_INVALID_ARG, what + ": null");
-    if (c->in_frame) return fail(c, R3N_ERR_STATE, what + ": inside a frame");
-    // ---- plan on the host; nothing changes before every cube has been accepted
-    struct Launch { size_t at; vertex_block::layout layout; uint64_t waves; };  // one wave-mapped table inside eq_block
-    std::vector<r3n_ctx::Cube> cubes(n);
-    std::vector<cube_faces::Record> recs;
-    std::vector<equirect::FaceRec> face_recs;
-    std::vector<std::vector<equirect::ChainRec>> level_recs;  // [k - 1]: level launch k
-    std::vector<equirect::ChainRec> tail_recs;
-    TextureWork work;
-    uint64_t pool_words = 0, dense_words = 0, asm_waves = 0;
-    const uint32_t T = c->equirect_tail;
-    for (uint32_t ci = 0; ci < n; ++ci) {
-        const r3n_cube_source &s = sources[ci];
-        if (s.kind != R3N_CUBE_SOURCE_CUBE && s.kind != R3N_CUBE_SOURCE_EQUIRECT) return fail(c, R3N_ERR_INVALID_ARG, what + ": unknown source kind");
-        const bool equi = s.kind == R3N_CUBE_SOURCE_EQUIRECT, rgbe = equi && s.format == R3N_CUBE_ENCODING_RGBE8;
-        if (!rgbe && s.format >= R3N_TEXTURE_FORMAT_COUNT) return fail(c, R3N_ERR_INVALID_ARG, what + ": unknown format id");
-        if (!s.width || !s.height || !s.face_extent) return fail(c, R3N_ERR_INVALID_ARG, what + ": zero extent");
-        if (s.width > equirect_rule::MAX_SOURCE_EXTENT || s.height > equirect_rule::MAX_SOURCE_EXTENT) return fail(c, R3N_ERR_INVALID_ARG, what + ": a source extent above 65535");
-        if (s.face_extent > equirect_rule::MAX_FACE_EXTENT) return fail(c, R3N_ERR_INVALID_ARG, what + ": a face extent above 16384");
-        if (!equi && (s.width != s.height || s.width != s.face_extent)) return fail(c, R3N_ERR_INVALID_ARG, what + ": a cube's faces are square, of the face extent");
-        const uint32_t N = s.face_extent;
-        if (!s.mips || s.mips > equirect_rule::max_mips(N)) return fail(c, R3N_ERR_INVALID_ARG, what + ": more mips than the extent has");
-        if ((s.offset & 3u) != 0u) return fail(c, R3N_ERR_INVALID_ARG, what + ": a source must start on a 4-byte boundary");
-        const uint32_t per_texel = equi || texture_jobs::is_float(s.format) ? 4u : 1u;
-        uint64_t source_bytes = 0, face_bytes = 0;
-        if (equi) {
-            source_bytes = rgbe ? (uint64_t)s.width * s.height * 4u : r3n_internal_level_bytes(s.format, s.width, s.height);
-        } else {
-            for (uint32_t k = 0; k < s.mips; ++k) face_bytes += r3n_internal_level_bytes(s.format, cube_faces::level_extent(N, k), cube_faces::level_extent(N, k));
-            source_bytes = 6u * face_bytes;
-        }
-        if (s.offset > payload_bytes || source_bytes > payload_bytes - s.offset) return fail(c, R3N_ERR_INVALID_ARG, what + ": data outside the payload");
-        const uint64_t words = cube_faces::cube_words(N, s.mips, per_texel);
-        if (pool_words + words > 0xFFFFFFFFull) return fail(c, R3N_ERR_CAPACITY, what + ": the cube pool exceeds 2^32 words");
-        const bool srgb = !equi && format_is_srgb(s.format);
-        cubes[ci] = {(size_t)pool_words, N, srgb ? 1u : 0u, s.mips, per_texel == 4u ? 2u : (srgb ? 1u : 0u)};
-        // an equirect source that is not RGBE is decoded by the 2D job tables into the scratch block, in front of the cube's faces
-        uint64_t decoded_at = 0;
-        uint32_t mode = equirect::SOURCE_RGBE8;
-        if (equi && !rgbe) {
-            const bool f32 = texture_jobs::is_float(s.format);
-            mode = f32 ? equirect::SOURCE_F32 : (format_is_srgb(s.format) ? equirect::SOURCE_RGBA8_SRGB : equirect::SOURCE_RGBA8);
-            decoded_at = dense_words;
-            dense_words += ((uint64_t)s.width * s.height * (f32 ? 4u : 1u) + 3u) & ~3ull;
-            if (dense_words > 0xFFFFFFFFull) return fail(c, R3N_ERR_CAPACITY, what + ": the scratch block exceeds 2^32 words");
-            texture_jobs::add_level(work.tables, s.format, s.width, s.height, s.offset, (uint32_t)decoded_at);
-        }
-        const uint32_t from = equi ? equirect_rule::tail_from(N, s.mips, T) : 0u;
-        uint64_t level_at = pool_words, above_at = 0;
-        for (uint32_t k = 0; k < s.mips; ++k) {
-            const uint32_t nk = cube_faces::level_extent(N, k);
-            const uint64_t stride = cube_faces::dense_face_words(nk, per_texel), units = (uint64_t)(nk + 2u) * (nk + 2u);
-            if (dense_words + 6u * stride > 0xFFFFFFFFull) return fail(c, R3N_ERR_CAPACITY, what + ": the scratch block exceeds 2^32 words");
-            for (uint32_t f = 0; f < 6u; ++f) {
-                if (!equi) {
-                    // LayerMajor: face f's levels lie back to back
-                    uint64_t src = s.offset + f * face_bytes;
-                    for (uint32_t l = 0; l < k; ++l) src += r3n_internal_level_bytes(s.format, cube_faces::level_extent(N, l), cube_faces::level_extent(N, l));
-                    texture_jobs::add_level(work.tables, s.format, nk, nk, src, (uint32_t)(dense_words + f * stride));
-                } else if (k == 0u) {
-                    equirect::FaceRec r{};
-                    r.n = N; r.face = f; r.mode = mode; r.W = s.width; r.H = s.height;
-                    r.src_lo = rgbe ? (uint32_t)s.offset : (uint32_t)decoded_at;
-                    r.src_hi = rgbe ? (uint32_t)(s.offset >> 32) : 0u;
-                    r.dst = (uint32_t)(dense_words + f * stride);
-                    r.units = N * N;
-                    face_recs.push_back(r);
-                } else if (k <= from) {
-                    const uint32_t sk = cube_faces::level_extent(N, k - 1u);
-                    if (level_recs.size() < k) level_recs.resize(k);
-                    level_recs[k - 1u].push_back(equirect::ChainRec{sk, nk, (uint32_t)(above_at + f * cube_faces::dense_face_words(sk, 4u)),
-                                                                    (uint32_t)(dense_words + f * stride), nk * nk, f, 1u, 0u});
-                } else if (k == from + 1u) {
-                    tail_recs.push_back(equirect::ChainRec{cube_faces::level_extent(N, from), nk, (uint32_t)above_at, (uint32_t)dense_words, 0u, f, s.mips - 1u - from, 0u});
-                }
-                recs.push_back(cube_faces::Record{nk, f, per_texel, (uint32_t)units, (uint32_t)dense_words, (uint32_t)stride,
-                                                  (uint32_t)(level_at + f * cube_faces::face_words(nk, per_texel)), 0u});
-                asm_waves += vertex_block::waves(units, cube_faces::UNITS_PER_WAVE);
-            }
-            above_at = dense_words;
-            dense_words += 6u * stride;
-            level_at += cube_faces::level_words(nk, per_texel);
-        }
-        pool_words += words;
-    }
-    if (!finish_texture_work(work) || asm_waves > vertex_block::MAX_WAVES)
-        return fail(c, R3N_ERR_CAPACITY, what + ": more than 2^31 wave slots of decode or assemble work in one call");
-    std::vector<uint32_t> asm_block;
-    const vertex_block::layout asm_layout = vertex_block::lay_out(asm_block, (uint32_t)recs.size(), cube_faces::REC_WORDS, asm_waves, [&](uint32_t i) {
-        return vertex_block::waves(recs[i].units, cube_faces::UNITS_PER_WAVE);
-    });
-    if (!recs.empty()) std::memcpy(asm_block.data(), recs.data(), recs.size() * sizeof(cube_faces::Record));
-    // the equirect tables as ONE block: faces | level 1 | level 2 | ... | tail records, each on a 16-word boundary
-    std::vector<uint32_t> eq_block;
-    std::vector<Launch> eq_launches;  // [0]: the faces, then the level launches
-    auto add_table = [&](const void *records, uint32_t count, size_t rec_words, auto units_of) {
-        uint64_t waves = 0;
-        for (uint32_t i = 0; i < count; ++i) waves += vertex_block::waves(units_of(i), equirect::UNITS_PER_WAVE);
-        if (waves > vertex_block::MAX_WAVES) return false;
-        std::vector<uint32_t> block;
-        const vertex_block::layout l = vertex_block::lay_out(block, count, rec_words, waves, [&](uint32_t i) { return vertex_block::waves(units_of(i), equirect::UNITS_PER_WAVE); });
-        std::memcpy(block.data(), records, (size_t)count * rec_words * 4u);
-        eq_launches.push_back(Launch{eq_block.size(), l, waves});
-        eq_block.insert(eq_block.end(), block.begin(), block.end());
-        eq_block.resize((eq_block.size() + 15u) & ~(size_t)15u, 0u);
-        return true;
-    };
-    bool fits = true;
-    if (!face_recs.empty()) {
-        fits = add_table(face_recs.data(), (uint32_t)face_recs.size(), equirect::FACE_REC_WORDS, [&](uint32_t i) { return (uint64_t)face_recs[i].units; });
-        for (size_t k = 0; k < level_recs.size() && fits; ++k)
-            fits = add_table(level_recs[k].data(), (uint32_t)level_recs[k].size(), equirect::CHAIN_REC_WORDS, [&](uint32_t i) { return (uint64_t)level_recs[k][i].units; });
-    }
-    if (!fits) return fail(c, R3N_ERR_CAPACITY, what + ": more than 2^31 wave slots of resampling work in one call");
-    const size_t tail_words_at = eq_block.size();
-    eq_block.resize(tail_words_at + tail_recs.size() * equirect::CHAIN_REC_WORDS, 0u);
-    if (!tail_recs.empty()) std::memcpy(eq_block.data() + tail_words_at, tail_recs.data(), tail_recs.size() * sizeof(equirect::ChainRec));
-    // ---- device side
+// The device half of every entry.  Every stored (cube, face, level) is one decode job into a DENSE face of the call's scratch block
+// (at most four launches, the 2D path's kernels); a panorama is resampled into dense level-0 faces (k_equirect_faces, one launch
+// for the call) and its chain built face by face (equirect_rule.h: the launch plan); k_cube_assemble then builds every bordered
+// face of the call in one launch.  Nothing of the context changes before the plan exists; the array is replaced at the end.
+static int write_cube_plan(r3n_ctx *c, const std::string &what, const cube_plan::Plan &plan, const void *payload, uint64_t payload_bytes) {
     HIP_TRY(c, hipSetDevice(c->device));
     TRY(sync_all(c));  // no frame may still sample the old array
-    TRY(ensure(c, c->cube_texels, std::max<uint64_t>(pool_words, 1) * 4, false, -1));
+    TRY(ensure(c, c->cube_texels, std::max<uint64_t>(plan.pool_words, 1) * 4, false, -1));
     uint64_t launches = 0;
-    if (n) {
-        // a block of the call's own, payload | job tables | assemble table | equirect tables | decoded sources and dense faces, freed
-        // before the call returns
-        const uint64_t jobs_at = (std::max<uint64_t>(payload_bytes, 4) + 255u) & ~255ull;
-        const uint64_t asm_at = (jobs_at + work.job_block.size() * 4u + 255u) & ~255ull;
-        const uint64_t eq_at = (asm_at + asm_block.size() * 4u + 255u) & ~255ull;
-        const uint64_t dense_at = (eq_at + eq_block.size() * 4u + 255u) & ~255ull;
+    if (!plan.cubes.empty()) {
+        // a block of the call's own (cube_plan.h lays it out), freed before the call returns
         DeviceBuffer scratch;
-        HIP_TRY(c, scratch.alloc(dense_at + std::max<uint64_t>(dense_words, 4) * 4u));
-        uint32_t *dense = reinterpret_cast<uint32_t *>(scratch.as<char>() + dense_at);
-        uint32_t *asm_dev = reinterpret_cast<uint32_t *>(scratch.as<char>() + asm_at);
-        uint32_t *eq_dev = reinterpret_cast<uint32_t *>(scratch.as<char>() + eq_at);
+        HIP_TRY(c, scratch.alloc(plan.scratch_bytes));
+        auto part = [&](uint64_t at) { return reinterpret_cast<uint32_t *>(scratch.as<char>() + at); };
+        uint32_t *dense = part(plan.dense_at), *asm_dev = part(plan.asm_at), *eq_dev = part(plan.eq_at);
         Event taps[5];  // phase boundaries, with r3n_timing_enable only
         auto tap = [&](int k) {
             if (c->timing && taps[k].create() == hipSuccess) (void)hipEventRecord(taps[k], c->stream);
         };
         tap(0);
-        hipError_t e = hipMemcpyAsync(asm_dev, asm_block.data(), asm_block.size() * 4u, hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess && !eq_block.empty()) e = hipMemcpyAsync(eq_dev, eq_block.data(), eq_block.size() * 4u, hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess)
-            e = enqueue_texture_work(c, work, payload, payload_bytes, c->stream, scratch.p, reinterpret_cast<uint32_t *>(scratch.as<char>() + jobs_at), launches, dense);
+        hipError_t e = hipMemcpyAsync(asm_dev, plan.assemble.block.data(), plan.assemble.block.size() * 4u, hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess && !plan.eq_block.empty()) e = hipMemcpyAsync(eq_dev, plan.eq_block.data(), plan.eq_block.size() * 4u, hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess) e = enqueue_decode_jobs(plan.jobs, payload, payload_bytes, c->stream, scratch.p, part(plan.jobs_at), launches, dense);
         tap(1);
-        for (size_t i = 0; i < eq_launches.size() && e == hipSuccess; ++i) {
-            const Launch &l = eq_launches[i];
+        for (size_t i = 0; i < plan.eq_launches.size() && e == hipSuccess; ++i) {
+            const cube_plan::Launch &l = plan.eq_launches[i];
             if (i == 1u) tap(2);
             if (i == 0u)
                 e = (hipError_t)r3n_internal_equirect_faces(eq_dev + l.at, l.layout.o_first, l.layout.o_inst, (uint32_t)l.waves, scratch.p, dense, c->srgb8_decode.as<float>() + 256,  // (the table's sRGB half)
@@ -3547,14 +3255,14 @@ int r3n_texture_cubes_write_sources(r3n_ctx *c, const r3n_cube_source *sources, 
                 e = (hipError_t)r3n_internal_equirect_level(eq_dev + l.at, l.layout.o_first, l.layout.o_inst, (uint32_t)l.waves, dense, c->stream);
             ++launches;
         }
-        if (eq_launches.size() <= 1u) tap(2);
-        if (e == hipSuccess && !tail_recs.empty()) {
-            e = (hipError_t)r3n_internal_equirect_tail(eq_dev + tail_words_at, (uint32_t)tail_recs.size(), dense, c->stream);
+        if (plan.eq_launches.size() <= 1u) tap(2);
+        if (e == hipSuccess && plan.tail_recs) {
+            e = (hipError_t)r3n_internal_equirect_tail(eq_dev + plan.tail_at, plan.tail_recs, dense, c->stream);
             ++launches;
         }
         tap(3);
         if (e == hipSuccess) {
-            e = (hipError_t)r3n_internal_cube_assemble(asm_dev, asm_layout.o_first, asm_layout.o_inst, (uint32_t)asm_waves, dense, c->cube_texels.as<uint32_t>(), c->stream);
+            e = (hipError_t)r3n_internal_cube_assemble(asm_dev, plan.assemble.layout.o_first, plan.assemble.layout.o_inst, (uint32_t)plan.assemble.waves, dense, c->cube_texels.as<uint32_t>(), c->stream);
             ++launches;
         }
         tap(4);
@@ -3566,9 +3274,55 @@ int r3n_texture_cubes_write_sources(r3n_ctx *c, const r3n_cube_source *sources, 
         if (e2 != hipSuccess) return fail(c, R3N_ERR_HIP, what + ": " + hipGetErrorString(e2));
     }
     c->cube_source_launches = launches;
-    c->cubes = std::move(cubes);
-    if (c->sky_cube > n) c->sky_cube = 0;
+    c->cubes = plan.cubes;
+    if (c->sky_cube > plan.cubes.size()) c->sky_cube = 0;
     return R3N_OK;
+}
+// plans on the host -- nothing changes before every cube has been accepted -- then executes
+static int plan_and_write_cubes(r3n_ctx *c, const std::string &what, const std::vector<cube_plan::Source> &sources, const void *payload, uint64_t payload_bytes) {
+    cube_plan::Plan plan;
+    const cube_plan::Refusal refused = cube_plan::plan(sources.data(), (uint32_t)sources.size(), payload_bytes, c->equirect_tail, plan);
+    if (refused.code != R3N_OK) return fail(c, refused.code, what + ": " + refused.why);
+    return write_cube_plan(c, what, plan, payload, payload_bytes);
+}
+
+int r3n_texture_cubes_write(r3n_ctx *c, const r3n_texture_desc32 *descs, uint32_t n, const uint32_t *texels, uint64_t n_texels) {
+    if (!c || (n && (!descs || !texels))) return fail(c, R3N_ERR_INVALID_ARG, "texture cubes write: null");
+    if (c->in_frame) return fail(c, R3N_ERR_STATE, "texture cubes write: inside a frame");
+    for (uint32_t i = 0; i < n; ++i) {
+        const r3n_texture_desc32 &d = descs[i];
+        if (d.width != d.height) return fail(c, R3N_ERR_INVALID_ARG, "texture cubes write: a cube's faces are square");
+        if (!d.width || d.width > 16384u) return fail(c, R3N_ERR_INVALID_ARG, "texture cubes write: bad extent");
+        if (d.format > R3N_TEXTURE_RGBA8_UNORM_SRGB) return fail(c, R3N_ERR_UNSUPPORTED, "texture cubes write: Rgba8Unorm / Rgba8UnormSrgb cubes only");
+        if (d.mips != 1u) return fail(c, R3N_ERR_UNSUPPORTED, "texture cubes write: single-level cubes only (no level selection from cube-direction derivatives)");
+        if ((uint64_t)d.offset + 6ull * d.width * d.width > n_texels) return fail(c, R3N_ERR_INVALID_ARG, "texture cubes write: faces outside the texel array");
+    }
+    // one-level stored cubes of the encoded entry: a texel is a 4-byte word of the payload
+    std::vector<cube_plan::Source> sources(n);
+    for (uint32_t i = 0; i < n; ++i) {
+        sources[i] = cube_plan::from_desc(descs[i]);
+        sources[i].offset = 4ull * descs[i].offset;
+        sources[i].stored_mips = 0u;
+    }
+    return plan_and_write_cubes(c, "texture cubes write", sources, texels, 4u * n_texels);
+}
+
+int r3n_texture_cubes_write_encoded(r3n_ctx *c, const r3n_texture_desc32 *descs, uint32_t n, const void *payload, uint64_t payload_bytes) {
+    const std::string what = "texture cubes write (encoded)";
+    if (!c || (n && (!descs || !payload))) return fail(c, R3N_ERR_INVALID_ARG, what + ": null");
+    if (c->in_frame) return fail(c, R3N_ERR_STATE, what + ": inside a frame");
+    std::vector<cube_plan::Source> sources(n);
+    for (uint32_t i = 0; i < n; ++i) sources[i] = cube_plan::from_desc(descs[i]);
+    return plan_and_write_cubes(c, what, sources, payload, payload_bytes);
+}
+
+int r3n_texture_cubes_write_sources(r3n_ctx *c, const r3n_cube_source *sources, uint32_t n, const void *payload, uint64_t payload_bytes) {
+    const std::string what = "texture cubes write (sources)";
+    if (!c || (n && (!sources || !payload))) return fail(c, R3N_ERR_INVALID_ARG, what + ": null");
+    if (c->in_frame) return fail(c, R3N_ERR_STATE, what + ": inside a frame");
+    std::vector<cube_plan::Source> planned(n);
+    for (uint32_t i = 0; i < n; ++i) planned[i] = cube_plan::from_source(sources[i]);
+    return plan_and_write_cubes(c, what, planned, payload, payload_bytes);
 }
 
 int r3n_skybox_set(r3n_ctx *c, uint32_t cube_id) {

@@ -1,15 +1,15 @@
 // skybox.h -- the skybox node (rend3-routine/src/skybox.rs + skybox.wgsl): argument block and launcher of k_skybox (skybox.hip),
-// and the layout of the cube-texture pool r3n_texture_cubes_write / r3n_texture_cubes_write_encoded build (r3n.hip).
+// and the layout of the cube-texture pool the three upload entries build (r3n_texture_cubes_write, _encoded, _sources; cube_plan.h).
 //
 // Cube pool: every cube is six faces in layer order +X, -X, +Y, -Y, +Z, -Z, each stored WITH A ONE-TEXEL BORDER: (N + 2) x (N + 2)
 // texels, row-major, interior texel (i, j) at (i + 1, j + 1).  The border of an edge holds the adjacent face's texels across
-// that edge (filled on the host by r3n_texture_cubes_write, by k_cube_assemble for the encoded entry), so the seamless footprint of
+// that edge (filled by k_cube_assemble for every entry, from the edge table of cube_faces.h), so the seamless footprint of
 // DESIGN section 2 is a plain fetch; the four corner texels of a face are never read -- the kernel forms a corner from the three
 // texels that exist.
 //
 // A texel is one RGBA8 word (classes 0 / 1: Rgba8Unorm / Rgba8UnormSrgb words) or four f32 words (class 2, the formats
 // texture_jobs::is_float names).  A cube with `mips` levels holds level 0's six bordered faces, then level 1's (extent
-// n_1 = max(1, N >> 1)), and so on; every level -- and, from the encoded entry, every cube -- starts on a 4-word boundary, so an
+// n_1 = max(1, N >> 1)), and so on; every level and every cube starts on a 4-word boundary, so an
 // f32 texel is one aligned 16-byte access.  cube_faces.h has the arithmetic (level_start, face_words) and the edge table.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -614,34 +614,10 @@ extern "C" int r3n_internal_generate_mip(uint32_t srgb, uint32_t sw, uint32_t sh
     return (int)hipGetLastError();
 }
 
-// bytes of one w x h level in `format`; 0 for an unknown format
-extern "C" uint64_t r3n_internal_level_bytes(uint32_t format, uint32_t w, uint32_t h) {
-    switch (format) {
-    case R3N_TEXTURE_RGBA8_UNORM: case R3N_TEXTURE_RGBA8_UNORM_SRGB: case R3N_TEXTURE_BGRA8_UNORM: case R3N_TEXTURE_BGRA8_UNORM_SRGB:
-        return (uint64_t)w * h * 4u;
-    case R3N_TEXTURE_R8_UNORM: return (uint64_t)w * h;
-    case R3N_TEXTURE_RG8_UNORM: return (uint64_t)w * h * 2u;
-    case R3N_TEXTURE_BC1_RGBA_UNORM: case R3N_TEXTURE_BC1_RGBA_UNORM_SRGB: case R3N_TEXTURE_BC4_R_UNORM:
-        return (uint64_t)((w + 3u) / 4u) * ((h + 3u) / 4u) * 8u;
-    case R3N_TEXTURE_BC2_RGBA_UNORM: case R3N_TEXTURE_BC2_RGBA_UNORM_SRGB: case R3N_TEXTURE_BC3_RGBA_UNORM:
-    case R3N_TEXTURE_BC3_RGBA_UNORM_SRGB: case R3N_TEXTURE_BC5_RG_UNORM: case R3N_TEXTURE_BC7_RGBA_UNORM:
-    case R3N_TEXTURE_BC7_RGBA_UNORM_SRGB: case R3N_TEXTURE_BC5_RG_SNORM: case R3N_TEXTURE_BC6H_RGB_UFLOAT: case R3N_TEXTURE_BC6H_RGB_FLOAT:
-        return (uint64_t)((w + 3u) / 4u) * ((h + 3u) / 4u) * 16u;
-    case R3N_TEXTURE_BC4_R_SNORM: return (uint64_t)((w + 3u) / 4u) * ((h + 3u) / 4u) * 8u;
-    case R3N_TEXTURE_R8_SNORM: return (uint64_t)w * h;
-    case R3N_TEXTURE_RG8_SNORM: case R3N_TEXTURE_R16_FLOAT: return (uint64_t)w * h * 2u;
-    case R3N_TEXTURE_RGBA8_SNORM: case R3N_TEXTURE_RG16_FLOAT: case R3N_TEXTURE_R32_FLOAT: case R3N_TEXTURE_RGB10A2_UNORM:
-    case R3N_TEXTURE_RG11B10_FLOAT: case R3N_TEXTURE_RGB9E5_UFLOAT:
-        return (uint64_t)w * h * 4u;
-    case R3N_TEXTURE_RGBA16_FLOAT: case R3N_TEXTURE_RG32_FLOAT: case R3N_TEXTURE_RGBA16_UNORM: case R3N_TEXTURE_RGBA16_SNORM:
-        return (uint64_t)w * h * 8u;
-    case R3N_TEXTURE_RGBA32_FLOAT: return (uint64_t)w * h * 16u;
-    default: return 0;
-    }
-}
-
+// bytes of one w x h level in `format`; 0 for an unknown format (texture_jobs.h; Python and the tools call this)
+extern "C" uint64_t r3n_internal_level_bytes(uint32_t format, uint32_t w, uint32_t h) { return texture_jobs::level_bytes(format, w, h); }
 // 1: the format decodes to four f32 per texel (the f32 job families), 0: to RGBA8
-extern "C" int r3n_internal_format_is_float(uint32_t format) { return format >= R3N_TEXTURE_R8_SNORM && format < R3N_TEXTURE_FORMAT_COUNT; }
+extern "C" int r3n_internal_format_is_float(uint32_t format) { return texture_jobs::is_float(format) ? 1 : 0; }
 // required alignment of a level's first byte in the payload (the decoders read it through that type)
 extern "C" uint32_t r3n_internal_format_align(uint32_t format) {
     switch (format) {

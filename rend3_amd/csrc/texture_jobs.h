@@ -58,6 +58,36 @@ inline bool is_float(uint32_t format) { return format >= R3N_TEXTURE_R8_SNORM &&
 inline bool is_block(uint32_t format) {
     return is_float(format) ? format >= R3N_TEXTURE_BC4_R_SNORM : format >= R3N_TEXTURE_BC1_RGBA_UNORM;
 }
+// the RGBA8-decoded formats whose pool words are sRGB-encoded
+inline bool is_srgb(uint32_t format) {
+    return format == R3N_TEXTURE_RGBA8_UNORM_SRGB || format == R3N_TEXTURE_BGRA8_UNORM_SRGB || format == R3N_TEXTURE_BC1_RGBA_UNORM_SRGB ||
+           format == R3N_TEXTURE_BC2_RGBA_UNORM_SRGB || format == R3N_TEXTURE_BC3_RGBA_UNORM_SRGB || format == R3N_TEXTURE_BC7_RGBA_UNORM_SRGB;
+}
+// bytes of one w x h level in `format`; 0 for an unknown format
+inline uint64_t level_bytes(uint32_t format, uint32_t w, uint32_t h) {
+    switch (format) {
+    case R3N_TEXTURE_RGBA8_UNORM: case R3N_TEXTURE_RGBA8_UNORM_SRGB: case R3N_TEXTURE_BGRA8_UNORM: case R3N_TEXTURE_BGRA8_UNORM_SRGB:
+        return (uint64_t)w * h * 4u;
+    case R3N_TEXTURE_R8_UNORM: return (uint64_t)w * h;
+    case R3N_TEXTURE_RG8_UNORM: return (uint64_t)w * h * 2u;
+    case R3N_TEXTURE_BC1_RGBA_UNORM: case R3N_TEXTURE_BC1_RGBA_UNORM_SRGB: case R3N_TEXTURE_BC4_R_UNORM:
+        return (uint64_t)((w + 3u) / 4u) * ((h + 3u) / 4u) * 8u;
+    case R3N_TEXTURE_BC2_RGBA_UNORM: case R3N_TEXTURE_BC2_RGBA_UNORM_SRGB: case R3N_TEXTURE_BC3_RGBA_UNORM:
+    case R3N_TEXTURE_BC3_RGBA_UNORM_SRGB: case R3N_TEXTURE_BC5_RG_UNORM: case R3N_TEXTURE_BC7_RGBA_UNORM:
+    case R3N_TEXTURE_BC7_RGBA_UNORM_SRGB: case R3N_TEXTURE_BC5_RG_SNORM: case R3N_TEXTURE_BC6H_RGB_UFLOAT: case R3N_TEXTURE_BC6H_RGB_FLOAT:
+        return (uint64_t)((w + 3u) / 4u) * ((h + 3u) / 4u) * 16u;
+    case R3N_TEXTURE_BC4_R_SNORM: return (uint64_t)((w + 3u) / 4u) * ((h + 3u) / 4u) * 8u;
+    case R3N_TEXTURE_R8_SNORM: return (uint64_t)w * h;
+    case R3N_TEXTURE_RG8_SNORM: case R3N_TEXTURE_R16_FLOAT: return (uint64_t)w * h * 2u;
+    case R3N_TEXTURE_RGBA8_SNORM: case R3N_TEXTURE_RG16_FLOAT: case R3N_TEXTURE_R32_FLOAT: case R3N_TEXTURE_RGB10A2_UNORM:
+    case R3N_TEXTURE_RG11B10_FLOAT: case R3N_TEXTURE_RGB9E5_UFLOAT:
+        return (uint64_t)w * h * 4u;
+    case R3N_TEXTURE_RGBA16_FLOAT: case R3N_TEXTURE_RG32_FLOAT: case R3N_TEXTURE_RGBA16_UNORM: case R3N_TEXTURE_RGBA16_SNORM:
+        return (uint64_t)w * h * 8u;
+    case R3N_TEXTURE_RGBA32_FLOAT: return (uint64_t)w * h * 16u;
+    default: return 0;
+    }
+}
 inline Family family_of(uint32_t format) {
     return is_float(format) ? (is_block(format) ? F32_BLOCK : F32_EXPAND) : (is_block(format) ? RGBA8_BLOCK : RGBA8_EXPAND);
 }
@@ -92,6 +122,25 @@ inline bool finish(Table tables[FAMILIES]) {
                                          [&](uint32_t i) { return vertex_block::waves(t.jobs[i].units, UNITS_PER_WAVE); });
         if (n) std::memcpy(t.block.data(), t.jobs.data(), (size_t)n * sizeof(Job));
     }
+    return true;
+}
+
+// a call's four tables and the ONE block it uploads: every table on an 8-word boundary, table f at job_at[f]
+struct Work {
+    Table tables[FAMILIES];
+    size_t job_at[FAMILIES];
+    std::vector<uint32_t> job_block;
+};
+// lays the filled tables out as the ONE block: false when a family has more wave slots than its kernel counts
+inline bool finish_work(Work &work) {
+    if (!finish(work.tables)) return false;
+    size_t words = 0;
+    for (int f = 0; f < FAMILIES; ++f) {
+        work.job_at[f] = words;
+        words += (work.tables[f].block.size() + 7u) & ~(size_t)7u;
+    }
+    work.job_block.assign(std::max<size_t>(words, 1), 0u);
+    for (int f = 0; f < FAMILIES; ++f) std::copy(work.tables[f].block.begin(), work.tables[f].block.end(), work.job_block.begin() + work.job_at[f]);
     return true;
 }
 

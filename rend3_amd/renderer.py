@@ -1235,24 +1235,35 @@ class Renderer:
             total = total + f[1, 1]
         return total / np.float32(6.0)
 
+    @staticmethod
+    def _pack_cube(payload, cube):
+        """appends a cube's bytes to `payload` at a 4-byte boundary -- a stored cube LayerMajor (face by face, a face's levels back to
+        back), a panorama as its one level -- and returns the offset"""
+        payload += bytes(-len(payload) % 4)
+        at = len(payload)
+        if isinstance(cube, _EquirectCube):
+            payload += cube.data
+        elif isinstance(cube, _EncodedCube):
+            for levels in cube.faces:
+                for level in levels:
+                    payload += level
+        else:
+            payload += cube[0].tobytes()
+        return at
+
     def _flush_cubes_sources(self):
         """the whole array through r3n_texture_cubes_write_sources: stored cubes LayerMajor, panoramas as one level"""
         src = (_ffi.CubeSource * max(len(self.cubes), 1))()
         payload = bytearray()
         for i, cube in enumerate(self.cubes):
-            payload += bytes(-len(payload) % 4)
+            at = self._pack_cube(payload, cube)
             if isinstance(cube, _EquirectCube):
-                src[i] = _ffi.CubeSource(_ffi.CUBE_SOURCE_EQUIRECT, cube.fmt, cube.src_width, cube.src_height, cube.width, cube.mips, len(payload))
-                payload += cube.data
+                src[i] = _ffi.CubeSource(_ffi.CUBE_SOURCE_EQUIRECT, cube.fmt, cube.src_width, cube.src_height, cube.width, cube.mips, at)
             elif isinstance(cube, _EncodedCube):
-                src[i] = _ffi.CubeSource(_ffi.CUBE_SOURCE_CUBE, cube.fmt, cube.width, cube.width, cube.width, cube.mips, len(payload))
-                for levels in cube.faces:
-                    for level in levels:
-                        payload += level
+                src[i] = _ffi.CubeSource(_ffi.CUBE_SOURCE_CUBE, cube.fmt, cube.width, cube.width, cube.width, cube.mips, at)
             else:
                 faces, srgb = cube
-                src[i] = _ffi.CubeSource(_ffi.CUBE_SOURCE_CUBE, 1 if srgb else 0, faces.shape[2], faces.shape[1], faces.shape[1], 1, len(payload))
-                payload += faces.tobytes()
+                src[i] = _ffi.CubeSource(_ffi.CUBE_SOURCE_CUBE, 1 if srgb else 0, faces.shape[2], faces.shape[1], faces.shape[1], 1, at)
         data = np.frombuffer(bytes(payload) + bytes(4), dtype=np.uint8)
         self._check(self.lib.r3n_texture_cubes_write_sources(self.ctx, ctypes.addressof(src), len(self.cubes), _ffi.ptr(data), len(payload)),
                     "r3n_texture_cubes_write_sources")
@@ -1275,16 +1286,12 @@ class Renderer:
         descs = np.zeros((max(len(self.cubes), 1), 8), dtype=np.uint32)
         payload = bytearray()
         for i, cube in enumerate(self.cubes):
-            payload += bytes(-len(payload) % 4)
+            at = self._pack_cube(payload, cube)
             if isinstance(cube, _EncodedCube):
-                descs[i, :5] = (len(payload), cube.width, cube.width, cube.mips, cube.fmt)
-                for levels in cube.faces:
-                    for level in levels:
-                        payload += level
+                descs[i, :5] = (at, cube.width, cube.width, cube.mips, cube.fmt)
             else:
                 faces, srgb = cube
-                descs[i, :5] = (len(payload), faces.shape[2], faces.shape[1], 1, 1 if srgb else 0)
-                payload += faces.tobytes()
+                descs[i, :5] = (at, faces.shape[2], faces.shape[1], 1, 1 if srgb else 0)
         data = np.frombuffer(bytes(payload) + bytes(4), dtype=np.uint8)
         self._check(self.lib.r3n_texture_cubes_write_encoded(self.ctx, _ffi.ptr(descs), len(self.cubes), _ffi.ptr(data), len(payload)),
                     "r3n_texture_cubes_write_encoded")

@@ -10,6 +10,7 @@ import os
 import numpy as np
 import pytest
 
+import cube_refusals
 import equirect_reference as Q
 import skybox_lod_cases as cases
 import skybox_lod_reference as lodref
@@ -260,34 +261,22 @@ def test_refusals_leave_everything_unchanged(r3):
     base = p.render(w, h)
     kept = [(0, 0), (0, 2), (1, 0), (1, 3)]
     before = [p.readback_cube_face(ci, k, 3).copy() for ci, k in kept]
-    payload = np.zeros(4096, dtype=np.uint8)
+    payload = np.zeros(cube_refusals.PAYLOAD_BYTES, dtype=np.uint8)
 
     def write(kind=1, fmt=RGBE8, width=8, height=4, extent=4, mips=1, offset=0, payload_bytes=len(payload), n=1, null=False):
         src = (_ffi.CubeSource * n)(*[_ffi.CubeSource(kind, fmt, width, height, extent, mips, offset)] * n)
         return lib.r3n_texture_cubes_write_sources(ctx, None if null else ctypes.addressof(src), n, _ffi.ptr(payload), payload_bytes)
 
-    refusals = [
-        ("an unknown kind", write(kind=2), ERR_INVALID_ARG),
-        ("an unknown format", write(fmt=C.FORMAT_COUNT), ERR_INVALID_ARG),
-        ("an unknown encoding", write(fmt=RGBE8 + 1), ERR_INVALID_ARG),
-        ("RGBE8 is no format of stored faces", write(kind=0, width=4, height=4), ERR_INVALID_ARG),
-        ("zero width", write(width=0), ERR_INVALID_ARG),
-        ("zero height", write(height=0), ERR_INVALID_ARG),
-        ("zero face extent", write(extent=0), ERR_INVALID_ARG),
-        ("a source extent above 65535", write(width=65536, height=1, payload_bytes=1 << 40), ERR_INVALID_ARG),
-        ("a face extent above 16384", write(extent=16385), ERR_INVALID_ARG),
-        ("more mips than N has", write(extent=4, mips=4), ERR_INVALID_ARG),
-        ("no mips", write(mips=0), ERR_INVALID_ARG),
-        ("data outside the payload", write(payload_bytes=8 * 4 * 4 - 1), ERR_INVALID_ARG),
-        ("an offset outside the payload", write(offset=1 << 33), ERR_INVALID_ARG),
-        ("a decoded source outside the payload", write(fmt=C.BC6H_UF, width=9, height=5, payload_bytes=6 * 16 - 1), ERR_INVALID_ARG),
-        ("a misaligned offset", write(offset=2), ERR_INVALID_ARG),
-        ("stored faces that are not square", write(kind=0, fmt=C.RGBA8, width=4, height=2), ERR_INVALID_ARG),
-        ("stored faces of another extent", write(kind=0, fmt=C.RGBA8, width=4, height=4, extent=2), ERR_INVALID_ARG),
-        ("a pool past 2^32 words", write(extent=16384), ERR_CAPACITY),
-        ("a pool past 2^32 words, four cubes", write(extent=8192, n=4), ERR_CAPACITY),
-        ("null", write(null=True), ERR_INVALID_ARG),
-    ]
+    # the rows of tests/cube_refusals.py, which tests/test_cube_plan.py sends to the planner on the CPU: code AND message
+    refusals = []
+    for row in cube_refusals.SOURCES:
+        cubes = cube_refusals.source_cubes(row)
+        src = (_ffi.CubeSource * len(cubes))(*[_ffi.CubeSource(*cube) for cube in cubes])
+        code = lib.r3n_texture_cubes_write_sources(ctx, ctypes.addressof(src), len(cubes), _ffi.ptr(payload), row[2])
+        assert lib.r3n_last_error(ctx).decode() == "texture cubes write (sources): " + row[4], row[0]
+        refusals.append((row[0], code, row[3]))
+    refusals.append(("null", write(null=True), ERR_INVALID_ARG))
+    assert len(refusals) >= 20
     for what, code, want in refusals:
         assert code == want, f"{what}: {code}"
     assert all(np.array_equal(words(x), words(p.readback_cube_face(ci, k, 3))) for x, (ci, k) in zip(before, kept))

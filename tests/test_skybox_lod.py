@@ -236,7 +236,11 @@ def test_abi_tables_name_the_new_entries():
 SRC = os.path.join(HERE, "cube_faces_check.cpp")
 HEADER = os.path.join(ROOT, "rend3_amd", "csrc", "cube_faces.h")
 OUT = os.path.join(HERE, "_build", "cube_faces_check")
-EXTENTS = (1, 2, 3, 5, 8)
+# Every entry's borders come from this table (k_cube_assemble), so this comparison is the one tie between it and resolve_texel:
+# every extent a test sends through the plain entry -- 4 (test_skybox.py's constant cubes, the viewer's PNG faces,
+# test_equirect_gpu.py, test_resources_gpu.py), 1, 2, 7, 8, 16, 64 (test_skybox.py), 7, 2 and 1, 3, 4, 5 (test_skybox_lod_gpu.py)
+# -- beside the smallest ones and one above 64 that is no power of two
+EXTENTS = (1, 2, 3, 4, 5, 7, 8, 16, 64, 100)
 
 
 def expected_sources(n):

@@ -7,6 +7,7 @@ the sampler are shared with, and proven by, tests/test_skybox_lod.py."""
 import numpy as np
 import pytest
 
+import cube_refusals
 import scenes
 import skybox_lod_cases as cases
 import skybox_lod_reference as lodref
@@ -193,7 +194,58 @@ def test_one_level_rgba8_cube_through_either_entry(r3):
     b.close()
 
 
+def test_plain_entry_word_for_word(r3):
+    """r3n_texture_cubes_write is the encoded entry's path: cubes of N = 1, 3, 4, 5 in ONE call (the second sRGB), every bordered
+    face word for word -- the interior, all four edges from resolve_texel, zero corners.  N = 1 makes every border texel another
+    face's only texel; the odd extents in front of other cubes need the 4-word padding of levels and cubes.  Two launches: one
+    decode family and the assemble."""
+    import ctypes
+    rng = np.random.default_rng(21)
+    p = r3.Renderer(oh.LEFT, f32(1.0))
+    cubes = [(rng.integers(0, 256, (6, n, n, 4), dtype=np.uint8), srgb) for n, srgb in ((1, False), (3, True), (4, False), (5, False))]
+    for ci, (faces, srgb) in enumerate(cubes):
+        assert p.add_texture_cube(faces, srgb=srgb) == ci
+    for ci, (faces, srgb) in enumerate(cubes):
+        for f in range(6):
+            got = p.readback_cube_face(ci, 0, f)
+            want, corner = lodref.bordered_face(faces, f)
+            want = np.ascontiguousarray(want).view(np.uint32)[..., 0]
+            assert got.dtype == np.uint32 and got.shape == corner.shape
+            bad = (got != want) & ~corner
+            assert not bad.any(), f"N {faces.shape[1]} face {f}: {bad.sum()} texels differ, first {np.argwhere(bad)[0]}"
+            assert not got[corner].any(), "corner words are written as zero"
+        out, cls = np.zeros(4 * (faces.shape[1] + 2) ** 2, dtype=np.uint32), np.zeros(1, dtype=np.uint32)
+        assert p.lib.r3n_readback_cube_face(p.ctx, ci, 0, 0, r3._ffi.ptr(out), out.size, r3._ffi.ptr(cls)) == 0 and cls[0] == (1 if srgb else 0)
+    fn = p.lib.r3n_internal_cube_source_launches  # an internal entry point: not in include/r3n.h, so it carries no signature
+    fn.argtypes, fn.restype = [ctypes.c_void_p], ctypes.c_uint64
+    assert int(fn(p.ctx)) == 2
+    p.close()
+
+
 # ------------------------------------------------------------------ 5. refusals and state
+def test_plain_entry_refuses_a_pool_past_2_32_words(r3):
+    """three 16384^2 cubes through r3n_texture_cubes_write: 6 * 16386^2 words each, the third passes 2^32 -> R3N_ERR_CAPACITY before
+    anything is read (n_texels claims room the small buffer does not have) or changed: the array, the binding, the next frame"""
+    from rend3_amd import _ffi
+    w, h = 16, 12
+    p = r3.Renderer(oh.LEFT, f32(w) / f32(h))
+    p.set_camera_data(oh.look_at_lh((0, 0, 0), (-1.0, 1.0, -1.0), (0, 1, 0)), ("perspective", 100.0, 0.1))
+    rng = np.random.default_rng(22)
+    p.add_texture_cube(rng.integers(0, 256, (6, 3, 3, 4), dtype=np.uint8), srgb=False)
+    p.set_background_texture(p.add_texture_cube(rng.integers(0, 256, (6, 4, 4, 4), dtype=np.uint8), srgb=True))
+    base = p.render(w, h)
+    words = [p.readback_cube_face(ci, 0, f).copy() for ci, f in ((0, 0), (0, 5), (1, 2))]
+    texels = np.zeros(1024, dtype=np.uint32)
+    desc = np.array([[0, 16384, 16384, 1, C.RGBA8, 0, 0, 0]] * 3, dtype=np.uint32)
+    assert p.lib.r3n_texture_cubes_write(p.ctx, _ffi.ptr(desc), 3, _ffi.ptr(texels), 1 << 40) == ERR_CAPACITY
+    assert p.lib.r3n_last_error(p.ctx).decode() == "texture cubes write: the cube pool exceeds 2^32 words"
+    assert all(np.array_equal(a, p.readback_cube_face(ci, 0, f)) for a, (ci, f) in zip(words, ((0, 0), (0, 5), (1, 2))))
+    after = p.render(w, h)
+    assert np.array_equal(base["hdr16"], after["hdr16"]) and np.array_equal(base["rgba8"], after["rgba8"])
+    assert len(np.unique(base["hdr16"].reshape(-1, 4), axis=0)) > 4, "the frame shows the bound cube"
+    p.close()
+
+
 def test_refusals_leave_everything_unchanged(r3):
     from rend3_amd import _ffi
     from rend3_amd.renderer import BaseRenderGraph, BaseRenderGraphInputs, BaseRenderGraphSettings, RenderGraph
@@ -208,28 +260,21 @@ def test_refusals_leave_everything_unchanged(r3):
     base = p.render(w, h)
     words = [p.readback_cube_face(ci, k, 3).copy() for ci, k in ((0, 0), (0, 3), (1, 2))]
 
-    payload = np.zeros(4096, dtype=np.uint8)
+    payload = np.zeros(cube_refusals.PAYLOAD_BYTES, dtype=np.uint8)
 
     def write(width, height, mips, fmt, offset=0, stored=0, payload_bytes=len(payload), n=1):
         desc = np.array([[offset, width, height, mips, fmt, stored, 0, 0]] * n, dtype=np.uint32)
         return lib.r3n_texture_cubes_write_encoded(ctx, _ffi.ptr(desc), n, _ffi.ptr(payload), payload_bytes)
 
-    refusals = [
-        ("not square", write(4, 2, 1, C.RGBA8), ERR_INVALID_ARG),
-        ("extent 0", write(0, 0, 1, C.RGBA8), ERR_INVALID_ARG),
-        ("extent past 16384", write(16385, 16385, 1, C.R8, payload_bytes=1 << 40), ERR_INVALID_ARG),
-        ("more mips than the extent has", write(4, 4, 4, C.RGBA8), ERR_INVALID_ARG),
-        ("no mips", write(4, 4, 0, C.RGBA8), ERR_INVALID_ARG),
-        ("a face outside the payload", write(4, 4, 1, C.RGBA8, payload_bytes=6 * 64 - 1), ERR_INVALID_ARG),
-        ("the chain outside the payload", write(4, 4, 3, C.BC1, payload_bytes=6 * 24 - 1), ERR_INVALID_ARG),
-        ("a misaligned offset", write(4, 4, 1, C.RGBA8, offset=2), ERR_INVALID_ARG),
-        ("an unknown format", write(4, 4, 1, C.FORMAT_COUNT), ERR_INVALID_ARG),
-        ("a generated chain", write(4, 4, 3, C.RGBA8, stored=1), ERR_UNSUPPORTED),
-        ("stored beyond mips", write(4, 4, 2, C.RGBA8, stored=3), ERR_UNSUPPORTED),
-        ("a pool past 2^32 words", write(16384, 16384, 1, C.R8_SNORM, payload_bytes=1 << 40), ERR_CAPACITY),
-        ("a pool past 2^32 words, three cubes", write(16384, 16384, 1, C.R8, payload_bytes=1 << 40, n=3), ERR_CAPACITY),
-        ("null", lib.r3n_texture_cubes_write_encoded(ctx, None, 1, _ffi.ptr(payload), 16), ERR_INVALID_ARG),
-    ]
+    # the rows of tests/cube_refusals.py, which tests/test_cube_plan.py sends to the planner on the CPU: code AND message
+    refusals = []
+    for row in cube_refusals.ENCODED:
+        desc = np.array(cube_refusals.encoded_cubes(row), dtype=np.uint32)
+        code = lib.r3n_texture_cubes_write_encoded(ctx, _ffi.ptr(desc), len(desc), _ffi.ptr(payload), row[2])
+        assert lib.r3n_last_error(ctx).decode() == "texture cubes write (encoded): " + row[4], row[0]
+        refusals.append((row[0], code, row[3]))
+    refusals.append(("null", lib.r3n_texture_cubes_write_encoded(ctx, None, 1, _ffi.ptr(payload), 16), ERR_INVALID_ARG))
+    assert len(refusals) >= 14
     # (a job family past 2^31 wave slots cannot be reached: a wave slot takes 64 texels or blocks and the pool's 2^32 words hold at
     # most 2^26 wave slots of them -- the pool is refused first; the check stands for a change of either constant)
     for what, code, want in refusals:

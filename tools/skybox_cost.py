@@ -18,7 +18,10 @@ is on every pixel; the `skybox` stage of
 each in --runs fresh processes, the median stage time per process (the camera's field of view is 60 degrees, which magnifies such a
 cube: every pixel stays on level 0, so cases 2 and 3 show the cost of selecting the level, not of fetching two).  With --parent-tree DIR (a checkout of the parent commit with its
 library built) case 1 alternates between the two trees, so that both spreads come from one session.  Then the host time of ONE
-r3n_texture_cubes_write_encoded call for case 3, in five fresh contexts.
+r3n_texture_cubes_write_encoded call for case 3 and of ONE r3n_texture_cubes_write call for case 1, each in five fresh contexts
+(both entries decode on the device and border the faces with k_cube_assemble; a parent commit that still built the plain entry's
+borders on the host is measured beside it: with --parent-tree the plain call is timed in this tree, then in the parent's, in the same
+session).
        python tools/skybox_cost.py --mips [--runs 5] [--parent-tree DIR] [--out FILE]"""
 import argparse
 import json
@@ -151,22 +154,28 @@ def child_stage(case, frames, warmup):
     print("RESULT " + json.dumps(out))
 
 
-def child_upload(contexts=5, n=1024):
-    """the host time of one r3n_texture_cubes_write_encoded call for case 3, a fresh context each"""
-    faces = bc6h_chain(n)
-    payload = np.frombuffer(b"".join(b"".join(levels) for levels in faces), dtype=np.uint8)
-    desc = np.array([[0, n, n, n.bit_length(), BC6H_UF, 0, 0, 0]], dtype=np.uint32)
+def child_upload(entry, contexts=5, n=1024):
+    """the host time of one upload call, a fresh context each: "encoded" = r3n_texture_cubes_write_encoded for case 3, "plain" =
+    r3n_texture_cubes_write for case 1"""
+    if entry == "plain":
+        payload = np.ascontiguousarray(sky_cube(n)).reshape(-1).view(np.uint32)
+        desc = np.array([[0, n, n, 1, RGBA8_SRGB, 0, 0, 0]], dtype=np.uint32)
+    else:
+        faces = bc6h_chain(n)
+        payload = np.frombuffer(b"".join(b"".join(levels) for levels in faces), dtype=np.uint8)
+        desc = np.array([[0, n, n, n.bit_length(), BC6H_UF, 0, 0, 0]], dtype=np.uint32)
+    write = r3._ffi.lib().r3n_texture_cubes_write if entry == "plain" else r3._ffi.lib().r3n_texture_cubes_write_encoded
     ms = []
     for _ in range(contexts):
         r = r3.Renderer(r3.host.RIGHT, np.float32(W / H))
         r.sync()
         t0 = time.perf_counter()
-        code = r.lib.r3n_texture_cubes_write_encoded(r.ctx, r3._ffi.ptr(desc), 1, r3._ffi.ptr(payload), payload.size)
+        code = write(r.ctx, r3._ffi.ptr(desc), 1, r3._ffi.ptr(payload), payload.size)  # (payload.size: texels there, bytes here)
         ms.append(1e3 * (time.perf_counter() - t0))
         assert code == 0
         copy_gbs = r.hbm_copy_rate()
         r.close()
-    print("RESULT " + json.dumps({"ms": ms, "payload_bytes": int(payload.size), "copy_gbs": copy_gbs}))
+    print("RESULT " + json.dumps({"ms": ms, "payload_bytes": int(payload.nbytes), "copy_gbs": copy_gbs}))
 
 
 def run_child(args, tree=None):
@@ -201,9 +210,16 @@ def mips_report(args):
     for case, name in ((2, "case 2, sRGB cube, full chain"), (3, "case 3, BC6H cube, full chain")):
         child[1] = str(case)
         row(name, [run_child(child) for _ in range(args.runs)])
-    up = run_child(["--child-upload"])
-    lines.append(f"  r3n_texture_cubes_write_encoded, case 3 ({up['payload_bytes'] / 1e6:.1f} MB payload), five fresh contexts: "
-                 f"median {np.median(up['ms']):.2f} ms  ({' '.join(f'{x:.2f}' for x in up['ms'])}); copy rate {up['copy_gbs']:.0f} GB/s")
+    def upload_row(name, up):
+        lines.append(f"  {name} ({up['payload_bytes'] / 1e6:.1f} MB payload), five fresh contexts: median {np.median(up['ms']):.2f} ms  "
+                     f"min {min(up['ms']):.2f}  max {max(up['ms']):.2f}  ({' '.join(f'{x:.2f}' for x in up['ms'])}); copy rate {up['copy_gbs']:.0f} GB/s")
+
+    upload_row("r3n_texture_cubes_write_encoded, case 3", run_child(["--child-upload", "encoded"]))
+    this_up = run_child(["--child-upload", "plain"])
+    parent_up = run_child(["--child-upload", "plain"], args.parent_tree) if args.parent_tree else None
+    upload_row("r3n_texture_cubes_write, case 1, this tree", this_up)
+    if parent_up:
+        upload_row("r3n_texture_cubes_write, case 1, parent commit", parent_up)
     text = "\n".join(lines) + "\n"
     print(text, end="")
     if args.out:
@@ -221,12 +237,12 @@ def main():
     ap.add_argument("--parent-tree", default=None, help="--mips: a checkout of the parent commit, its library built; measured on case 1 in alternation")
     ap.add_argument("--tree", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--child-stage", type=int, default=None, help=argparse.SUPPRESS)
-    ap.add_argument("--child-upload", action="store_true", help=argparse.SUPPRESS)
+    ap.add_argument("--child-upload", choices=("encoded", "plain"), default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.child_stage is not None:
         return child_stage(args.child_stage, args.frames, args.warmup)
     if args.child_upload:
-        return child_upload()
+        return child_upload(args.child_upload)
     if args.mips:
         return mips_report(args)
     lines = [f"tools/skybox_cost.py: bistro_like at {W}x{H}, 1024^2 Rgba8UnormSrgb cube"]
