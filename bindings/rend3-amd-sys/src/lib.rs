@@ -72,6 +72,7 @@ pub const R3N_PROBE_FORM_COUNT: i32 = 8;
 pub const R3N_CUBE_SOURCE_CUBE: u32 = 0;
 pub const R3N_CUBE_SOURCE_EQUIRECT: u32 = 1;
 pub const R3N_CUBE_ENCODING_RGBE8: u32 = 0x100;
+pub const R3N_ENV_MAX_LIGHTS: u32 = 16;
 pub const R3N_OUTPUT_RGBA8_UNORM_SRGB: u32 = 0;
 pub const R3N_OUTPUT_BGRA8_UNORM_SRGB: u32 = 1;
 pub const R3N_OUTPUT_RGBA8_UNORM: u32 = 2;
@@ -467,6 +468,52 @@ pub struct r3n_cube_source {
 
 #[repr(C)]
 #[derive(Clone, Copy)]
+pub struct r3n_env_lights_params {
+    pub cube: u32,
+    pub level: u32,
+    pub max_lights: u32,
+    pub cone_cos: f32,
+    pub min_share: f32,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct r3n_env_sums {
+    pub q: [u64; 3],
+    pub qy: u64,
+    pub qw: u64,
+    pub texels: u64,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct r3n_env_light {
+    pub direction: [f32; 3],
+    pub solid_angle: f32,
+    pub irradiance: [f32; 3],
+    pub texels: u32,
+    pub seed: u32,
+    pub _pad: [u32; 3],
+    pub shift: [[i64; 6]; 2],
+    pub sums: r3n_env_sums,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct r3n_env_lights_result {
+    pub n_lights: u32,
+    pub scale_exp: i32,
+    pub extent: u32,
+    pub emax_bits: u32,
+    pub ambient: [f32; 4],
+    pub total: r3n_env_sums,
+    pub remainder: r3n_env_sums,
+    pub seeds: [u64; 17],
+    pub lights: [r3n_env_light; 16],
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
 pub struct r3n_tonemap_opts {
     pub op: u32,
     pub exposure_mode: u32,
@@ -628,6 +675,7 @@ extern "C" {
     pub fn r3n_texture_cubes_write_encoded(ctx: *mut r3n_ctx, descs: *const r3n_texture_desc32, n_cubes: u32, payload: *const c_void, payload_bytes: u64) -> c_int;
     pub fn r3n_texture_cubes_write_sources(ctx: *mut r3n_ctx, sources: *const r3n_cube_source, n_cubes: u32, payload: *const c_void, payload_bytes: u64) -> c_int;
     pub fn r3n_skybox_set(ctx: *mut r3n_ctx, cube_id: u32) -> c_int;
+    pub fn r3n_environment_lights(ctx: *mut r3n_ctx, params: *const r3n_env_lights_params, out: *mut r3n_env_lights_result) -> c_int;
     pub fn r3n_blend_order_write(ctx: *mut r3n_ctx, objects_back_to_front: *const u32, n: u32) -> c_int;
     pub fn r3n_blend_objects_write(ctx: *mut r3n_ctx, slots: *const u32, locations: *const f32, n: u32) -> c_int;
     pub fn r3n_blend_sort(ctx: *mut r3n_ctx, camera_location: *const f32) -> c_int;

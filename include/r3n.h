@@ -585,6 +585,55 @@ int r3n_texture_cubes_write_sources(r3n_ctx *ctx, const r3n_cube_source *sources
 /*      SkyboxRoutine::set_background_texture (rend3-routine/src/skybox.rs): cube_id 0 = no skybox, i + 1 = cube i of the array
  *      above; an id past the array -> R3N_ERR_INVALID_ARG.  Between frames only (R3N_ERR_STATE inside one). */
 int r3n_skybox_set(r3n_ctx *ctx, uint32_t cube_id);
+/*      Environment lights: reads directional lights and an ambient term out of ONE level of ONE cube of the array above, on the
+ *      device.  Not in the reference: rend3-routine/src/skybox.rs only draws the cube, and its lights are whatever the caller
+ *      adds by hand.  Opt-in; changes nothing of the context that a frame reads.  This is light extraction, not image-based
+ *      lighting: the records are meant for r3n_lights_write (direction = -direction) and `ambient` for the frame uniforms.
+ *      The rule (DESIGN.md section 2 "Environment lights"; csrc/envlight_rule.h states it and proves its integer sums free of
+ *      overflow): every interior texel of the level has a solid angle and a unit direction; at most max_lights times the
+ *      brightest texel not yet taken seeds a cone of half-angle acos(cone_cos), the cone is moved onto the energy centroid
+ *      of its texels, twice, and the texels of the moved cone become a light -- unless they hold less than min_share of the level's
+ *      energy, which ends the search.  `ambient` is the solid-angle mean radiance of what no light took.  Every sum is an
+ *      integer sum of texel quantities quantised to 2^-scale_exp, so the result does not depend on the launch plan
+ *      (R3N_TUNE envlight_plane, envlight_blocks), word for word; a texel channel that is NaN, infinite or negative counts as 0.
+ *      `cube`, `level`: as r3n_readback_cube_face; any pool class.  No such cube or level, max_lights > R3N_ENV_MAX_LIGHTS,
+ *      cone_cos outside [0.5, 1) or NaN, min_share outside [0, 1) or NaN -> R3N_ERR_INVALID_ARG with a message that names the
+ *      field; a level of extent above 1024 -> R3N_ERR_UNSUPPORTED with a message that names the finest level the entry takes;
+ *      inside a frame -> R3N_ERR_STATE; all with nothing changed.  Synchronises, like the cube writes. */
+#define R3N_ENV_MAX_LIGHTS 16u   /* most lights of one call (no counterpart in skybox.rs) */
+typedef struct r3n_env_lights_params {   /* 20 B */
+    uint32_t cube, level, max_lights;
+    float cone_cos, min_share;
+} r3n_env_lights_params;
+typedef struct r3n_env_sums {   /* 48 B: raw integer sums over a set of texels */
+    uint64_t q[3];     /* sum of floor(channel * solid angle * 2^scale_exp) */
+    uint64_t qy;       /* sum of the energies (13933 q_r + 46871 q_g + 4732 q_b) >> 16 */
+    uint64_t qw;       /* sum of floor(solid angle * 2^44) */
+    uint64_t texels;
+} r3n_env_sums;
+typedef struct r3n_env_light {   /* 192 B */
+    float direction[3];    /* unit vector from the scene TOWARDS the light */
+    float solid_angle;     /* of the cone's texels, steradians */
+    float irradiance[3];   /* sum of radiance * solid angle over them */
+    uint32_t texels;
+    uint32_t seed;         /* linear index (face * n + j) * n + i of the seed texel */
+    uint32_t _pad[3];
+    int64_t shift[2][6];   /* the two mean-shift steps' sums of energy * direction: [c] of (qy >> 20), [3 + c] of (qy & 0xFFFFF) */
+    r3n_env_sums sums;     /* of the cone's texels */
+} r3n_env_light;
+typedef struct r3n_env_lights_result {   /* 3336 B */
+    uint32_t n_lights;
+    int32_t scale_exp;     /* the radiance sums are in units of 2^-scale_exp; 0 for a level without energy */
+    uint32_t extent;       /* of the level */
+    uint32_t emax_bits;    /* the f32 bits of the largest channel * solid angle of the level */
+    float ambient[4];      /* mean radiance of the remainder; [3] = 1 */
+    r3n_env_sums total;    /* the whole level */
+    r3n_env_sums remainder;/* what no light took: total - the lights */
+    uint64_t seeds[17];    /* the seed keys (luminance bits << 32 | ~index) found for light 0 .. 16, 0 where no search ran */
+    r3n_env_light lights[16]; /* [0, n_lights): emitted; the record behind them keeps the raw fields (seed, shift, sums) of the
+                                 candidate that was refused, everything else is 0 */
+} r3n_env_lights_result;
+int r3n_environment_lights(r3n_ctx *ctx, const r3n_env_lights_params *params, r3n_env_lights_result *out);
 /*      Draw order of the blend-key objects for the transparent pass: object slots back to front, as the CPU batcher
  *      sorts them every frame (rend3-routine/src/culling/batching.rs:146-176, Sorting::BLENDING: -distance^2 from the
  *      camera location to the object location).  Call once per frame before r3n_resolve_opaque (n may be 0). */

@@ -56,6 +56,7 @@ SIGNATURES = {
     "r3n_texture_cubes_write_encoded": (cint, [vp, vp, u32, vp, u64]),
     "r3n_texture_cubes_write_sources": (cint, [vp, vp, u32, vp, u64]),
     "r3n_skybox_set": (cint, [vp, u32]),
+    "r3n_environment_lights": (cint, [vp, vp, vp]),
     "r3n_animation_write": (cint, [vp, vp, u32, vp, u32, vp, u32, vp, u32, vp, u32, vp, u32]),
     "r3n_pose_skeletons": (cint, [vp, vp, u32]),
     "r3n_morph": (cint, [vp, vp, u32, vp, u32]),
@@ -276,6 +277,31 @@ class CubeSource(ctypes.Structure):
     _fields_ = [("kind", u32), ("format", u32), ("width", u32), ("height", u32), ("face_extent", u32), ("mips", u32), ("offset", u64)]
 
 
+ENV_MAX_LIGHTS = 16  # R3N_ENV_MAX_LIGHTS
+
+
+class EnvLightsParams(ctypes.Structure):
+    """r3n_env_lights_params"""
+    _fields_ = [("cube", u32), ("level", u32), ("max_lights", u32), ("cone_cos", cfloat), ("min_share", cfloat)]
+
+
+class EnvSums(ctypes.Structure):
+    """r3n_env_sums"""
+    _fields_ = [("q", u64 * 3), ("qy", u64), ("qw", u64), ("texels", u64)]
+
+
+class EnvLight(ctypes.Structure):
+    """r3n_env_light"""
+    _fields_ = [("direction", cfloat * 3), ("solid_angle", cfloat), ("irradiance", cfloat * 3), ("texels", u32), ("seed", u32), ("_pad", u32 * 3),
+                ("shift", ctypes.c_int64 * 6 * 2), ("sums", EnvSums)]
+
+
+class EnvLightsResult(ctypes.Structure):
+    """r3n_env_lights_result"""
+    _fields_ = [("n_lights", u32), ("scale_exp", ctypes.c_int32), ("extent", u32), ("emax_bits", u32), ("ambient", cfloat * 4),
+                ("total", EnvSums), ("remainder", EnvSums), ("seeds", u64 * (ENV_MAX_LIGHTS + 1)), ("lights", EnvLight * ENV_MAX_LIGHTS)]
+
+
 class Config(ctypes.Structure):
     """r3n_config"""
     _fields_ = [("struct_size", u32), ("max_big_items", u32), ("shade_mode", u32), ("_pad", u32), ("reserved", u64 * 2)]
@@ -285,6 +311,7 @@ class Config(ctypes.Structure):
 assert ctypes.sizeof(ShadowView272) == 272 and ctypes.sizeof(HostCamera144) == 144 and ctypes.sizeof(FrameDesc) == 152
 assert ctypes.sizeof(HostFrame) == 26712 and ctypes.sizeof(Config) == 32
 assert ctypes.sizeof(TonemapOpts) == 48 and ctypes.sizeof(ExposureState) == 1056 and ctypes.sizeof(BloomOpts) == 32
+assert ctypes.sizeof(EnvLightsParams) == 20 and ctypes.sizeof(EnvSums) == 48 and ctypes.sizeof(EnvLight) == 192 and ctypes.sizeof(EnvLightsResult) == 3336
 assert ctypes.sizeof(MeshBlock24) == 24 and ctypes.sizeof(MeshMove24) == 24 and ctypes.sizeof(MeshCounters) == 96
 
 _LIB = None

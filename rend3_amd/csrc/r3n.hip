@@ -19,6 +19,7 @@
 #include "exposure.h"
 #include "bloom.h"
 #include "equirect.h"
+#include "envlight.h"
 #include "kernels_cull.h"
 #include "kernels_raster.h"
 #define R3N_SHADE_DECL_ONLY
@@ -376,6 +377,12 @@ struct r3n_ctx {
     uint32_t equirect_tail = R3N_EQUIRECT_TAIL_DEFAULT;  // R3N_TUNE equirect_tail: a face of at most this extent builds the rest of its chain in ONE launch (0: never)
     uint64_t cube_source_launches = 0;  // kernels of the last call (r3n_internal_cube_source_launches)
     float cube_source_ms[4] = {0, 0, 0, 0};  // with r3n_timing_enable: its copies + decode jobs, k_equirect_faces, the chain, k_cube_assemble
+    // environment lights (r3n_environment_lights; envlight.h lays the scratch block out): grow-only, no frame reads or writes it
+    DeviceBuffer envlight_scratch;
+    uint32_t envlight_plane = R3N_ENVLIGHT_PLANE_DEFAULT;    // R3N_TUNE envlight_plane: 1 = quantise once into a plane and re-read it, 0 = decode the texels again in every pass
+    uint32_t envlight_blocks = R3N_ENVLIGHT_BLOCKS_DEFAULT;  // R3N_TUNE envlight_blocks: the grid of every pass (0: from the level's size)
+    uint64_t envlight_launches = 0;                          // kernels of the last call (r3n_internal_envlight_launches)
+    float envlight_ms[3] = {0, 0, 0};                        // with r3n_timing_enable: the e_max pass, the quantise pass, all light passes
 };
 
 namespace {
@@ -821,7 +828,7 @@ int read_timeline(r3n_ctx *c, float *out, int max) {
 // "key=value key=value ..." -> ctx.tune (unknown keys and out-of-range values are refused: nothing is applied then)
 int apply_tuning(r3n_ctx *c, const char *kv) {
     r3n_ctx::Tune t = c->tune;
-    uint32_t equirect_tail = c->equirect_tail;
+    uint32_t equirect_tail = c->equirect_tail, envlight_plane = c->envlight_plane, envlight_blocks = c->envlight_blocks;
     std::string text(kv ? kv : "");
     for (size_t at = 0; at < text.size();) {
         while (at < text.size() && (text[at] == ' ' || text[at] == ',')) ++at;
@@ -839,7 +846,7 @@ int apply_tuning(r3n_ctx *c, const char *kv) {
             {"resolve_lds", &t.resolve_lds, 0, 61440, 1}, {"big_grid", &t.big_grid, 256, 65536, 1},
             {"small_grid", &t.small_grid, R3N_SUBQ, 32768, R3N_SUBQ}, {"timed_pipeline", &t.timed_pipeline, 0, 1, 1},
             {"comm_serial", &t.comm_serial, 0, 1, 1}, {"shadow_occlusion", &t.shadow_occlusion, 0, 1, 1}, {"front_end_fast", &t.front_end_fast, 0, 1, 1},
-            {"bloom_tail", &t.bloom_tail, 0, 1u << 24, 1}, {"bloom_keep_down", &t.bloom_keep_down, 0, 1, 1}, {"equirect_tail", &equirect_tail, 0, equirect_rule::TAIL_CAP, 1}, {"prio_main", &t.prio_main, 0, 2, 1}, {"prio_shade", &t.prio_shade, 0, 2, 1}, {"prio_aux", &t.prio_aux, 0, 2, 1}};  // (read at r3n_create only)  // (a multiple of R3N_SUBQ: whole blocks per sub-list)
+            {"bloom_tail", &t.bloom_tail, 0, 1u << 24, 1}, {"bloom_keep_down", &t.bloom_keep_down, 0, 1, 1}, {"equirect_tail", &equirect_tail, 0, equirect_rule::TAIL_CAP, 1}, {"envlight_plane", &envlight_plane, 0, 1, 1}, {"envlight_blocks", &envlight_blocks, 0, R3N_ENVLIGHT_BLOCKS_MAX, 1}, {"prio_main", &t.prio_main, 0, 2, 1}, {"prio_shade", &t.prio_shade, 0, 2, 1}, {"prio_aux", &t.prio_aux, 0, 2, 1}};  // (read at r3n_create only)  // (a multiple of R3N_SUBQ: whole blocks per sub-list)
         bool known = false;
         for (auto &k : keys)
             if (key == k.name) {
@@ -852,6 +859,8 @@ int apply_tuning(r3n_ctx *c, const char *kv) {
     }
     c->tune = t;
     c->equirect_tail = equirect_tail;
+    c->envlight_plane = envlight_plane;
+    c->envlight_blocks = envlight_blocks;
     return R3N_OK;
 }
 
@@ -3331,6 +3340,94 @@ int r3n_skybox_set(r3n_ctx *c, uint32_t cube_id) {
     if (cube_id > c->cubes.size()) return fail(c, R3N_ERR_INVALID_ARG, "skybox_set: no such cube");
     c->sky_cube = cube_id;
     return R3N_OK;
+}
+
+// Environment lights (envlight.h, envlight_rule.h): every pass is enqueued behind the other on the main stream -- the device
+// decides from its state block whether a light's passes still have work -- and ONE read-back of that block follows; the record
+// the caller gets is derived from its raw sums here, with the rule's own functions.
+extern "C" uint64_t r3n_internal_envlight_launches(const r3n_ctx *c) { return c ? c->envlight_launches : 0; }
+// with r3n_timing_enable, the passes of the last call between device events, in ms (tools/envlight_cost.py)
+extern "C" int r3n_internal_envlight_times(const r3n_ctx *c, float out[3]) {
+    if (!c || !out) return R3N_ERR_INVALID_ARG;
+    std::memcpy(out, c->envlight_ms, sizeof c->envlight_ms);
+    return R3N_OK;
+}
+static r3n_env_sums env_sums(const envlight_rule::Sums &s) { return r3n_env_sums{{s.q[0], s.q[1], s.q[2]}, s.qy, s.qw, s.texels}; }
+
+int r3n_environment_lights(r3n_ctx *c, const r3n_env_lights_params *p, r3n_env_lights_result *out) {
+    const std::string what = "environment lights";
+    if (!c || !p || !out) return fail(c, R3N_ERR_INVALID_ARG, what + ": null");
+    if (c->in_frame) return fail(c, R3N_ERR_STATE, what + ": inside a frame");
+    if (p->cube >= c->cubes.size()) return fail(c, R3N_ERR_INVALID_ARG, what + ": cube: no such cube");
+    const r3n_ctx::Cube &cb = c->cubes[p->cube];
+    if (p->level >= cb.mips) return fail(c, R3N_ERR_INVALID_ARG, what + ": level: the cube has no such level");
+    if (p->max_lights > R3N_ENV_MAX_LIGHTS) return fail(c, R3N_ERR_INVALID_ARG, what + ": max_lights: at most 16");
+    if (!(p->cone_cos >= envlight_rule::COS_MIN && p->cone_cos < 1.0f)) return fail(c, R3N_ERR_INVALID_ARG, what + ": cone_cos: outside [0.5, 1)");
+    if (!(p->min_share >= 0.0f && p->min_share < 1.0f)) return fail(c, R3N_ERR_INVALID_ARG, what + ": min_share: outside [0, 1)");
+    const uint32_t n = cube_faces::level_extent(cb.n, p->level);
+    if (n > envlight_rule::MAX_EXTENT) {
+        uint32_t fits = p->level;
+        while (cube_faces::level_extent(cb.n, fits) > envlight_rule::MAX_EXTENT) ++fits;
+        return fail(c, R3N_ERR_UNSUPPORTED, what + ": level: extent " + std::to_string(n) + " is above 1024; the finest level this entry takes is level " + std::to_string(fits) +
+                                                (fits < cb.mips ? "" : ", which this cube does not store"));
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    const bool plane = c->envlight_plane != 0u;
+    TRY(ensure(c, c->envlight_scratch, envlight_scratch_bytes(n, plane), false, -1));
+    const uint32_t per_texel = cb.cls == 2u ? 4u : 1u;
+    const size_t texels = (size_t)6u * n * n;
+    EnvlightArgs a{};
+    a.level = c->cube_texels.as<uint32_t>() + cb.first_word + cube_faces::level_start(cb.n, p->level, per_texel);
+    a.decode = c->srgb8_decode.as<float>() + (cb.cls == 1u ? 256 : 0);
+    a.n = n;
+    a.f32_class = cb.cls == 2u ? 1u : 0u;
+    a.state = c->envlight_scratch.as<envlight_rule::State>();
+    a.plane_q = plane ? reinterpret_cast<uint4 *>(c->envlight_scratch.as<char>() + R3N_ENVLIGHT_STATE_BYTES) : nullptr;
+    a.plane_lum = plane ? reinterpret_cast<float *>(a.plane_q + texels) : nullptr;
+    a.rule = envlight_rule::Params{n, p->max_lights, p->cone_cos, envlight_rule::share_floor(p->min_share)};
+    a.blocks = envlight_grid(n, c->envlight_blocks);
+    Event taps[4];
+    hipEvent_t raw[4];
+    bool timed = c->timing;
+    for (int k = 0; k < 4 && timed; ++k) {
+        timed = taps[k].create() == hipSuccess;
+        raw[k] = taps[k];
+    }
+    uint64_t launches = 0;
+    const hipError_t e = (hipError_t)r3n_internal_envlight(&a, timed ? raw : nullptr, c->stream, &launches);
+    envlight_rule::State st;
+    hipError_t e2 = e == hipSuccess ? hipMemcpyAsync(&st, a.state, sizeof st, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
+    const hipError_t e3 = hipStreamSynchronize(c->stream);  // `st` is a local; and the call synchronises, like the cube writes
+    for (int k = 0; k < 3; ++k)
+        if (!timed || e != hipSuccess || e2 != hipSuccess || e3 != hipSuccess || hipEventElapsedTime(&c->envlight_ms[k], taps[k], taps[k + 1]) != hipSuccess) c->envlight_ms[k] = 0.0f;
+    if (e != hipSuccess) return fail(c, R3N_ERR_HIP, what + ": " + hipGetErrorString(e));
+    if (e2 != hipSuccess) return fail(c, R3N_ERR_HIP, what + ": " + hipGetErrorString(e2));
+    if (e3 != hipSuccess) return fail(c, R3N_ERR_HIP, what + ": " + hipGetErrorString(e3));
+    c->envlight_launches = launches;
+    // the record, from the raw sums
+    const envlight_rule::Outputs o = envlight_rule::outputs(st, a.rule);
+    std::memset(out, 0, sizeof *out);
+    out->n_lights = o.n_lights;
+    out->scale_exp = o.scale_exp;
+    out->extent = n;
+    out->emax_bits = st.emax_bits;
+    for (int t = 0; t < 4; ++t) out->ambient[t] = o.ambient[t];
+    out->total = env_sums(st.total);
+    out->remainder = env_sums(o.remainder);
+    for (uint32_t k = 0; k <= R3N_ENV_MAX_LIGHTS; ++k) out->seeds[k] = st.seed[k];
+    for (uint32_t k = 0; k < o.ran; ++k) {
+        r3n_env_light &l = out->lights[k];
+        l.seed = envlight_rule::seed_index(st.seed[k]);
+        std::memcpy(l.shift, st.shift[k], sizeof l.shift);
+        l.sums = env_sums(st.light[k]);
+        if (k >= o.n_lights) break;  // the candidate that was refused keeps its raw fields only
+        const envlight_rule::LightOut &lo = o.lights[k];
+        l.direction[0] = lo.direction.x; l.direction[1] = lo.direction.y; l.direction[2] = lo.direction.z;
+        l.solid_angle = lo.solid_angle;
+        for (int t = 0; t < 3; ++t) l.irradiance[t] = lo.irradiance[t];
+        l.texels = lo.texels;
+    }
+    return check_async_status(c);
 }
 
 int r3n_skybox(r3n_ctx *c) {

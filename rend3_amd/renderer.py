@@ -1219,7 +1219,9 @@ class Renderer:
     def environment_mean(self, cube):
         """The mean colour of a cube: the mean of the six 1 x 1 faces of its LAST level (r3n_readback_cube_face), which a cube with a
         full chain has box-filtered down from every texel.  It weighs every texel of a face alike: the box-filtered mean, NOT a
-        solid-angle integral (texels near a face's corners cover less of the sphere).  Needs a cube whose last level is 1 x 1."""
+        solid-angle integral (texels near a face's corners cover less of the sphere).  Needs a cube whose last level is 1 x 1.
+        environment_lights returns the solid-angle mean (its `ambient`, with max_lights = 0 the mean of the whole level), for any
+        cube and pool class."""
         self._flush_cubes()
         if not 0 <= cube < len(self.cubes):
             raise ValueError("environment_mean: no such cube")
@@ -1234,6 +1236,54 @@ class Renderer:
         for f in faces:
             total = total + f[1, 1]
         return total / np.float32(6.0)
+
+    def _cube_extent_and_mips(self, cube):
+        c = self.cubes[cube]
+        return (c.width, c.mips) if isinstance(c, (_EncodedCube, _EquirectCube)) else (c[0].shape[1], 1)
+
+    def environment_lights(self, cube, max_lights=4, cone_degrees=6.0, min_share=0.02, level=None, raw=False):
+        """Directional lights and an ambient term read out of one level of a cube on the GPU (r3n_environment_lights; DESIGN.md
+        section 2 "Environment lights"): at most max_lights (0 .. 16) times the brightest texel not yet taken seeds a cone of
+        half-angle cone_degrees (in (0, 60]), which is moved onto the energy centroid of its texels and becomes a light unless it
+        holds less than min_share (in [0, 1)) of the level's energy.  level=None: the finest level of extent <= 1024.  Returns
+        (lights, ambient): lights = [dict(direction=unit vector TOWARDS the light, irradiance=rgb, solid_angle, texels, seed)],
+        brightest seed first; ambient = float32[4], the solid-angle mean radiance of what no light took, alpha 1.  raw=True returns
+        the whole _ffi.EnvLightsResult (the integer sums included) instead.  Light extraction, not image-based lighting."""
+        self._flush_cubes()
+        if not 0 <= cube < len(self.cubes):
+            raise ValueError("environment_lights: no such cube")
+        if not 0 <= int(max_lights) <= _ffi.ENV_MAX_LIGHTS:
+            raise ValueError(f"environment_lights: max_lights is 0 .. {_ffi.ENV_MAX_LIGHTS}")
+        if not 0.0 < float(cone_degrees) <= 60.0:
+            raise ValueError("environment_lights: cone_degrees is in (0, 60]")
+        if not 0.0 <= float(min_share) < 1.0:
+            raise ValueError("environment_lights: min_share is in [0, 1)")
+        width, mips = self._cube_extent_and_mips(cube)
+        if level is None:
+            level = next((k for k in range(mips) if max(1, width >> k) <= 1024), None)
+            if level is None:
+                raise ValueError(f"environment_lights: the cube stores no level of extent <= 1024 (its last is {max(1, width >> (mips - 1))})")
+        cone_cos = min(np.float32(math.cos(math.radians(float(cone_degrees)))), np.nextafter(np.float32(1), np.float32(0)))
+        params = _ffi.EnvLightsParams(cube, int(level), int(max_lights), float(max(cone_cos, np.float32(0.5))), float(np.float32(min_share)))
+        out = _ffi.EnvLightsResult()
+        self._check(self.lib.r3n_environment_lights(self.ctx, ctypes.addressof(params), ctypes.addressof(out)), "r3n_environment_lights")
+        if raw:
+            return out
+        lights = [dict(direction=np.array(l.direction[:], dtype=np.float32), irradiance=np.array(l.irradiance[:], dtype=np.float32),
+                       solid_angle=float(l.solid_angle), texels=int(l.texels), seed=int(l.seed)) for l in out.lights[:out.n_lights]]
+        return lights, np.array(out.ambient[:], dtype=np.float32)
+
+    def add_environment_lights(self, cube, max_lights=4, cone_degrees=6.0, min_share=0.02, level=None, scale=1.0, distance=100.0, resolution=2048):
+        """environment_lights, then one add_directional_light(color=irradiance, intensity=scale, direction=-direction to the light)
+        per record.  Returns (light ids, scale * ambient): pass the second as `ambient=` to render."""
+        lights, ambient = self.environment_lights(cube, max_lights, cone_degrees, min_share, level)
+        if len(self.dir_lights) + len(lights) > 16:
+            raise ValueError(f"add_environment_lights: {len(lights)} lights on top of {len(self.dir_lights)}: a frame shades at most 16 directional lights")
+        ids = [self.add_directional_light(color=tuple(float(v) for v in l["irradiance"]), intensity=float(scale),
+                                          direction=tuple(-float(v) for v in l["direction"]), distance=distance, resolution=resolution) for l in lights]
+        scaled = ambient * np.float32(scale)
+        scaled[3] = np.float32(1.0)
+        return ids, scaled
 
     @staticmethod
     def _pack_cube(payload, cube):

@@ -71,7 +71,7 @@ def add_arguments(ap):
     ap.add_argument("--normal-y-down", action="store_true", help="NormalTextureYDirection::Down (Bistro)")
     ap.add_argument("--directional-light", type=_vec3, default=None, metavar="X,Y,Z", help="add a directional light with this direction")
     ap.add_argument("--directional-light-intensity", type=float, default=1.0)
-    ap.add_argument("--ambient", type=float, default=0.1, help="ambient light level (default 0.1)")
+    ap.add_argument("--ambient", type=float, default=None, help="ambient light level (default 0.1)")
     ap.add_argument("--scale", type=float, default=1.0, help="GltfLoadSettings::scale")
     ap.add_argument("--shadow-distance", type=float, default=100.0, help="GltfLoadSettings::directional_light_shadow_distance")
     ap.add_argument("--shadow-resolution", type=int, default=2048, help="GltfLoadSettings::directional_light_resolution (lights of the file)")
@@ -89,6 +89,14 @@ def add_arguments(ap):
     ap.add_argument("--ambient-from-skybox", type=float, default=None, metavar="SCALE",
                     help="ambient colour = SCALE x the mean colour of the panorama's cube (the box-filtered mean of its texels, not a "
                          "solid-angle integral) instead of --ambient")
+    ap.add_argument("--lights-from-skybox", type=int, default=0, metavar="N",
+                    help="read at most N (1..16) directional lights out of the skybox on the GPU (r3n_environment_lights) and add them, with "
+                         "shadows; the ambient colour becomes the solid-angle mean of the sky the lights did not take, unless --ambient or "
+                         "--ambient-from-skybox is given (light extraction, not image-based lighting; not in the reference)")
+    ap.add_argument("--skybox-light-cone", type=float, default=6.0, metavar="DEG", help="with --lights-from-skybox: half-angle of a light's cone, in (0, 60]")
+    ap.add_argument("--skybox-light-share", type=float, default=0.02, metavar="F",
+                    help="with --lights-from-skybox: a cone with less than this share of the sky's energy ends the search, in [0, 1)")
+    ap.add_argument("--skybox-light-scale", type=float, default=1.0, metavar="S", help="with --lights-from-skybox: scales the lights and their ambient")
     ap.add_argument("--blend-sort", choices=("host", "gpu"), default="host",
                     help="where the transparent pass's back-to-front order is sorted (not in the reference, whose CPU batcher sorts): "
                          "host = every frame on the CPU, gpu = r3n_blend_sort")
@@ -144,11 +152,13 @@ def settings_from(args):
     """argparse namespace (add_arguments) -> plain settings dict."""
     return dict(file=getattr(args, "scene", None) or getattr(args, "file", None), samples=args.msaa, normal_y_down=args.normal_y_down,
                 directional_light=args.directional_light, directional_light_intensity=args.directional_light_intensity,
-                ambient=args.ambient, scale=args.scale, shadow_distance=args.shadow_distance,
+                ambient=0.1 if args.ambient is None else args.ambient, ambient_given=args.ambient is not None, scale=args.scale, shadow_distance=args.shadow_distance,
                 shadow_resolution=args.shadow_resolution, enable_directional=not args.gltf_disable_directional_lights,
                 camera=args.camera or DEFAULT_CAMERA, skybox=getattr(args, "skybox", None),
                 skybox_extent=getattr(args, "skybox_extent", None), skybox_equirect=getattr(args, "skybox_equirect", None),
                 ambient_from_skybox=getattr(args, "ambient_from_skybox", None),
+                lights_from_skybox=getattr(args, "lights_from_skybox", 0), skybox_light_cone=getattr(args, "skybox_light_cone", 6.0),
+                skybox_light_share=getattr(args, "skybox_light_share", 0.02), skybox_light_scale=getattr(args, "skybox_light_scale", 1.0),
                 blend_sort=getattr(args, "blend_sort", "host"), morph_normals=getattr(args, "morph_normals", "base"),
                 build_tangents=getattr(args, "build_tangents", False), morph_tangents=getattr(args, "morph_tangents", "base"),
                 texture_upload=getattr(args, "texture_upload", "whole"), texture_compact=getattr(args, "texture_compact", None),
@@ -256,6 +266,12 @@ def build(r, hm, mk, settings):
         sky = add_skybox(r, settings["skybox_equirect"], extent=settings.get("skybox_extent"), equirect=True)
     if settings.get("ambient_from_skybox") is not None and (sky is None or not hasattr(r, "environment_mean")):
         raise ValueError("--ambient-from-skybox needs a skybox on a renderer that can read its mean")
+    n_sky_lights = int(settings.get("lights_from_skybox", 0) or 0)
+    if n_sky_lights:
+        if not 1 <= n_sky_lights <= 16:
+            raise ValueError("--lights-from-skybox: 1 .. 16 lights")
+        if sky is None or not hasattr(r, "add_environment_lights"):
+            raise ValueError("--lights-from-skybox needs a skybox on a renderer that can read lights out of it")
     if settings.get("tonemap", "blit") != "blit" or settings.get("exposure", 0.0) != 0.0 or settings.get("auto_exposure"):
         if not hasattr(r, "set_tonemapping"):  # (a renderer that only has the reference's blit fails here)
             raise ValueError("--tonemap / --exposure / --auto-exposure: this renderer has the blit alone")
@@ -313,6 +329,12 @@ def build(r, hm, mk, settings):
     r.set_camera_data(view, PROJECTION)
     a = settings["ambient"]
     ambient = (a, a, a, 1.0)
+    if n_sky_lights:  # (behind the file's and the flagged lights: the call refuses more than 16 in all)
+        _ids, rest = r.add_environment_lights(sky, max_lights=n_sky_lights, cone_degrees=settings.get("skybox_light_cone", 6.0),
+                                              min_share=settings.get("skybox_light_share", 0.02), scale=settings.get("skybox_light_scale", 1.0),
+                                              distance=settings["shadow_distance"], resolution=settings["shadow_resolution"])
+        if not settings.get("ambient_given") and settings.get("ambient_from_skybox") is None:
+            ambient = tuple(float(v) for v in rest[:3]) + (1.0,)
     if settings.get("ambient_from_skybox") is not None:
         mean = r.environment_mean(sky)
         ambient = tuple(float(settings["ambient_from_skybox"]) * float(v) for v in mean[:3]) + (1.0,)

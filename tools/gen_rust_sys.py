@@ -10,7 +10,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "r3n.h")
 OUT = os.path.join(ROOT, "bindings", "rend3-amd-sys", "src", "lib.rs")
 
-SCALARS = {"int": "c_int", "uint32_t": "u32", "uint64_t": "u64", "uint8_t": "u8", "uint16_t": "u16", "int32_t": "i32",
+SCALARS = {"int": "c_int", "uint32_t": "u32", "uint64_t": "u64", "uint8_t": "u8", "uint16_t": "u16", "int32_t": "i32", "int64_t": "i64",
            "float": "f32", "double": "f64", "r3n_camera": "u32", "char": "c_char", "void": "c_void",
            "unsigned long long": "u64", "long long": "i64", "unsigned": "u32", "unsigned int": "u32", "size_t": "usize"}
 # what a type of the generated file may be made of: anything else is a C spelling that leaked through (rustc would reject it)
