@@ -514,6 +514,42 @@ pub struct r3n_env_lights_result {
 
 #[repr(C)]
 #[derive(Clone, Copy)]
+pub struct r3n_env_prefilter_params {
+    pub cube: u32,
+    pub level: u32,
+    pub levels: u32,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct r3n_env_prefilter_result {
+    pub cube_id: u32,
+    pub extent: u32,
+    pub levels: u32,
+    pub sh_level: u32,
+    pub sh: [[f32; 4]; 9],
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct r3n_env_query32 {
+    pub dir: [f32; 3],
+    pub roughness: f32,
+    pub n: [f32; 3],
+    pub pad: f32,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct r3n_env_sample32 {
+    pub specular: [f32; 3],
+    pub irradiance: [f32; 3],
+    pub level: u32,
+    pub fraction: f32,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
 pub struct r3n_tonemap_opts {
     pub op: u32,
     pub exposure_mode: u32,
@@ -676,6 +712,9 @@ extern "C" {
     pub fn r3n_texture_cubes_write_sources(ctx: *mut r3n_ctx, sources: *const r3n_cube_source, n_cubes: u32, payload: *const c_void, payload_bytes: u64) -> c_int;
     pub fn r3n_skybox_set(ctx: *mut r3n_ctx, cube_id: u32) -> c_int;
     pub fn r3n_environment_lights(ctx: *mut r3n_ctx, params: *const r3n_env_lights_params, out: *mut r3n_env_lights_result) -> c_int;
+    pub fn r3n_environment_prefilter(ctx: *mut r3n_ctx, params: *const r3n_env_prefilter_params, out: *mut r3n_env_prefilter_result) -> c_int;
+    pub fn r3n_environment_probe(ctx: *mut r3n_ctx, cube: u32, sh: *const f32, queries: *const r3n_env_query32, n: u32, out: *mut r3n_env_sample32) -> c_int;
+    pub fn r3n_skybox_set_level(ctx: *mut r3n_ctx, level: f32) -> c_int;
     pub fn r3n_blend_order_write(ctx: *mut r3n_ctx, objects_back_to_front: *const u32, n: u32) -> c_int;
     pub fn r3n_blend_objects_write(ctx: *mut r3n_ctx, slots: *const u32, locations: *const f32, n: u32) -> c_int;
     pub fn r3n_blend_sort(ctx: *mut r3n_ctx, camera_location: *const f32) -> c_int;

@@ -634,6 +634,52 @@ typedef struct r3n_env_lights_result {   /* 3336 B */
                                  candidate that was refused, everything else is 0 */
 } r3n_env_lights_result;
 int r3n_environment_lights(r3n_ctx *ctx, const r3n_env_lights_params *params, r3n_env_lights_result *out);
+/*      Environment prefilter: builds, on the device, the two resources image-based lighting derives from an environment -- a chain
+ *      of GGX-prefiltered specular levels and nine SH coefficients of its radiance -- from the STORED levels of one cube of the
+ *      array above.  Not in the reference (rend3-routine/src/skybox.rs only draws the cube).  Opt-in.  This is still not lighting:
+ *      no frame kernel reads either resource until the resolve consumes them; today the skybox node can draw a level of the new
+ *      cube (r3n_skybox_set_level), and r3n_environment_probe evaluates the lookups a resolve will call (csrc/ibl_lookup.h).
+ *      The rule (DESIGN.md section 2 "Environment prefilter"; csrc/ibl_rule.h states it with its error bound): with S the extent of
+ *      `level` and L = `levels`, result level 0 is the decoded source level; result level k in 1 .. L - 1 (extent max(1, S >> k),
+ *      perceptual roughness k / (L - 1)) is, per texel, the GGX-weighted mean over EVERY texel of the stored level `level` + k; the
+ *      SH coefficients are taken from the first of those levels of extent <= 32 (else the last).  Every sum follows one fixed tree
+ *      (per source row, per face, the six faces), so every launch plan (R3N_TUNE ibl_tile, ibl_block) gives the same words.  A texel
+ *      channel that is NaN, infinite, negative or zero counts as 0 in every sum; level 0 is copied as it decodes.
+ *      APPENDS one f32-class cube of extent S with L levels to the cube array: existing cubes keep their ids and their words, a
+ *      bound skybox stays bound, result->cube_id is the old count (r3n_skybox_set takes cube_id + 1).  A later whole-array write
+ *      (r3n_texture_cubes_write and its siblings) replaces the array, this cube included.
+ *      Refused with nothing changed, the message naming the field: no such cube or level, levels < 2 or above
+ *      min(floor(log2 S) + 1, 16) -> R3N_ERR_INVALID_ARG; S above 256 -> R3N_ERR_UNSUPPORTED with a message that names the finest
+ *      level the entry takes (the pair loop is quadratic in the level's texels); more levels than the cube stores from `level` on
+ *      -> R3N_ERR_UNSUPPORTED (chains are never generated here); a pool beyond 2^32 words -> R3N_ERR_CAPACITY; inside a frame ->
+ *      R3N_ERR_STATE.  Synchronises; its scratch block is freed before it returns. */
+typedef struct r3n_env_prefilter_params { uint32_t cube, level, levels; } r3n_env_prefilter_params;
+typedef struct r3n_env_prefilter_result {   /* 160 B */
+    uint32_t cube_id;   /* index of the new cube in the array */
+    uint32_t extent, levels, sh_level;   /* sh_level: the source level (relative to params.level) the coefficients were taken from */
+    float sh[9][4];     /* Llm rgb in the order Y00, Y1-1, Y10, Y11, Y2-2, Y2-1, Y20, Y21, Y22; [3] = 0 */
+} r3n_env_prefilter_result;
+int r3n_environment_prefilter(r3n_ctx *ctx, const r3n_env_prefilter_params *params, r3n_env_prefilter_result *out);
+/*      A test and diagnostic entry in the manner of r3n_sample_probe: the two lookups of csrc/ibl_lookup.h, one thread per query.
+ *      specular = ibl_specular(cube, dir, roughness): lod = roughness * (levels - 1) clamped to [0, levels - 1] (NaN gives 0), its
+ *      floor and fraction, the seamless bilinear of the skybox node on that level and the next, mixed by the fraction; `dir` need
+ *      not be normalised.  irradiance = ibl_irradiance(sh, n) = E(n) / pi of the nine coefficients.  `cube` may be any cube of the
+ *      array, of any class.  No such cube -> R3N_ERR_INVALID_ARG.  Waits for every frame in flight and for its own launch. */
+typedef struct r3n_env_query32 {
+    float dir[3], roughness;
+    float n[3], pad;
+} r3n_env_query32;
+typedef struct r3n_env_sample32 {
+    float specular[3], irradiance[3];
+    uint32_t level;     /* floor(lod) */
+    float fraction;     /* lod - level */
+} r3n_env_sample32;
+int r3n_environment_probe(r3n_ctx *ctx, uint32_t cube, const float sh[9][4], const r3n_env_query32 *queries, uint32_t n, r3n_env_sample32 *out);
+/*      Which level of the bound cube the skybox node draws.  A negative level (the default) selects the level per pixel from the
+ *      direction's screen-space differences, as ever.  level >= 0 draws the bound cube at that level, clamped to its last one:
+ *      floor(level) mixed with the next by the fraction, each filtered seamlessly -- a blurred backdrop when the cube is a
+ *      prefiltered chain.  A one-level cube ignores it.  NaN -> R3N_ERR_INVALID_ARG.  Between frames only (R3N_ERR_STATE). */
+int r3n_skybox_set_level(r3n_ctx *ctx, float level);
 /*      Draw order of the blend-key objects for the transparent pass: object slots back to front, as the CPU batcher
  *      sorts them every frame (rend3-routine/src/culling/batching.rs:146-176, Sorting::BLENDING: -distance^2 from the
  *      camera location to the object location).  Call once per frame before r3n_resolve_opaque (n may be 0). */

@@ -57,6 +57,9 @@ SIGNATURES = {
     "r3n_texture_cubes_write_sources": (cint, [vp, vp, u32, vp, u64]),
     "r3n_skybox_set": (cint, [vp, u32]),
     "r3n_environment_lights": (cint, [vp, vp, vp]),
+    "r3n_environment_prefilter": (cint, [vp, vp, vp]),
+    "r3n_environment_probe": (cint, [vp, u32, vp, vp, u32, vp]),
+    "r3n_skybox_set_level": (cint, [vp, cfloat]),
     "r3n_animation_write": (cint, [vp, vp, u32, vp, u32, vp, u32, vp, u32, vp, u32, vp, u32]),
     "r3n_pose_skeletons": (cint, [vp, vp, u32]),
     "r3n_morph": (cint, [vp, vp, u32, vp, u32]),
@@ -280,6 +283,16 @@ class CubeSource(ctypes.Structure):
 ENV_MAX_LIGHTS = 16  # R3N_ENV_MAX_LIGHTS
 
 
+class EnvPrefilterParams(ctypes.Structure):
+    """r3n_env_prefilter_params"""
+    _fields_ = [("cube", u32), ("level", u32), ("levels", u32)]
+
+
+class EnvPrefilterResult(ctypes.Structure):
+    """r3n_env_prefilter_result"""
+    _fields_ = [("cube_id", u32), ("extent", u32), ("levels", u32), ("sh_level", u32), ("sh", cfloat * 4 * 9)]
+
+
 class EnvLightsParams(ctypes.Structure):
     """r3n_env_lights_params"""
     _fields_ = [("cube", u32), ("level", u32), ("max_lights", u32), ("cone_cos", cfloat), ("min_share", cfloat)]
@@ -312,6 +325,7 @@ assert ctypes.sizeof(ShadowView272) == 272 and ctypes.sizeof(HostCamera144) == 1
 assert ctypes.sizeof(HostFrame) == 26712 and ctypes.sizeof(Config) == 32
 assert ctypes.sizeof(TonemapOpts) == 48 and ctypes.sizeof(ExposureState) == 1056 and ctypes.sizeof(BloomOpts) == 32
 assert ctypes.sizeof(EnvLightsParams) == 20 and ctypes.sizeof(EnvSums) == 48 and ctypes.sizeof(EnvLight) == 192 and ctypes.sizeof(EnvLightsResult) == 3336
+assert ctypes.sizeof(EnvPrefilterParams) == 12 and ctypes.sizeof(EnvPrefilterResult) == 160
 assert ctypes.sizeof(MeshBlock24) == 24 and ctypes.sizeof(MeshMove24) == 24 and ctypes.sizeof(MeshCounters) == 96
 
 _LIB = None

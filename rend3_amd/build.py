@@ -24,16 +24,17 @@ UNITS = {
     "r3n.hip": ["texture.h", "kernels_cull.h", "kernels_raster.h", "kernels_shade.h", "comm.h", "skybox.h", "blend_sort.h", "morph.h", "normals.h", "tangents.h",
                 "vertex_block.h", "vertex_gather.h", "exact_math.h", "texel_alloc.h", "texel_compact.h", "texel_tail.h", "texture_jobs.h", "mesh_reloc.h",
                 "hip_owned.h", "cube_faces.h", "cube_plan.h", "exposure.h", "exposure_rule.h", "bloom.h", "bloom_rule.h", "equirect.h", "equirect_rule.h",
-                "envlight.h", "envlight_rule.h"],
+                "envlight.h", "envlight_rule.h", "ibl.h", "ibl_rule.h", "ibl_lookup.h", "cube_sample.h"],
     "shade.hip": ["texture.h", "kernels_shade.h"],
     "shade_cls.hip": ["texture.h", "kernels_shade.h"],
     "shade_ms.hip": ["texture.h", "kernels_shade.h"],
     "shade_blend.hip": ["texture.h", "kernels_shade.h"],
-    "skybox.hip": ["texture.h", "kernels_shade.h", "skybox.h", "cube_faces.h", "exact_math.h"],
+    "skybox.hip": ["texture.h", "kernels_shade.h", "skybox.h", "cube_faces.h", "cube_sample.h", "exact_math.h"],
     "exposure.hip": ["texture.h", "kernels_shade.h", "exposure.h", "exposure_rule.h", "bloom_rule.h"],
     "bloom.hip": ["bloom.h", "bloom_rule.h", "exposure_rule.h"],
     "equirect.hip": ["equirect.h", "equirect_rule.h", "vertex_gather.h", "exact_math.h"],
     "envlight.hip": ["envlight.h", "envlight_rule.h", "equirect_rule.h", "exposure_rule.h"],
+    "ibl.hip": ["ibl.h", "ibl_rule.h", "ibl_lookup.h", "cube_sample.h", "cube_faces.h", "envlight_rule.h", "equirect_rule.h", "exposure_rule.h"],
     "cube_faces.hip": ["cube_faces.h", "vertex_gather.h", "exact_math.h"],
     "sampler_probe.hip": ["texture.h", "exact_math.h"],
     "blend_sort.hip": ["blend_sort.h"],

@@ -98,6 +98,17 @@ bool lay_table(WaveTable &t, const std::vector<Rec> &recs, uint32_t per_wave) {
     return true;
 }
 
+// ---- the six assemble records of ONE level of one cube: the only statement of where a level's dense faces lie in a dense block
+// (six faces `dense_face_words` apart from `dense_at`) and where its bordered faces lie in the pool (from `level_at`).  Returns the
+// words from one dense face to the next.
+inline uint64_t add_level_records(std::vector<cube_faces::Record> &recs, uint32_t nk, uint32_t per_texel, uint64_t dense_at, uint64_t level_at) {
+    const uint64_t stride = cube_faces::dense_face_words(nk, per_texel), units = (uint64_t)(nk + 2u) * (nk + 2u);
+    for (uint32_t f = 0; f < 6u; ++f)
+        recs.push_back(cube_faces::Record{nk, f, per_texel, (uint32_t)units, (uint32_t)dense_at, (uint32_t)stride,
+                                          (uint32_t)(level_at + f * cube_faces::face_words(nk, per_texel)), 0u});
+    return stride;
+}
+
 // ---- the plan of one call
 struct Launch { size_t at; vertex_block::layout layout; uint64_t waves; };  // one wave-mapped table inside eq_block, from word `at`
 struct Plan {
@@ -152,8 +163,9 @@ inline Refusal plan(const Source *sources, uint32_t n, uint64_t payload_bytes, u
         uint64_t level_at = pool_words, above_at = 0, level_byte = 0;  // level_byte: of level k inside a stored face's chain
         for (uint32_t k = 0; k < s.mips; ++k) {
             const uint32_t nk = cube_faces::level_extent(N, k);
-            const uint64_t stride = cube_faces::dense_face_words(nk, per_texel), units = (uint64_t)(nk + 2u) * (nk + 2u);
+            const uint64_t stride = cube_faces::dense_face_words(nk, per_texel);
             if (dense_words + 6u * stride > 0xFFFFFFFFull) return {R3N_ERR_CAPACITY, "the scratch block exceeds 2^32 words"};
+            add_level_records(recs, nk, per_texel, dense_words, level_at);
             for (uint32_t f = 0; f < 6u; ++f) {
                 const uint32_t dense_face = (uint32_t)(dense_words + f * stride);
                 if (!equi) {
@@ -174,8 +186,6 @@ inline Refusal plan(const Source *sources, uint32_t n, uint64_t payload_bytes, u
                 } else if (k == from + 1u) {
                     tail_recs.push_back(equirect::ChainRec{cube_faces::level_extent(N, from), nk, (uint32_t)above_at, (uint32_t)dense_words, 0u, f, s.mips - 1u - from, 0u});
                 }
-                recs.push_back(cube_faces::Record{nk, f, per_texel, (uint32_t)units, (uint32_t)dense_words, (uint32_t)stride,
-                                                  (uint32_t)(level_at + f * cube_faces::face_words(nk, per_texel)), 0u});
             }
             above_at = dense_words;
             dense_words += 6u * stride;
@@ -211,6 +221,41 @@ inline Refusal plan(const Source *sources, uint32_t n, uint64_t payload_bytes, u
     out.eq_at = align256(out.asm_at + out.assemble.block.size() * 4u);
     out.dense_at = align256(out.eq_at + out.eq_block.size() * 4u);
     out.scratch_bytes = out.dense_at + std::max<uint64_t>(dense_words, 4) * 4u;
+    return {};
+}
+
+// ---- one more cube of the f32 class behind the array's last (r3n_environment_prefilter): where it lies in the pool, the first word
+// of every level's six dense faces in a dense block of the call's own (the same dense layout as above: a level's faces back to
+// back), and the assemble table of its faces.  The existing cubes keep their words.
+struct Append {
+    Cube cube;
+    uint64_t pool_words = 0, dense_words = 0;  // the pool with the new cube; the dense block
+    std::vector<uint32_t> level_dense;         // [k]: first dense word of level k
+    WaveTable assemble;
+};
+inline uint64_t pool_end(const std::vector<Cube> &cubes) {
+    if (cubes.empty()) return 0u;
+    const Cube &last = cubes.back();
+    return last.first_word + cube_faces::cube_words(last.n, last.mips, last.cls == 2u ? 4u : 1u);
+}
+inline Refusal plan_append(const std::vector<Cube> &cubes, uint32_t N, uint32_t mips, Append &out) {
+    out = Append{};
+    constexpr uint32_t per_texel = 4u;
+    const uint64_t first = pool_end(cubes), words = cube_faces::cube_words(N, mips, per_texel);
+    if (first + words > 0xFFFFFFFFull) return {R3N_ERR_CAPACITY, "the cube pool exceeds 2^32 words"};
+    out.cube = Cube{(size_t)first, N, 0u, mips, 2u};
+    std::vector<cube_faces::Record> recs;
+    uint64_t level_at = first, dense_words = 0;
+    for (uint32_t k = 0; k < mips; ++k) {
+        const uint32_t nk = cube_faces::level_extent(N, k);
+        if (dense_words + 6u * cube_faces::dense_face_words(nk, per_texel) > 0xFFFFFFFFull) return {R3N_ERR_CAPACITY, "the scratch block exceeds 2^32 words"};
+        out.level_dense.push_back((uint32_t)dense_words);
+        dense_words += 6u * add_level_records(recs, nk, per_texel, dense_words, level_at);
+        level_at += cube_faces::level_words(nk, per_texel);
+    }
+    out.pool_words = first + words;
+    out.dense_words = dense_words;
+    if (!lay_table(out.assemble, recs, cube_faces::UNITS_PER_WAVE)) return {R3N_ERR_CAPACITY, "more than 2^31 wave slots of assemble work in one call"};
     return {};
 }
 

@@ -20,6 +20,8 @@
 #include "bloom.h"
 #include "equirect.h"
 #include "envlight.h"
+#include "ibl.h"
+#include "ibl_lookup.h"
 #include "kernels_cull.h"
 #include "kernels_raster.h"
 #define R3N_SHADE_DECL_ONLY
@@ -293,6 +295,7 @@ struct r3n_ctx {
     DeviceBuffer cube_texels;
     std::vector<Cube> cubes;
     uint32_t sky_cube = 0;            // r3n_skybox_set: 0 = none, i + 1 = cubes[i]
+    float sky_level = -1.0f;          // r3n_skybox_set_level: negative = the level follows from the footprint
     bool sky_window = false;          // between r3n_resolve_opaque and the transparent pass / tonemap: where r3n_skybox is legal
     bool resolve_on_shade = false;    // the stream this frame's resolve went to (the sky follows it there)
     uint32_t sky_samples_form = R3N_SKY_SAMPLES_ALL;  // four samples: where this frame's resolve left the per-sample colours
@@ -383,6 +386,11 @@ struct r3n_ctx {
     uint32_t envlight_blocks = R3N_ENVLIGHT_BLOCKS_DEFAULT;  // R3N_TUNE envlight_blocks: the grid of every pass (0: from the level's size)
     uint64_t envlight_launches = 0;                          // kernels of the last call (r3n_internal_envlight_launches)
     float envlight_ms[3] = {0, 0, 0};                        // with r3n_timing_enable: the e_max pass, the quantise pass, all light passes
+    // environment prefilter (r3n_environment_prefilter; ibl.h): the launch plan of the pair kernel, and what the last call cost
+    uint32_t ibl_tile = R3N_IBL_TILE_DEFAULT;    // R3N_TUNE ibl_tile: source records per LDS tile, 0 = wave-uniform loads, no LDS
+    uint32_t ibl_block = R3N_IBL_BLOCK_DEFAULT;  // R3N_TUNE ibl_block: outputs per workgroup, 64 | 128 | 256
+    uint64_t ibl_launches = 0;                   // kernels of the last call (r3n_internal_ibl_launches)
+    float ibl_ms[4] = {0, 0, 0, 0};              // with r3n_timing_enable: records + mirror, pairs, SH, assemble
 };
 
 namespace {
@@ -828,7 +836,7 @@ int read_timeline(r3n_ctx *c, float *out, int max) {
 // "key=value key=value ..." -> ctx.tune (unknown keys and out-of-range values are refused: nothing is applied then)
 int apply_tuning(r3n_ctx *c, const char *kv) {
     r3n_ctx::Tune t = c->tune;
-    uint32_t equirect_tail = c->equirect_tail, envlight_plane = c->envlight_plane, envlight_blocks = c->envlight_blocks;
+    uint32_t equirect_tail = c->equirect_tail, envlight_plane = c->envlight_plane, envlight_blocks = c->envlight_blocks, ibl_tile = c->ibl_tile, ibl_block = c->ibl_block;
     std::string text(kv ? kv : "");
     for (size_t at = 0; at < text.size();) {
         while (at < text.size() && (text[at] == ' ' || text[at] == ',')) ++at;
@@ -846,7 +854,7 @@ int apply_tuning(r3n_ctx *c, const char *kv) {
             {"resolve_lds", &t.resolve_lds, 0, 61440, 1}, {"big_grid", &t.big_grid, 256, 65536, 1},
             {"small_grid", &t.small_grid, R3N_SUBQ, 32768, R3N_SUBQ}, {"timed_pipeline", &t.timed_pipeline, 0, 1, 1},
             {"comm_serial", &t.comm_serial, 0, 1, 1}, {"shadow_occlusion", &t.shadow_occlusion, 0, 1, 1}, {"front_end_fast", &t.front_end_fast, 0, 1, 1},
-            {"bloom_tail", &t.bloom_tail, 0, 1u << 24, 1}, {"bloom_keep_down", &t.bloom_keep_down, 0, 1, 1}, {"equirect_tail", &equirect_tail, 0, equirect_rule::TAIL_CAP, 1}, {"envlight_plane", &envlight_plane, 0, 1, 1}, {"envlight_blocks", &envlight_blocks, 0, R3N_ENVLIGHT_BLOCKS_MAX, 1}, {"prio_main", &t.prio_main, 0, 2, 1}, {"prio_shade", &t.prio_shade, 0, 2, 1}, {"prio_aux", &t.prio_aux, 0, 2, 1}};  // (read at r3n_create only)  // (a multiple of R3N_SUBQ: whole blocks per sub-list)
+            {"bloom_tail", &t.bloom_tail, 0, 1u << 24, 1}, {"bloom_keep_down", &t.bloom_keep_down, 0, 1, 1}, {"equirect_tail", &equirect_tail, 0, equirect_rule::TAIL_CAP, 1}, {"envlight_plane", &envlight_plane, 0, 1, 1}, {"envlight_blocks", &envlight_blocks, 0, R3N_ENVLIGHT_BLOCKS_MAX, 1}, {"ibl_tile", &ibl_tile, 0, R3N_IBL_TILE_MAX, 1}, {"ibl_block", &ibl_block, 64, 256, 64}, {"prio_main", &t.prio_main, 0, 2, 1}, {"prio_shade", &t.prio_shade, 0, 2, 1}, {"prio_aux", &t.prio_aux, 0, 2, 1}};  // (read at r3n_create only)  // (a multiple of R3N_SUBQ: whole blocks per sub-list)
         bool known = false;
         for (auto &k : keys)
             if (key == k.name) {
@@ -857,7 +865,10 @@ int apply_tuning(r3n_ctx *c, const char *kv) {
         if (!known) return fail(c, R3N_ERR_INVALID_ARG, "tuning: unknown key " + key);
         at = end == std::string::npos ? text.size() : end;
     }
+    if (!ibl_block_valid(ibl_block)) return fail(c, R3N_ERR_INVALID_ARG, "tuning: value out of range for ibl_block");  // 64 | 128 | 256
     c->tune = t;
+    c->ibl_tile = ibl_tile;
+    c->ibl_block = ibl_block;
     c->equirect_tail = equirect_tail;
     c->envlight_plane = envlight_plane;
     c->envlight_blocks = envlight_blocks;
@@ -3430,6 +3441,151 @@ int r3n_environment_lights(r3n_ctx *c, const r3n_env_lights_params *p, r3n_env_l
     return check_async_status(c);
 }
 
+// Environment prefilter (ibl.h, ibl_rule.h): the records of the stored levels, the mirror level, ONE pair launch for every further
+// level and the SH passes go to the main stream behind one another, then k_cube_assemble borders the new cube's faces at the
+// pool's end (cube_plan::plan_append); the pool grows with its contents kept, and the array gains its cube only when all of it ran.
+extern "C" uint64_t r3n_internal_ibl_launches(const r3n_ctx *c) { return c ? c->ibl_launches : 0; }
+// with r3n_timing_enable, the phases of the last call between device events, in ms (tools/ibl_cost.py)
+extern "C" int r3n_internal_ibl_times(const r3n_ctx *c, float out[4]) {
+    if (!c || !out) return R3N_ERR_INVALID_ARG;
+    std::memcpy(out, c->ibl_ms, sizeof c->ibl_ms);
+    return R3N_OK;
+}
+extern "C" int r3n_internal_ibl_probe(const IblCube *cube, const IblSh *sh, uint32_t f32_class, const r3n_env_query32 *queries, uint32_t n,
+                                      r3n_env_sample32 *out, hipStream_t stream);
+
+int r3n_environment_prefilter(r3n_ctx *c, const r3n_env_prefilter_params *p, r3n_env_prefilter_result *out) {
+    const std::string what = "environment prefilter";
+    if (!c || !p || !out) return fail(c, R3N_ERR_INVALID_ARG, what + ": null");
+    if (c->in_frame) return fail(c, R3N_ERR_STATE, what + ": inside a frame");
+    if (p->cube >= c->cubes.size()) return fail(c, R3N_ERR_INVALID_ARG, what + ": cube: no such cube");
+    const r3n_ctx::Cube cb = c->cubes[p->cube];  // (a copy: the array grows below)
+    if (p->level >= cb.mips) return fail(c, R3N_ERR_INVALID_ARG, what + ": level: the cube has no such level");
+    const uint32_t S = cube_faces::level_extent(cb.n, p->level), L = p->levels;
+    if (S > ibl_rule::MAX_EXTENT) {
+        uint32_t fits = p->level;
+        while (cube_faces::level_extent(cb.n, fits) > ibl_rule::MAX_EXTENT) ++fits;
+        return fail(c, R3N_ERR_UNSUPPORTED, what + ": level: extent " + std::to_string(S) + " is above 256; the finest level this entry takes is level " + std::to_string(fits) +
+                                                (fits < cb.mips ? "" : ", which this cube does not store"));
+    }
+    const uint32_t by_extent = std::min(ibl_rule::levels_of(S), ibl_rule::MAX_LEVELS);
+    if (L < 2u) return fail(c, R3N_ERR_INVALID_ARG, what + ": levels: at least 2 (the mirror level and one filtered level)");
+    if (L > by_extent) return fail(c, R3N_ERR_INVALID_ARG, what + ": levels: extent " + std::to_string(S) + " has at most " + std::to_string(by_extent) + " levels");
+    if (L > cb.mips - p->level)
+        return fail(c, R3N_ERR_UNSUPPORTED, what + ": levels: the cube stores " + std::to_string(cb.mips - p->level) + " levels from level " + std::to_string(p->level) +
+                                                " on; result level k is filtered from the stored level " + std::to_string(p->level) + " + k (no chain is generated here)");
+    cube_plan::Append plan;
+    const cube_plan::Refusal refused = cube_plan::plan_append(c->cubes, S, L, plan);
+    if (refused.code != R3N_OK) return fail(c, refused.code, what + ": " + refused.why);
+    HIP_TRY(c, hipSetDevice(c->device));
+    TRY(sync_all(c));  // no frame in flight while the pool may move
+    TRY(ensure(c, c->cube_texels, plan.pool_words * 4u, true, -1));
+    // the launch plan
+    const uint32_t per_texel = cb.cls == 2u ? 4u : 1u;
+    IblArgs a{};
+    a.pool = c->cube_texels.as<uint32_t>();
+    a.decode = c->srgb8_decode.as<float>() + (cb.cls == 1u ? 256 : 0);
+    a.f32_class = cb.cls == 2u ? 1u : 0u;
+    a.L = L;
+    a.sh_k = ibl_rule::sh_level(S, L);
+    a.rec_from = a.sh_k == 0u ? 0u : 1u;
+    a.tile = c->ibl_tile;
+    a.block = c->ibl_block;
+    for (uint32_t k = 0; k < L; ++k) {
+        IblLevel &lv = a.lv[k];
+        lv.n = ibl_rule::level_extent(S, k);
+        lv.src_word = (uint32_t)(cb.first_word + cube_faces::level_start(cb.n, p->level + k, per_texel));
+        lv.dense_word = plan.level_dense[k];
+        const ibl_rule::Roughness r = ibl_rule::roughness(k, L);
+        lv.a2 = r.a2;
+        lv.oma = r.oma;
+        const uint32_t texels = 6u * lv.n * lv.n;
+        if (k >= a.rec_from) {
+            lv.rec_base = a.rec_total;
+            a.rec_total += texels;
+        }
+        if (k >= 1u) {
+            lv.first_block = a.pair_blocks;
+            a.pair_blocks += (texels + a.block - 1u) / a.block;
+        }
+    }
+    // the scratch block of the call (ibl.h lays it out)
+    const IblScratch lay = ibl_scratch(a.rec_total, plan.dense_words, a.lv[a.sh_k].n, plan.assemble.block.size());
+    DeviceBuffer scratch;
+    HIP_TRY(c, scratch.alloc(lay.bytes));
+    auto part = [&](uint64_t at) { return scratch.as<char>() + at; };
+    a.records = reinterpret_cast<IblRecord *>(part(lay.records));
+    a.dense = reinterpret_cast<uint32_t *>(part(lay.dense));
+    a.sh_rows = reinterpret_cast<float *>(part(lay.sh_rows));
+    a.sh_out = reinterpret_cast<float *>(part(lay.sh_out));
+    uint32_t *asm_dev = reinterpret_cast<uint32_t *>(part(lay.assemble));
+    Event taps[5];
+    hipEvent_t raw[5];
+    bool timed = c->timing;
+    for (int k = 0; k < 5 && timed; ++k) {
+        timed = taps[k].create() == hipSuccess;
+        raw[k] = taps[k];
+    }
+    uint64_t launches = 0;
+    float sums[27];
+    hipError_t e = hipMemcpyAsync(asm_dev, plan.assemble.block.data(), plan.assemble.block.size() * 4u, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = (hipError_t)r3n_internal_ibl(&a, timed ? raw : nullptr, c->stream, &launches);
+    if (e == hipSuccess) {
+        e = (hipError_t)r3n_internal_cube_assemble(asm_dev, plan.assemble.layout.o_first, plan.assemble.layout.o_inst, (uint32_t)plan.assemble.waves, a.dense,
+                                                   c->cube_texels.as<uint32_t>(), c->stream);
+        ++launches;
+    }
+    if (e == hipSuccess && timed) e = hipEventRecord(raw[4], c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(sums, a.sh_out, sizeof sums, hipMemcpyDeviceToHost, c->stream);
+    const hipError_t e2 = hipStreamSynchronize(c->stream);  // `sums` and the table are locals; and the call synchronises, like the cube writes
+    for (int k = 0; k < 4; ++k)
+        if (!timed || e != hipSuccess || e2 != hipSuccess || hipEventElapsedTime(&c->ibl_ms[k], taps[k], taps[k + 1]) != hipSuccess) c->ibl_ms[k] = 0.0f;
+    (void)scratch.reset();
+    if (e != hipSuccess) return fail(c, R3N_ERR_HIP, what + ": " + hipGetErrorString(e));
+    if (e2 != hipSuccess) return fail(c, R3N_ERR_HIP, what + ": " + hipGetErrorString(e2));
+    c->ibl_launches = launches;
+    c->cubes.push_back(plan.cube);
+    std::memset(out, 0, sizeof *out);
+    out->cube_id = (uint32_t)c->cubes.size() - 1u;
+    out->extent = S;
+    out->levels = L;
+    out->sh_level = a.sh_k;
+    for (int m = 0; m < 9; ++m)
+        for (int ch = 0; ch < 3; ++ch) out->sh[m][ch] = sums[3 * m + ch];
+    return check_async_status(c);
+}
+
+int r3n_environment_probe(r3n_ctx *c, uint32_t cube, const float sh[9][4], const r3n_env_query32 *queries, uint32_t n, r3n_env_sample32 *out) {
+    const std::string what = "environment probe";
+    if (!c || !sh || (n && (!queries || !out))) return fail(c, R3N_ERR_INVALID_ARG, what + ": null");
+    if (cube >= c->cubes.size()) return fail(c, R3N_ERR_INVALID_ARG, what + ": cube: no such cube");
+    if (!n) return R3N_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    TRY(sync_all(c));
+    const r3n_ctx::Cube &cb = c->cubes[cube];
+    const IblCube ic{c->cube_texels.as<uint32_t>() + cb.first_word, c->srgb8_decode.as<float>() + (cb.cls == 1u ? 256 : 0), cb.n, cb.mips};
+    IblSh is;
+    std::memcpy(is.sh, sh, sizeof is.sh);
+    DeviceBuffer dq, dr;
+    const size_t qb = (size_t)n * sizeof(r3n_env_query32), rb = (size_t)n * sizeof(r3n_env_sample32);
+    hipError_t e = dq.alloc(qb);
+    if (e == hipSuccess) e = dr.alloc(rb);
+    if (e == hipSuccess) e = hipMemcpyAsync(dq.p, queries, qb, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = (hipError_t)r3n_internal_ibl_probe(&ic, &is, cb.cls == 2u ? 1u : 0u, dq.as<const r3n_env_query32>(), n, dr.as<r3n_env_sample32>(), c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(out, dr.p, rb, hipMemcpyDeviceToHost, c->stream);
+    const hipError_t e2 = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess || e2 != hipSuccess) return fail(c, R3N_ERR_HIP, what + ": " + hipGetErrorString(e != hipSuccess ? e : e2));
+    return R3N_OK;
+}
+
+int r3n_skybox_set_level(r3n_ctx *c, float level) {
+    if (!c) return R3N_ERR_INVALID_ARG;
+    if (c->in_frame) return fail(c, R3N_ERR_STATE, "skybox_set_level: inside a frame");
+    if (!(level == level)) return fail(c, R3N_ERR_INVALID_ARG, "skybox_set_level: level: NaN");
+    c->sky_level = level < 0.0f ? -1.0f : level;
+    return R3N_OK;
+}
+
 int r3n_skybox(r3n_ctx *c) {
     if (!c || !c->in_frame || !c->sky_window) return fail(c, R3N_ERR_STATE, "skybox: the node follows r3n_resolve_opaque and precedes the transparent pass and r3n_tonemap");
     if (c->sky_cube == 0u) return R3N_OK;  // `if let Some(bg)`: nothing bound, nothing drawn
@@ -3450,6 +3606,12 @@ int r3n_skybox(r3n_ctx *c) {
     a.out_bgr = (c->output_format & 1u) != 0u ? 1u : 0u;
     a.samples = c->samples == 4 ? c->samples16.as<ushort4>() : nullptr;
     a.samples_form = c->sky_samples_form;
+    if (c->sky_level >= 0.0f && cube.mips > 1u) {  // r3n_skybox_set_level; a one-level cube ignores it
+        const float top = (float)(cube.mips - 1u), lod = c->sky_level > top ? top : c->sky_level;
+        a.fixed = 1u;
+        a.fixed_level = (uint32_t)lod;
+        a.fixed_frac = lod - (float)a.fixed_level;
+    }
     if (c->samples == 4 && !a.samples) return fail(c, R3N_ERR_STATE, "skybox: the resolve kept no samples");
     // the stream the resolve went to: its own while frames are in flight and no transparent pass follows, else the main stream
     hipStream_t stream = c->resolve_on_shade ? c->shade : c->stream;

@@ -37,6 +37,10 @@ struct SkyboxArgs {
     ushort4 *samples;
     uint32_t samples_form;
     uint32_t mips;                     // levels of the bound cube (read by the instantiations with level selection only)
+    // r3n_skybox_set_level: fixed != 0 draws a cube with levels at fixed_level (<= mips - 1) mixed with the next by fixed_frac (0 on
+    // the last level) instead of selecting the level per pixel; read by the FIXED instantiations only
+    uint32_t fixed, fixed_level;
+    float fixed_frac;
 };
 #define R3N_SKY_SAMPLES_ALL 0u
 #define R3N_SKY_SAMPLES_EDGES 1u

@@ -9,17 +9,13 @@
 
 #include "kernels_shade.h"
 #include "cube_faces.h"
+#include "cube_sample.h"
 #include "exact_math.h"
 #include "skybox.h"
 
 namespace {
 
-// A texel of a bordered face (skybox.h), decoded BEFORE filtering.  (bx, by) in [0, N + 1]^2.  The four corner positions of the
-// bordered face have no texel: there the value is ((a + b) + c) / 3 per channel of the in-face corner texel a, its neighbour b
-// across the s edge and its neighbour c across the t edge -- both are border texels of this very face.
-R3N_DEV void sky_decode(const float *__restrict__ tab, uint32_t w, float o[3]) {
-    o[0] = tab[w & 0xFFu]; o[1] = tab[(w >> 8) & 0xFFu]; o[2] = tab[(w >> 16) & 0xFFu];
-}
+// A texel of a bordered face of RGBA8 words, corners included: cube_sample.h's sky_texel_any for the one-level RGBA8 kernel.
 R3N_DEV void sky_texel(const uint32_t *__restrict__ face, const float *__restrict__ tab, uint32_t n, uint32_t bx, uint32_t by, float o[3]) {
     const uint32_t pitch = n + 2u;
     const bool edge_x = bx == 0u || bx == n + 1u, edge_y = by == 0u || by == n + 1u;
@@ -35,14 +31,6 @@ R3N_DEV void sky_texel(const uint32_t *__restrict__ face, const float *__restric
     }
     sky_decode(tab, face[(size_t)by * pitch + bx], o);
 }
-// floor(coordinate) of the footprint's first texel -> its index in the bordered face.  s in [0, 1] gives a floor in [-1, N - 1];
-// anything else (a NaN direction) is clamped, so no fetch can leave the face's (N + 2)^2 words.
-R3N_DEV uint32_t sky_border_index(float f0, uint32_t n) {
-    int i = (f0 == f0) ? (int)fminf(fmaxf(f0, -1.0f), (float)n) : -1;
-    i = i < -1 ? -1 : (i > (int)n - 1 ? (int)n - 1 : i);
-    return (uint32_t)(i + 1);
-}
-
 // skybox.wgsl fs_main at the centre of pixel (x, y), rounded to half.
 R3N_DEV ushort4 sky_fragment(const SkyboxArgs &a, uint32_t x, uint32_t y) {
     // 1. clip position of the pixel centre
@@ -107,78 +95,14 @@ R3N_DEV void sky_direction(const SkyboxArgs &a, uint32_t x, uint32_t y, float d[
     d[0] = wu[0] / wu[3]; d[1] = wu[1] / wu[3]; d[2] = wu[2] / wu[3];
     normalize3(d);
 }
-// a row of the cube table: (sc, tc) and the signed major component m of direction e ON FACE `face` -- the face is given, not
-// selected from e
-R3N_DEV void sky_project(uint32_t face, const float e[3], float &sc, float &tc, float &m) {
-    const bool neg = (face & 1u) != 0u;
-    if (face >= 4u) { sc = neg ? -e[0] : e[0]; tc = -e[1]; m = neg ? -e[2] : e[2]; }
-    else if (face >= 2u) { sc = e[0]; tc = neg ? -e[2] : e[2]; m = neg ? -e[1] : e[1]; }
-    else { sc = neg ? e[2] : -e[2]; tc = -e[1]; m = neg ? -e[0] : e[0]; }
-}
-template <bool F32>
-R3N_DEV void sky_fetch(const uint32_t *__restrict__ face, const float *__restrict__ tab, size_t at, float o[3]) {
-    if (F32) {
-        const float4 v = reinterpret_cast<const float4 *>(face)[at];
-        o[0] = v.x; o[1] = v.y; o[2] = v.z;
-    } else {
-        sky_decode(tab, face[at], o);
-    }
-}
-template <bool F32>
-R3N_DEV void sky_texel_any(const uint32_t *__restrict__ face, const float *__restrict__ tab, uint32_t n, uint32_t bx, uint32_t by, float o[3]) {
-    const uint32_t pitch = n + 2u;
-    const bool edge_x = bx == 0u || bx == n + 1u, edge_y = by == 0u || by == n + 1u;
-    if (edge_x && edge_y) {
-        const uint32_t ix = bx == 0u ? 1u : n, iy = by == 0u ? 1u : n;
-        float a[3], b[3], c[3];
-        sky_fetch<F32>(face, tab, (size_t)iy * pitch + ix, a);
-        sky_fetch<F32>(face, tab, (size_t)iy * pitch + bx, b);
-        sky_fetch<F32>(face, tab, (size_t)by * pitch + ix, c);
-#pragma unroll
-        for (int k = 0; k < 3; ++k) o[k] = ((a[k] + b[k]) + c[k]) / 3.0f;
-        return;
-    }
-    sky_fetch<F32>(face, tab, (size_t)by * pitch + bx, o);
-}
-// step 5 on one level: the seamless bilinear of sky_fragment on the bordered face `face_texels` of extent n
-template <bool F32>
-R3N_DEV void sky_bilinear(const uint32_t *__restrict__ face_texels, const float *__restrict__ tab, uint32_t n, float s, float t, float v[3]) {
-    const float tx = s * (float)n - 0.5f, ty = t * (float)n - 0.5f;
-    const float fx0 = floorf(tx), fy0 = floorf(ty);
-    float fx = tx - fx0, fy = ty - fy0;
-    if (!(fx == fx)) fx = 0.0f;
-    if (!(fy == fy)) fy = 0.0f;
-    const uint32_t x0 = sky_border_index(fx0, n), y0 = sky_border_index(fy0, n);
-    float c00[3], c10[3], c01[3], c11[3];
-    sky_texel_any<F32>(face_texels, tab, n, x0, y0, c00);
-    sky_texel_any<F32>(face_texels, tab, n, x0 + 1u, y0, c10);
-    sky_texel_any<F32>(face_texels, tab, n, x0, y0 + 1u, c01);
-    sky_texel_any<F32>(face_texels, tab, n, x0 + 1u, y0 + 1u, c11);
-    const float omx = 1.0f - fx, omy = 1.0f - fy;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const float top = c00[k] * omx + c10[k] * fx, bot = c01[k] * omx + c11[k] * fx;
-        v[k] = top * omy + bot * fy;
-    }
-}
 template <bool F32, bool LOD>
 R3N_DEV ushort4 sky_fragment_levels(const SkyboxArgs &a, uint32_t x, uint32_t y) {
     float d[3];
     sky_direction(a, x, y, d);
     // 4. face and coordinates, as sky_fragment
-    const float ax = fabsf(d[0]), ay = fabsf(d[1]), az = fabsf(d[2]);
     uint32_t face;
     float sc, tc, ma;
-    if (az >= ax && az >= ay) {
-        const bool neg = d[2] < 0.0f;
-        face = neg ? 5u : 4u; sc = neg ? -d[0] : d[0]; tc = -d[1]; ma = az;
-    } else if (ay >= ax) {
-        const bool neg = d[1] < 0.0f;
-        face = neg ? 3u : 2u; sc = d[0]; tc = neg ? -d[2] : d[2]; ma = ay;
-    } else {
-        const bool neg = d[0] < 0.0f;
-        face = neg ? 1u : 0u; sc = neg ? d[2] : -d[2]; tc = -d[1]; ma = ax;
-    }
+    sky_select_face(d, face, sc, tc, ma);
     const float s = 0.5f * (sc / ma) + 0.5f, t = 0.5f * (tc / ma) + 0.5f;
     // the level: the gradients are the differences to the pixels (x + 1, y) and (x, y + 1), projected onto THIS face; then
     // tex_footprint's rule (texture.h) with W = H = N.  A one-level cube pays for none of it.
@@ -231,8 +155,20 @@ R3N_DEV ushort4 sky_fragment_levels(const SkyboxArgs &a, uint32_t x, uint32_t y)
     v[3] = 1.0f;  // 6.
     return pack_half4(v);
 }
-template <bool F32, bool LOD>
+// a cube with levels drawn at a GIVEN level (r3n_skybox_set_level): steps 1-4, then step 5 with the level and fraction of the
+// argument block instead of the footprint's
+template <bool F32>
+R3N_DEV ushort4 sky_fragment_fixed(const SkyboxArgs &a, uint32_t x, uint32_t y) {
+    float d[3];
+    sky_direction(a, x, y, d);
+    float v[4];
+    cube_sample_level<F32>(a.texels, a.decode + (a.srgb ? 256 : 0), a.n, a.mips, d, a.fixed_level, a.fixed_frac, v);
+    v[3] = 1.0f;
+    return pack_half4(v);
+}
+template <bool F32, bool LOD, bool FIXED>
 R3N_DEV ushort4 sky_fragment_of(const SkyboxArgs &a, uint32_t x, uint32_t y) {
+    if (FIXED) return sky_fragment_fixed<F32>(a, x, y);
     if (!F32 && !LOD) return sky_fragment(a, x, y);
     return sky_fragment_levels<F32, LOD>(a, x, y);
 }
@@ -249,8 +185,8 @@ R3N_DEV void half4_to_float(ushort4 h, float o[4]) {
 }
 
 // F32: the cube's texels are four f32 words; LOD: the cube has more than one level.  <S, false, false> is the kernel of the
-// one-level RGBA8 cubes.
-template <int S, bool F32, bool LOD>
+// one-level RGBA8 cubes.  FIXED (with LOD): the level is the argument block's, not the footprint's.
+template <int S, bool F32, bool LOD, bool FIXED = false>
 __global__ __launch_bounds__(256) void k_skybox(SkyboxArgs a) {
     const size_t i = (size_t)blockIdx.x * 256u + threadIdx.x;
     const size_t first = (size_t)a.row_begin * a.width, count = (size_t)(a.row_end - a.row_begin) * a.width;
@@ -259,7 +195,7 @@ __global__ __launch_bounds__(256) void k_skybox(SkyboxArgs a) {
     const uint32_t y = (uint32_t)pix / a.width, x = (uint32_t)pix - y * a.width;  // (a target holds fewer than 2^29 samples: r3n_frame_begin)
     if (S == 1) {
         if (!sky_passes(a.vis[pix])) return;
-        const ushort4 h = sky_fragment_of<F32, LOD>(a, x, y);
+        const ushort4 h = sky_fragment_of<F32, LOD, FIXED>(a, x, y);
         a.hdr_out[pix] = h;
         a.ldr_out[pix] = tonemap_half4(a.srgb_lut, h, a.out_bgr != 0u);
         return;
@@ -276,7 +212,7 @@ __global__ __launch_bounds__(256) void k_skybox(SkyboxArgs a) {
 #pragma unroll
     for (int sm = 0; sm < 4; ++sm) mask |= sky_passes(keys[sm]) ? 1u << sm : 0u;
     if (mask == 0u) return;
-    const ushort4 h = sky_fragment_of<F32, LOD>(a, x, y);
+    const ushort4 h = sky_fragment_of<F32, LOD, FIXED>(a, x, y);
     const bool keep_samples = a.samples_form == R3N_SKY_SAMPLES_ALL;
     float col[4][4];
     half4_to_float(h, col[0]);
@@ -328,6 +264,11 @@ __global__ __launch_bounds__(256) void k_skybox(SkyboxArgs a) {
 
 template <int S>
 static void launch_skybox(const SkyboxArgs &a, bool f32, bool lod, dim3 grid, hipStream_t stream) {
+    if (lod && a.fixed != 0u) {  // a one-level cube ignores the fixed level
+        if (f32) hipLaunchKernelGGL((k_skybox<S, true, true, true>), grid, dim3(256), 0, stream, a);
+        else hipLaunchKernelGGL((k_skybox<S, false, true, true>), grid, dim3(256), 0, stream, a);
+        return;
+    }
     if (f32 && lod) hipLaunchKernelGGL((k_skybox<S, true, true>), grid, dim3(256), 0, stream, a);
     else if (f32) hipLaunchKernelGGL((k_skybox<S, true, false>), grid, dim3(256), 0, stream, a);
     else if (lod) hipLaunchKernelGGL((k_skybox<S, false, true>), grid, dim3(256), 0, stream, a);

@@ -49,6 +49,11 @@ FLAGS_NEAREST = 0x4000
 SAMPLE_QUERY = np.dtype([("id", np.uint32, 3), ("nearest", np.uint32), ("u", f32), ("v", f32), ("ddx", f32, 2), ("ddy", f32, 2)])
 SAMPLE_RESULT = np.dtype([("rgba", f32, (3, 4)), ("flags", np.uint32)])
 assert SAMPLE_QUERY.itemsize == 40 and SAMPLE_RESULT.itemsize == 52
+# r3n_environment_probe (include/r3n.h r3n_env_query32 / r3n_env_sample32)
+ENV_QUERY = np.dtype([("dir", f32, 3), ("roughness", f32), ("n", f32, 3), ("pad", f32)])
+ENV_SAMPLE = np.dtype([("specular", f32, 3), ("irradiance", f32, 3), ("level", np.uint32), ("fraction", f32)])
+assert ENV_QUERY.itemsize == 32 and ENV_SAMPLE.itemsize == 32
+IBL_MAX_EXTENT, IBL_MAX_LEVELS = 256, 16  # csrc/ibl_rule.h
 PROBE_FORMS = ("grad", "grad_rgb", "short", "short_rgb", "share", "alpha", "alpha_short", "batched")  # index = R3N_PROBE_*
 
 
@@ -374,6 +379,7 @@ class Renderer:
         self._cubes_dirty = False
         self._background = None    # SkyboxRoutine.set_background_texture: the cube handle bound as the skybox, or None
         self._background_sent = None
+        self._skybox_level, self._skybox_level_sent = -1.0, None
         self._pose_state = {}      # skeleton handle -> (clip, time): rend3-anim poses re-evaluated in front of every skinning pass
         self._anim_sets = None     # concatenated rend3-anim tables of every AnimationData (animation_add)
         self.output_format = 0
@@ -1145,6 +1151,7 @@ class Renderer:
         faces = np.ascontiguousarray(faces, dtype=np.uint8)
         if faces.ndim != 4 or faces.shape[0] != 6 or faces.shape[3] != 4:
             raise ValueError("a cube texture is uint8[6, N, N, 4]")
+        self._drop_derived_cubes()
         self.cubes.append((faces, bool(srgb)))
         self._cubes_dirty = True
         return len(self.cubes) - 1
@@ -1179,6 +1186,7 @@ class Renderer:
                                      f"{containers.FORMAT_NAMES[fmt]} {n} x {n} takes {containers.level_bytes(fmt, n, n)}")
                 row.append(level)
             kept.append(row)
+        self._drop_derived_cubes()
         self.cubes.append(_EncodedCube(fmt, width, mips, kept))
         self._cubes_dirty = True
         return len(self.cubes) - 1
@@ -1212,6 +1220,7 @@ class Renderer:
         data = data.tobytes() if isinstance(data, np.ndarray) else bytes(data)
         if len(data) != need:
             raise ValueError(f"add_texture_cube_equirect: {len(data)} bytes, a {width} x {height} panorama of this format has {need}")
+        self._drop_derived_cubes()
         self.cubes.append(_EquirectCube(fmt, width, height, data, n, mips))
         self._cubes_dirty = True
         return len(self.cubes) - 1
@@ -1226,7 +1235,7 @@ class Renderer:
         if not 0 <= cube < len(self.cubes):
             raise ValueError("environment_mean: no such cube")
         c = self.cubes[cube]
-        width, mips = (c.width, c.mips) if isinstance(c, (_EncodedCube, _EquirectCube)) else (c[0].shape[1], 1)
+        width, mips = self._cube_extent_and_mips(cube)
         if max(1, width >> (mips - 1)) != 1:
             raise ValueError("environment_mean: the cube's last level is not 1 x 1")
         faces = [self.readback_cube_face(cube, mips - 1, f) for f in range(6)]
@@ -1239,7 +1248,73 @@ class Renderer:
 
     def _cube_extent_and_mips(self, cube):
         c = self.cubes[cube]
-        return (c.width, c.mips) if isinstance(c, (_EncodedCube, _EquirectCube)) else (c[0].shape[1], 1)
+        return (c.width, c.mips) if isinstance(c, (_EncodedCube, _EquirectCube, _DerivedCube)) else (c[0].shape[1], 1)
+
+    def _drop_derived_cubes(self):
+        """A whole-array write replaces the array, the cubes prefilter_environment appended included: they leave the host's list
+        when a cube is added (their handles die; a background bound to one is unbound, as the library does)."""
+        kept = [c for c in self.cubes if not isinstance(c, _DerivedCube)]
+        if len(kept) != len(self.cubes):
+            if self._background is not None and self._background < len(self.cubes) and isinstance(self.cubes[self._background], _DerivedCube):
+                self._background = None
+            self.cubes = kept
+            self._cubes_dirty = True
+
+    def prefilter_environment(self, cube, level=None, levels=None):
+        """The roughness-prefiltered specular chain and the SH9 irradiance of an environment, built on the GPU from the STORED levels
+        of `cube` (r3n_environment_prefilter; DESIGN.md section 2 "Environment prefilter").  level=None: the finest stored level of
+        extent <= 256; levels=None: all that fit (the stored levels from `level` on, at most floor(log2 extent) + 1 and 16).  Returns
+        (handle, sh): the handle of a NEW cube of float texels appended to the array -- level k filtered for the roughness
+        k / (levels - 1), level 0 the source itself -- and sh = float32[9, 3], the radiance coefficients L_lm.  The new cube lives
+        until the array is re-sent (any add_texture_cube*).  Not lighting yet: no frame reads it but the skybox node
+        (set_background_texture(handle), set_skybox_level)."""
+        self._flush_cubes()
+        if not 0 <= cube < len(self.cubes):
+            raise ValueError("prefilter_environment: no such cube")
+        width, mips = self._cube_extent_and_mips(cube)
+        if level is None:
+            level = next((k for k in range(mips) if max(1, width >> k) <= IBL_MAX_EXTENT), None)
+            if level is None:
+                raise ValueError(f"prefilter_environment: the cube stores no level of extent <= {IBL_MAX_EXTENT} (its last is {max(1, width >> (mips - 1))})")
+        level = int(level)
+        if not 0 <= level < mips:
+            raise ValueError("prefilter_environment: the cube has no such level")
+        extent = max(1, width >> level)
+        if levels is None:
+            levels = min(mips - level, extent.bit_length(), IBL_MAX_LEVELS)
+        params = _ffi.EnvPrefilterParams(int(cube), level, int(levels))
+        out = _ffi.EnvPrefilterResult()
+        self._check(self.lib.r3n_environment_prefilter(self.ctx, ctypes.addressof(params), ctypes.addressof(out)), "r3n_environment_prefilter")
+        self.cubes.append(_DerivedCube(int(out.extent), int(out.levels), cube, level))
+        assert int(out.cube_id) == len(self.cubes) - 1
+        sh = np.array([[out.sh[m][ch] for ch in range(3)] for m in range(9)], dtype=np.float32)
+        return len(self.cubes) - 1, sh
+
+    def environment_probe(self, cube, sh, queries):
+        """r3n_environment_probe: the lookups a resolve will call (csrc/ibl_lookup.h) on a list of queries.  sh: float32[9, 3] (or
+        [9, 4]) as prefilter_environment returns it; queries: array of ENV_QUERY (dir, roughness, n).  Returns an array of
+        ENV_SAMPLE: specular = the cube at lod = roughness * (levels - 1), irradiance = E(n) / pi, and the level and fraction."""
+        self._flush_cubes()
+        if not 0 <= cube < len(self.cubes):
+            raise ValueError("environment_probe: no such cube")
+        coeff = np.zeros((9, 4), dtype=np.float32)
+        sh = np.asarray(sh, dtype=np.float32)
+        if sh.shape not in ((9, 3), (9, 4)):
+            raise ValueError("environment_probe: sh is float32[9, 3]")
+        coeff[:, :3] = sh[:, :3]
+        q = np.ascontiguousarray(queries, dtype=ENV_QUERY)
+        out = np.zeros(len(q), dtype=ENV_SAMPLE)
+        self._check(self.lib.r3n_environment_probe(self.ctx, int(cube), _ffi.ptr(coeff), _ffi.ptr(q), len(q), _ffi.ptr(out)), "r3n_environment_probe")
+        return out
+
+    def set_skybox_level(self, level=None):
+        """Which level of the background cube the skybox node draws (r3n_skybox_set_level): None or a negative number = selected
+        per pixel, as ever; level >= 0 = that level, clamped to the cube's last, fractions mixing two levels.  A one-level cube
+        ignores it.  Sent when the next frame is evaluated."""
+        level = -1.0 if level is None else float(level)
+        if level != level:
+            raise ValueError("set_skybox_level: NaN")
+        self._skybox_level = -1.0 if level < 0 else level
 
     def environment_lights(self, cube, max_lights=4, cone_degrees=6.0, min_share=0.02, level=None, raw=False):
         """Directional lights and an ambient term read out of one level of a cube on the GPU (r3n_environment_lights; DESIGN.md
@@ -1320,6 +1395,8 @@ class Renderer:
 
     def replace_texture_cubes(self, cubes):
         """Replaces the whole cube array: `cubes` = [(faces, srgb), ...]; handles are indices into it."""
+        if self._background is not None and self._background < len(self.cubes) and isinstance(self.cubes[self._background], _DerivedCube):
+            self._background = None
         self.cubes = []
         for faces, srgb in cubes:
             self.add_texture_cube(faces, srgb)
@@ -1369,6 +1446,9 @@ class Renderer:
         if self._background_sent is None or self._background_sent[0] != self._background:
             self._check(self.lib.r3n_skybox_set(self.ctx, 0 if self._background is None else int(self._background) + 1), "r3n_skybox_set")
             self._background_sent = (self._background,)
+        if self._skybox_level_sent != self._skybox_level:
+            self._check(self.lib.r3n_skybox_set_level(self.ctx, float(self._skybox_level)), "r3n_skybox_set_level")
+            self._skybox_level_sent = self._skybox_level
 
     def add_material(self, record, key=OPAQUE):
         idx = len(self.materials)
@@ -1976,7 +2056,7 @@ class Renderer:
         if not 0 <= cube < len(self.cubes):
             raise ValueError("readback_cube_face: no such cube")
         c = self.cubes[cube]
-        width = c.width if isinstance(c, (_EncodedCube, _EquirectCube)) else c[0].shape[1]
+        width = c.width if isinstance(c, (_EncodedCube, _EquirectCube, _DerivedCube)) else c[0].shape[1]
         p = max(1, width >> level) + 2
         words = np.zeros(p * p * 4, dtype=np.uint32)
         cls = np.zeros(1, dtype=np.uint32)
@@ -2176,6 +2256,13 @@ class TonemappingRoutine:
             r._check(r.lib.r3n_tonemap(r.ctx, None, 0), "r3n_tonemap")
 
         graph.add_node("Tonemapping", body)
+
+
+class _DerivedCube:
+    """a cube prefilter_environment appended on the device: nothing of it is kept on the host"""
+
+    def __init__(self, width, mips, source, level):
+        self.width, self.mips, self.source, self.level = width, mips, source, level
 
 
 class _EncodedCube:

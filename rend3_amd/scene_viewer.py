@@ -138,6 +138,9 @@ def add_arguments(ap):
     ap.add_argument("--bloom-knee", type=float, default=0.5, metavar="K", help="with --bloom: half width of the soft knee around the threshold")
     ap.add_argument("--bloom-scatter", type=float, default=0.7, metavar="S", help="with --bloom: share of each coarser level added on the way up, in [0, 1]")
     ap.add_argument("--bloom-levels", type=int, default=8, metavar="N", help="with --bloom: most levels of the pyramid, 1..16")
+    ap.add_argument("--skybox-blur", type=float, default=None, metavar="ROUGHNESS",
+                    help="draw the skybox blurred: prefilter the environment on the GPU (r3n_environment_prefilter), bind the result and draw "
+                         "its level ROUGHNESS * (levels - 1), ROUGHNESS in [0, 1] (not in the reference)")
     return ap
 
 
@@ -159,6 +162,7 @@ def settings_from(args):
                 ambient_from_skybox=getattr(args, "ambient_from_skybox", None),
                 lights_from_skybox=getattr(args, "lights_from_skybox", 0), skybox_light_cone=getattr(args, "skybox_light_cone", 6.0),
                 skybox_light_share=getattr(args, "skybox_light_share", 0.02), skybox_light_scale=getattr(args, "skybox_light_scale", 1.0),
+                skybox_blur=getattr(args, "skybox_blur", None),
                 blend_sort=getattr(args, "blend_sort", "host"), morph_normals=getattr(args, "morph_normals", "base"),
                 build_tangents=getattr(args, "build_tangents", False), morph_tangents=getattr(args, "morph_tangents", "base"),
                 texture_upload=getattr(args, "texture_upload", "whole"), texture_compact=getattr(args, "texture_compact", None),
@@ -266,6 +270,12 @@ def build(r, hm, mk, settings):
         sky = add_skybox(r, settings["skybox_equirect"], extent=settings.get("skybox_extent"), equirect=True)
     if settings.get("ambient_from_skybox") is not None and (sky is None or not hasattr(r, "environment_mean")):
         raise ValueError("--ambient-from-skybox needs a skybox on a renderer that can read its mean")
+    blur = settings.get("skybox_blur")
+    if blur is not None:
+        if sky is None or not hasattr(r, "prefilter_environment"):
+            raise ValueError("--skybox-blur needs a skybox on a renderer that can prefilter it")
+        if not 0.0 <= float(blur) <= 1.0:
+            raise ValueError("--skybox-blur: a roughness in [0, 1]")
     n_sky_lights = int(settings.get("lights_from_skybox", 0) or 0)
     if n_sky_lights:
         if not 1 <= n_sky_lights <= 16:
@@ -338,6 +348,10 @@ def build(r, hm, mk, settings):
     if settings.get("ambient_from_skybox") is not None:
         mean = r.environment_mean(sky)
         ambient = tuple(float(settings["ambient_from_skybox"]) * float(v) for v in mean[:3]) + (1.0,)
+    if blur is not None:  # last: the derived cube lives until the cube array is next re-sent
+        blurred, _sh = r.prefilter_environment(sky)
+        r.set_background_texture(blurred)
+        r.set_skybox_level(float(blur) * (r.cubes[blurred].mips - 1))
     meshes = r.meshes
     tris = int(sum(meshes[m["mesh"]].index_count // 3 for m in r.object_meta.values() if m["enabled"]))
     return dict(instance=inst, gltf=g, light=light, camera=(view, PROJECTION), ambient=ambient, clear=CLEAR,
