@@ -84,6 +84,27 @@ protected:
 struct Event : Handle<hipEvent_t, hipEventDestroy, kEvents> {
     hipError_t create(unsigned flags = hipEventDefault) { reset(); return created(hipEventCreateWithFlags(&h, flags)); }
 };
+// The phase boundaries of one synchronous call: up to MAX events, all of them or none (arm(false): none), gone with the call.
+// read() writes the time from event k to event k + 1 into ms[k]: 0 when unarmed, when the call failed (!ok) or where the query fails.
+struct PhaseTaps {
+    static constexpr int MAX = 5;
+    Event ev[MAX];
+    hipEvent_t handles[MAX] = {};  // the events as raw() hands them to a kernel unit that records them itself
+    void arm(bool timing, int n = MAX) {
+        for (int k = 0; k < n && timing; ++k) timing = ev[k].create() == hipSuccess;
+        for (int k = 0; k < MAX; ++k) {
+            if (!timing) ev[k].reset();
+            handles[k] = ev[k];
+        }
+    }
+    bool armed() const { return ev[0] != nullptr; }
+    hipEvent_t *raw() { return armed() ? handles : nullptr; }
+    hipError_t record(int k, hipStream_t stream) const { return armed() ? hipEventRecord(ev[k], stream) : hipSuccess; }
+    void read(float *ms, int n_phases, bool ok) const {
+        for (int k = 0; k < n_phases; ++k)
+            if (!ok || !armed() || hipEventElapsedTime(&ms[k], ev[k], ev[k + 1]) != hipSuccess) ms[k] = 0.0f;
+    }
+};
 struct Stream : Handle<hipStream_t, hipStreamDestroy, kStreams> {
     hipError_t create(unsigned flags) { reset(); return created(hipStreamCreateWithFlags(&h, flags)); }
     hipError_t create(unsigned flags, int priority) { reset(); return created(hipStreamCreateWithPriority(&h, flags, priority)); }

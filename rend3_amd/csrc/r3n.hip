@@ -378,19 +378,17 @@ struct r3n_ctx {
     uint64_t stage_launches[R3N_STAGE_COUNT] = {0};
     // cubes from panoramas (r3n_texture_cubes_write_sources; behind everything a frame touches)
     uint32_t equirect_tail = R3N_EQUIRECT_TAIL_DEFAULT;  // R3N_TUNE equirect_tail: a face of at most this extent builds the rest of its chain in ONE launch (0: never)
-    uint64_t cube_source_launches = 0;  // kernels of the last call (r3n_internal_cube_source_launches)
-    float cube_source_ms[4] = {0, 0, 0, 0};  // with r3n_timing_enable: its copies + decode jobs, k_equirect_faces, the chain, k_cube_assemble
+    struct CallCost { uint64_t launches = 0; float ms[4] = {0, 0, 0, 0}; };  // the last call of a synchronous set-up entry: its kernels, and with r3n_timing_enable its phases in ms
+    CallCost cube_source_cost;  // r3n_internal_cube_source_*: its copies + decode jobs, k_equirect_faces, the chain, k_cube_assemble
     // environment lights (r3n_environment_lights; envlight.h lays the scratch block out): grow-only, no frame reads or writes it
     DeviceBuffer envlight_scratch;
     uint32_t envlight_plane = R3N_ENVLIGHT_PLANE_DEFAULT;    // R3N_TUNE envlight_plane: 1 = quantise once into a plane and re-read it, 0 = decode the texels again in every pass
     uint32_t envlight_blocks = R3N_ENVLIGHT_BLOCKS_DEFAULT;  // R3N_TUNE envlight_blocks: the grid of every pass (0: from the level's size)
-    uint64_t envlight_launches = 0;                          // kernels of the last call (r3n_internal_envlight_launches)
-    float envlight_ms[3] = {0, 0, 0};                        // with r3n_timing_enable: the e_max pass, the quantise pass, all light passes
+    CallCost envlight_cost;                                  // r3n_internal_envlight_*: the e_max pass, the quantise pass, all light passes
     // environment prefilter (r3n_environment_prefilter; ibl.h): the launch plan of the pair kernel, and what the last call cost
     uint32_t ibl_tile = R3N_IBL_TILE_DEFAULT;    // R3N_TUNE ibl_tile: source records per LDS tile, 0 = wave-uniform loads, no LDS
     uint32_t ibl_block = R3N_IBL_BLOCK_DEFAULT;  // R3N_TUNE ibl_block: outputs per workgroup, 64 | 128 | 256
-    uint64_t ibl_launches = 0;                   // kernels of the last call (r3n_internal_ibl_launches)
-    float ibl_ms[4] = {0, 0, 0, 0};              // with r3n_timing_enable: records + mirror, pairs, SH, assemble
+    CallCost ibl_cost;                           // r3n_internal_ibl_*: records + mirror, pairs, SH, assemble
 };
 
 namespace {
@@ -419,6 +417,25 @@ static void crumb(const r3n_ctx *c, const char *what, long long a = -1, long lon
         int _r = (expr);               \
         if (_r != R3N_OK) return _r;   \
     } while (0)
+
+// What a synchronous entry reports once it has waited and released its scratch: the first failure of (enqueue, copy back, wait).
+int first_failure(r3n_ctx *c, const std::string &what, std::initializer_list<hipError_t> errors) {
+    for (hipError_t e : errors)
+        if (e != hipSuccess) return fail(c, R3N_ERR_HIP, what + ": " + hipGetErrorString(e));
+    return R3N_OK;
+}
+// The round trip of a probe on the main stream: the queries go up, `launch(queries, results)` runs, the results come down, the call waits.
+template <class Q, class R, class Launch>
+int probe_round_trip(r3n_ctx *c, const std::string &what, const Q *queries, uint32_t n, R *out, Launch launch) {
+    DeviceBuffer dq, dr;
+    const size_t qb = (size_t)n * sizeof(Q), rb = (size_t)n * sizeof(R);
+    hipError_t e = dq.alloc(qb);
+    if (e == hipSuccess) e = dr.alloc(rb);
+    if (e == hipSuccess) e = hipMemcpyAsync(dq.p, queries, qb, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = (hipError_t)launch(dq.as<const Q>(), dr.as<R>());
+    if (e == hipSuccess) e = hipMemcpyAsync(out, dr.p, rb, hipMemcpyDeviceToHost, c->stream);
+    return first_failure(c, what, {e, hipStreamSynchronize(c->stream)});
+}
 
 int sync_all(r3n_ctx *c);
 int join_shade(r3n_ctx *c);
@@ -1447,8 +1464,7 @@ int r3n_textures_write_encoded(r3n_ctx *c, const r3n_texture_desc32 *descs, uint
             e = enqueue_texture_work(c, work, payload, payload_bytes, c->stream, scratch.p, reinterpret_cast<uint32_t *>(scratch.as<char>() + jobs_at), launches);
         const hipError_t e2 = hipStreamSynchronize(c->stream);  // the caller owns the sources only for the duration of the call
         (void)scratch.reset();
-        if (e != hipSuccess) return fail(c, R3N_ERR_HIP, std::string("textures write (encoded): ") + hipGetErrorString(e));
-        if (e2 != hipSuccess) return fail(c, R3N_ERR_HIP, std::string("textures write (encoded): ") + hipGetErrorString(e2));
+        TRY(first_failure(c, "textures write (encoded)", {e, e2}));
     }
     TRY(upload_level_offsets(c, internal.data(), n, n_texels));
     c->n_textures = n;
@@ -1706,8 +1722,7 @@ int r3n_textures_update(r3n_ctx *c, const uint32_t *slots, const r3n_texture_des
     uint64_t launches = 0;
     const hipError_t e = enqueue_texture_work(c, work, payload, payload_bytes, c->tex_stream, c->tex_stage.p, c->tex_jobs.as<uint32_t>(), launches);
     const hipError_t e2 = hipStreamSynchronize(c->tex_stream);  // its own work alone; the caller owns the payload only for the duration of the call
-    if (e != hipSuccess) return fail(c, R3N_ERR_HIP, std::string("textures update: ") + hipGetErrorString(e));
-    if (e2 != hipSuccess) return fail(c, R3N_ERR_HIP, std::string("textures update: ") + hipGetErrorString(e2));
+    TRY(first_failure(c, "textures update", {e, e2}));
     ++c->tex_stats.update_calls;
     c->tex_stats.kernel_launches += launches;
     c->tex_stats.bytes_staged += payload_bytes;
@@ -1767,16 +1782,9 @@ int r3n_sample_probe(r3n_ctx *c, uint32_t form, const r3n_sample_query40 *querie
     HIP_TRY(c, hipSetDevice(c->device));
     TRY(sync_all(c));  // texture calls run on a stream of their own: what they wrote is there now
     const TextureArgs t = texture_args(c);
-    DeviceBuffer dq, dr;
-    const size_t qb = (size_t)n * sizeof(r3n_sample_query40), rb = (size_t)n * sizeof(r3n_sample_result52);
-    hipError_t e = dq.alloc(qb);
-    if (e == hipSuccess) e = dr.alloc(rb);
-    if (e == hipSuccess) e = hipMemcpyAsync(dq.p, queries, qb, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = (hipError_t)r3n_internal_sample_probe(&t, form, dq.as<const r3n_sample_query40>(), n, dr.as<r3n_sample_result52>(), c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(out, dr.p, rb, hipMemcpyDeviceToHost, c->stream);
-    const hipError_t e2 = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess || e2 != hipSuccess) return fail(c, R3N_ERR_HIP, std::string("sample probe: ") + hipGetErrorString(e != hipSuccess ? e : e2));
-    return R3N_OK;
+    return probe_round_trip(c, "sample probe", queries, n, out, [&](const r3n_sample_query40 *dq, r3n_sample_result52 *dr) {
+        return r3n_internal_sample_probe(&t, form, dq, n, dr, c->stream);
+    });
 }
 
 extern "C" int r3n_internal_move_segments(const uint32_t *block, uint64_t o_first, uint64_t o_inst, uint32_t first_wave, uint32_t waves,
@@ -1847,8 +1855,7 @@ int r3n_textures_compact(r3n_ctx *c, const r3n_texture_compact_opts *opts, r3n_t
     const hipError_t e2 = hipStreamSynchronize(c->tex_stream);  // the update path relies on it: everything that rewrote the pool ended in a wait
     if (e != hipSuccess || e2 != hipSuccess || up != R3N_OK) {
         for (const texel_compact::Move &m : plan.moves) c->h_tex_descs[m.slot].offset = (uint32_t)m.src;  // the mirror as it was (r3n.h: the pool's words are not)
-        if (e != hipSuccess) return fail(c, R3N_ERR_HIP, std::string("textures compact: ") + hipGetErrorString(e));
-        if (e2 != hipSuccess) return fail(c, R3N_ERR_HIP, std::string("textures compact: ") + hipGetErrorString(e2));
+        TRY(first_failure(c, "textures compact", {e, e2}));
         return up;  // (upload_texture_slots has set the message)
     }
     texel_compact::rebuild(c->tex_alloc, plan);
@@ -1931,8 +1938,7 @@ int r3n_textures_from_texture(r3n_ctx *c, const r3n_texture_tail16 *items, uint3
     const hipError_t e2 = hipStreamSynchronize(c->tex_stream);  // its own work alone; later calls rely on it: the new words are complete
     if (up != R3N_OK || e != hipSuccess || e2 != hipSuccess) {
         undo_texture_placement(c, undo);  // the mirror as it was (r3n.h: the device's rows of the destination slots are not)
-        if (e != hipSuccess) return fail(c, R3N_ERR_HIP, std::string("textures from texture: ") + hipGetErrorString(e));
-        if (e2 != hipSuccess) return fail(c, R3N_ERR_HIP, std::string("textures from texture: ") + hipGetErrorString(e2));
+        TRY(first_failure(c, "textures from texture", {e, e2}));
         return up;  // (upload_texture_slots has set the message)
     }
     res.textures = n;
@@ -2038,8 +2044,7 @@ int r3n_mesh_blocks_add(r3n_ctx *c, const r3n_mesh_block24 *blocks, uint32_t n, 
     }
     const hipError_t e2 = hipStreamSynchronize(c->tex_stream);  // its own work alone; the caller owns the payload only for the duration of the call
     ++c->main_epoch;  // the shadow lanes read the mesh buffer
-    if (e != hipSuccess) return fail(c, R3N_ERR_HIP, std::string("mesh blocks add: ") + hipGetErrorString(e));
-    if (e2 != hipSuccess) return fail(c, R3N_ERR_HIP, std::string("mesh blocks add: ") + hipGetErrorString(e2));
+    TRY(first_failure(c, "mesh blocks add", {e, e2}));
     ++c->mesh_stats.add_calls;
     c->mesh_stats.bytes_staged += staged;
     c->mesh_stats.launches += fills;
@@ -2140,8 +2145,7 @@ int r3n_mesh_compact(r3n_ctx *c, const r3n_mesh_compact_opts *opts, r3n_mesh_com
         float ms = 0.0f;
         if (hipEventElapsedTime(&ms, c->mesh_reloc_ev[0], c->mesh_reloc_ev[1]) == hipSuccess) res.relocate_ns = (uint64_t)((double)ms * 1e6);
     }
-    if (e != hipSuccess) return fail(c, R3N_ERR_HIP, std::string("mesh compact: ") + hipGetErrorString(e));
-    if (e2 != hipSuccess) return fail(c, R3N_ERR_HIP, std::string("mesh compact: ") + hipGetErrorString(e2));
+    TRY(first_failure(c, "mesh compact", {e, e2}));
     texel_compact::rebuild(c->mesh_alloc, plan);
     c->mesh_blocks.clear();
     for (const texel_compact::Live &t : plan.live) c->mesh_blocks[t.start] = t.words;
@@ -3233,12 +3237,31 @@ extern "C" int r3n_internal_equirect_level(const uint32_t *block, uint64_t o_fir
                                            hipStream_t stream);
 extern "C" int r3n_internal_equirect_tail(const uint32_t *recs, uint32_t n_recs, uint32_t *dense, hipStream_t stream);
 // kernels the last cube upload enqueued: decode families, k_equirect_faces, the chain, k_cube_assemble
-extern "C" uint64_t r3n_internal_cube_source_launches(const r3n_ctx *c) { return c ? c->cube_source_launches : 0; }
-// with r3n_timing_enable, the phases of that call between device events, in ms (tools/equirect_cost.py)
-extern "C" int r3n_internal_cube_source_times(const r3n_ctx *c, float out[4]) {
-    if (!c || !out) return R3N_ERR_INVALID_ARG;
-    std::memcpy(out, c->cube_source_ms, sizeof c->cube_source_ms);
+extern "C" uint64_t r3n_internal_cube_source_launches(const r3n_ctx *c) { return c ? c->cube_source_cost.launches : 0; }
+// with r3n_timing_enable, the first n phases of a call between device events, in ms (tools/equirect_cost.py and its two neighbours)
+static int phase_times(const r3n_ctx::CallCost *cost, float *out, size_t n) {
+    if (!cost || !out) return R3N_ERR_INVALID_ARG;
+    std::memcpy(out, cost->ms, n * sizeof(float));
     return R3N_OK;
+}
+extern "C" int r3n_internal_cube_source_times(const r3n_ctx *c, float out[4]) { return phase_times(c ? &c->cube_source_cost : nullptr, out, 4); }
+
+// A cube of the pool by its class (cube_plan::Cube::cls): how its texels lie and how a kernel reads them.
+struct CubeView {
+    uint32_t *first;                    // the cube's first word in the pool as it stands: a view does not outlive an ensure() of c->cube_texels
+    uint32_t n, per_texel, f32_class;   // extent of level 0; pool words per texel (4 in the f32 class, else 1); 1 in the f32 class
+    const float *decode;                // the half of the sRGB8 table that decodes the class's colour bytes
+    uint32_t *level_ptr(uint32_t level) const { return first + cube_faces::level_start(n, level, per_texel); }
+};
+static CubeView cube_view(const r3n_ctx *c, const r3n_ctx::Cube &cb) {
+    return CubeView{c->cube_texels.as<uint32_t>() + cb.first_word, cb.n, cb.cls == 2u ? 4u : 1u, cb.cls == 2u ? 1u : 0u, c->srgb8_decode.as<float>() + (cb.cls == 1u ? 256 : 0)};
+}
+// what the environment entries answer to a level whose extent is above their rule's MAX_EXTENT
+static int refuse_extent(r3n_ctx *c, const std::string &what, const r3n_ctx::Cube &cb, uint32_t level, uint32_t max_extent) {
+    uint32_t fits = level;
+    while (cube_faces::level_extent(cb.n, fits) > max_extent) ++fits;
+    return fail(c, R3N_ERR_UNSUPPORTED, what + ": level: extent " + std::to_string(cube_faces::level_extent(cb.n, level)) + " is above " + std::to_string(max_extent) +
+                                            "; the finest level this entry takes is level " + std::to_string(fits) + (fits < cb.mips ? "" : ", which this cube does not store"));
 }
 
 // The device half of every entry.  Every stored (cube, face, level) is one decode job into a DENSE face of the call's scratch block
@@ -3256,10 +3279,9 @@ static int write_cube_plan(r3n_ctx *c, const std::string &what, const cube_plan:
         HIP_TRY(c, scratch.alloc(plan.scratch_bytes));
         auto part = [&](uint64_t at) { return reinterpret_cast<uint32_t *>(scratch.as<char>() + at); };
         uint32_t *dense = part(plan.dense_at), *asm_dev = part(plan.asm_at), *eq_dev = part(plan.eq_at);
-        Event taps[5];  // phase boundaries, with r3n_timing_enable only
-        auto tap = [&](int k) {
-            if (c->timing && taps[k].create() == hipSuccess) (void)hipEventRecord(taps[k], c->stream);
-        };
+        hip_owned::PhaseTaps taps;  // phase boundaries, with r3n_timing_enable only
+        taps.arm(c->timing);
+        auto tap = [&](int k) { (void)taps.record(k, c->stream); };
         tap(0);
         hipError_t e = hipMemcpyAsync(asm_dev, plan.assemble.block.data(), plan.assemble.block.size() * 4u, hipMemcpyHostToDevice, c->stream);
         if (e == hipSuccess && !plan.eq_block.empty()) e = hipMemcpyAsync(eq_dev, plan.eq_block.data(), plan.eq_block.size() * 4u, hipMemcpyHostToDevice, c->stream);
@@ -3287,13 +3309,11 @@ static int write_cube_plan(r3n_ctx *c, const std::string &what, const cube_plan:
         }
         tap(4);
         const hipError_t e2 = hipStreamSynchronize(c->stream);  // the caller owns the sources only for the duration of the call
-        for (int k = 0; k < 4; ++k)
-            if (!c->timing || e != hipSuccess || e2 != hipSuccess || hipEventElapsedTime(&c->cube_source_ms[k], taps[k], taps[k + 1]) != hipSuccess) c->cube_source_ms[k] = 0.0f;
+        taps.read(c->cube_source_cost.ms, 4, e == hipSuccess && e2 == hipSuccess);
         (void)scratch.reset();
-        if (e != hipSuccess) return fail(c, R3N_ERR_HIP, what + ": " + hipGetErrorString(e));
-        if (e2 != hipSuccess) return fail(c, R3N_ERR_HIP, what + ": " + hipGetErrorString(e2));
+        TRY(first_failure(c, what, {e, e2}));
     }
-    c->cube_source_launches = launches;
+    c->cube_source_cost.launches = launches;
     c->cubes = plan.cubes;
     if (c->sky_cube > plan.cubes.size()) c->sky_cube = 0;
     return R3N_OK;
@@ -3356,13 +3376,8 @@ int r3n_skybox_set(r3n_ctx *c, uint32_t cube_id) {
 // Environment lights (envlight.h, envlight_rule.h): every pass is enqueued behind the other on the main stream -- the device
 // decides from its state block whether a light's passes still have work -- and ONE read-back of that block follows; the record
 // the caller gets is derived from its raw sums here, with the rule's own functions.
-extern "C" uint64_t r3n_internal_envlight_launches(const r3n_ctx *c) { return c ? c->envlight_launches : 0; }
-// with r3n_timing_enable, the passes of the last call between device events, in ms (tools/envlight_cost.py)
-extern "C" int r3n_internal_envlight_times(const r3n_ctx *c, float out[3]) {
-    if (!c || !out) return R3N_ERR_INVALID_ARG;
-    std::memcpy(out, c->envlight_ms, sizeof c->envlight_ms);
-    return R3N_OK;
-}
+extern "C" uint64_t r3n_internal_envlight_launches(const r3n_ctx *c) { return c ? c->envlight_cost.launches : 0; }
+extern "C" int r3n_internal_envlight_times(const r3n_ctx *c, float out[3]) { return phase_times(c ? &c->envlight_cost : nullptr, out, 3); }
 static r3n_env_sums env_sums(const envlight_rule::Sums &s) { return r3n_env_sums{{s.q[0], s.q[1], s.q[2]}, s.qy, s.qw, s.texels}; }
 
 int r3n_environment_lights(r3n_ctx *c, const r3n_env_lights_params *p, r3n_env_lights_result *out) {
@@ -3376,45 +3391,31 @@ int r3n_environment_lights(r3n_ctx *c, const r3n_env_lights_params *p, r3n_env_l
     if (!(p->cone_cos >= envlight_rule::COS_MIN && p->cone_cos < 1.0f)) return fail(c, R3N_ERR_INVALID_ARG, what + ": cone_cos: outside [0.5, 1)");
     if (!(p->min_share >= 0.0f && p->min_share < 1.0f)) return fail(c, R3N_ERR_INVALID_ARG, what + ": min_share: outside [0, 1)");
     const uint32_t n = cube_faces::level_extent(cb.n, p->level);
-    if (n > envlight_rule::MAX_EXTENT) {
-        uint32_t fits = p->level;
-        while (cube_faces::level_extent(cb.n, fits) > envlight_rule::MAX_EXTENT) ++fits;
-        return fail(c, R3N_ERR_UNSUPPORTED, what + ": level: extent " + std::to_string(n) + " is above 1024; the finest level this entry takes is level " + std::to_string(fits) +
-                                                (fits < cb.mips ? "" : ", which this cube does not store"));
-    }
+    if (n > envlight_rule::MAX_EXTENT) return refuse_extent(c, what, cb, p->level, envlight_rule::MAX_EXTENT);
     HIP_TRY(c, hipSetDevice(c->device));
     const bool plane = c->envlight_plane != 0u;
     TRY(ensure(c, c->envlight_scratch, envlight_scratch_bytes(n, plane), false, -1));
-    const uint32_t per_texel = cb.cls == 2u ? 4u : 1u;
+    const CubeView view = cube_view(c, cb);
     const size_t texels = (size_t)6u * n * n;
     EnvlightArgs a{};
-    a.level = c->cube_texels.as<uint32_t>() + cb.first_word + cube_faces::level_start(cb.n, p->level, per_texel);
-    a.decode = c->srgb8_decode.as<float>() + (cb.cls == 1u ? 256 : 0);
+    a.level = view.level_ptr(p->level);
     a.n = n;
-    a.f32_class = cb.cls == 2u ? 1u : 0u;
+    a.decode = view.decode; a.f32_class = view.f32_class;
     a.state = c->envlight_scratch.as<envlight_rule::State>();
     a.plane_q = plane ? reinterpret_cast<uint4 *>(c->envlight_scratch.as<char>() + R3N_ENVLIGHT_STATE_BYTES) : nullptr;
     a.plane_lum = plane ? reinterpret_cast<float *>(a.plane_q + texels) : nullptr;
     a.rule = envlight_rule::Params{n, p->max_lights, p->cone_cos, envlight_rule::share_floor(p->min_share)};
     a.blocks = envlight_grid(n, c->envlight_blocks);
-    Event taps[4];
-    hipEvent_t raw[4];
-    bool timed = c->timing;
-    for (int k = 0; k < 4 && timed; ++k) {
-        timed = taps[k].create() == hipSuccess;
-        raw[k] = taps[k];
-    }
+    hip_owned::PhaseTaps taps;
+    taps.arm(c->timing, 4);
     uint64_t launches = 0;
-    const hipError_t e = (hipError_t)r3n_internal_envlight(&a, timed ? raw : nullptr, c->stream, &launches);
+    const hipError_t e = (hipError_t)r3n_internal_envlight(&a, taps.raw(), c->stream, &launches);
     envlight_rule::State st;
     hipError_t e2 = e == hipSuccess ? hipMemcpyAsync(&st, a.state, sizeof st, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
     const hipError_t e3 = hipStreamSynchronize(c->stream);  // `st` is a local; and the call synchronises, like the cube writes
-    for (int k = 0; k < 3; ++k)
-        if (!timed || e != hipSuccess || e2 != hipSuccess || e3 != hipSuccess || hipEventElapsedTime(&c->envlight_ms[k], taps[k], taps[k + 1]) != hipSuccess) c->envlight_ms[k] = 0.0f;
-    if (e != hipSuccess) return fail(c, R3N_ERR_HIP, what + ": " + hipGetErrorString(e));
-    if (e2 != hipSuccess) return fail(c, R3N_ERR_HIP, what + ": " + hipGetErrorString(e2));
-    if (e3 != hipSuccess) return fail(c, R3N_ERR_HIP, what + ": " + hipGetErrorString(e3));
-    c->envlight_launches = launches;
+    taps.read(c->envlight_cost.ms, 3, e == hipSuccess && e2 == hipSuccess && e3 == hipSuccess);
+    TRY(first_failure(c, what, {e, e2, e3}));
+    c->envlight_cost.launches = launches;
     // the record, from the raw sums
     const envlight_rule::Outputs o = envlight_rule::outputs(st, a.rule);
     std::memset(out, 0, sizeof *out);
@@ -3444,13 +3445,8 @@ int r3n_environment_lights(r3n_ctx *c, const r3n_env_lights_params *p, r3n_env_l
 // Environment prefilter (ibl.h, ibl_rule.h): the records of the stored levels, the mirror level, ONE pair launch for every further
 // level and the SH passes go to the main stream behind one another, then k_cube_assemble borders the new cube's faces at the
 // pool's end (cube_plan::plan_append); the pool grows with its contents kept, and the array gains its cube only when all of it ran.
-extern "C" uint64_t r3n_internal_ibl_launches(const r3n_ctx *c) { return c ? c->ibl_launches : 0; }
-// with r3n_timing_enable, the phases of the last call between device events, in ms (tools/ibl_cost.py)
-extern "C" int r3n_internal_ibl_times(const r3n_ctx *c, float out[4]) {
-    if (!c || !out) return R3N_ERR_INVALID_ARG;
-    std::memcpy(out, c->ibl_ms, sizeof c->ibl_ms);
-    return R3N_OK;
-}
+extern "C" uint64_t r3n_internal_ibl_launches(const r3n_ctx *c) { return c ? c->ibl_cost.launches : 0; }
+extern "C" int r3n_internal_ibl_times(const r3n_ctx *c, float out[4]) { return phase_times(c ? &c->ibl_cost : nullptr, out, 4); }
 extern "C" int r3n_internal_ibl_probe(const IblCube *cube, const IblSh *sh, uint32_t f32_class, const r3n_env_query32 *queries, uint32_t n,
                                       r3n_env_sample32 *out, hipStream_t stream);
 
@@ -3462,12 +3458,7 @@ int r3n_environment_prefilter(r3n_ctx *c, const r3n_env_prefilter_params *p, r3n
     const r3n_ctx::Cube cb = c->cubes[p->cube];  // (a copy: the array grows below)
     if (p->level >= cb.mips) return fail(c, R3N_ERR_INVALID_ARG, what + ": level: the cube has no such level");
     const uint32_t S = cube_faces::level_extent(cb.n, p->level), L = p->levels;
-    if (S > ibl_rule::MAX_EXTENT) {
-        uint32_t fits = p->level;
-        while (cube_faces::level_extent(cb.n, fits) > ibl_rule::MAX_EXTENT) ++fits;
-        return fail(c, R3N_ERR_UNSUPPORTED, what + ": level: extent " + std::to_string(S) + " is above 256; the finest level this entry takes is level " + std::to_string(fits) +
-                                                (fits < cb.mips ? "" : ", which this cube does not store"));
-    }
+    if (S > ibl_rule::MAX_EXTENT) return refuse_extent(c, what, cb, p->level, ibl_rule::MAX_EXTENT);
     const uint32_t by_extent = std::min(ibl_rule::levels_of(S), ibl_rule::MAX_LEVELS);
     if (L < 2u) return fail(c, R3N_ERR_INVALID_ARG, what + ": levels: at least 2 (the mirror level and one filtered level)");
     if (L > by_extent) return fail(c, R3N_ERR_INVALID_ARG, what + ": levels: extent " + std::to_string(S) + " has at most " + std::to_string(by_extent) + " levels");
@@ -3481,11 +3472,10 @@ int r3n_environment_prefilter(r3n_ctx *c, const r3n_env_prefilter_params *p, r3n
     TRY(sync_all(c));  // no frame in flight while the pool may move
     TRY(ensure(c, c->cube_texels, plan.pool_words * 4u, true, -1));
     // the launch plan
-    const uint32_t per_texel = cb.cls == 2u ? 4u : 1u;
+    const CubeView view = cube_view(c, cb);
     IblArgs a{};
     a.pool = c->cube_texels.as<uint32_t>();
-    a.decode = c->srgb8_decode.as<float>() + (cb.cls == 1u ? 256 : 0);
-    a.f32_class = cb.cls == 2u ? 1u : 0u;
+    a.decode = view.decode; a.f32_class = view.f32_class;
     a.L = L;
     a.sh_k = ibl_rule::sh_level(S, L);
     a.rec_from = a.sh_k == 0u ? 0u : 1u;
@@ -3494,7 +3484,7 @@ int r3n_environment_prefilter(r3n_ctx *c, const r3n_env_prefilter_params *p, r3n
     for (uint32_t k = 0; k < L; ++k) {
         IblLevel &lv = a.lv[k];
         lv.n = ibl_rule::level_extent(S, k);
-        lv.src_word = (uint32_t)(cb.first_word + cube_faces::level_start(cb.n, p->level + k, per_texel));
+        lv.src_word = (uint32_t)(view.level_ptr(p->level + k) - a.pool);
         lv.dense_word = plan.level_dense[k];
         const ibl_rule::Roughness r = ibl_rule::roughness(k, L);
         lv.a2 = r.a2;
@@ -3519,31 +3509,24 @@ int r3n_environment_prefilter(r3n_ctx *c, const r3n_env_prefilter_params *p, r3n
     a.sh_rows = reinterpret_cast<float *>(part(lay.sh_rows));
     a.sh_out = reinterpret_cast<float *>(part(lay.sh_out));
     uint32_t *asm_dev = reinterpret_cast<uint32_t *>(part(lay.assemble));
-    Event taps[5];
-    hipEvent_t raw[5];
-    bool timed = c->timing;
-    for (int k = 0; k < 5 && timed; ++k) {
-        timed = taps[k].create() == hipSuccess;
-        raw[k] = taps[k];
-    }
+    hip_owned::PhaseTaps taps;
+    taps.arm(c->timing);
     uint64_t launches = 0;
     float sums[27];
     hipError_t e = hipMemcpyAsync(asm_dev, plan.assemble.block.data(), plan.assemble.block.size() * 4u, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = (hipError_t)r3n_internal_ibl(&a, timed ? raw : nullptr, c->stream, &launches);
+    if (e == hipSuccess) e = (hipError_t)r3n_internal_ibl(&a, taps.raw(), c->stream, &launches);
     if (e == hipSuccess) {
         e = (hipError_t)r3n_internal_cube_assemble(asm_dev, plan.assemble.layout.o_first, plan.assemble.layout.o_inst, (uint32_t)plan.assemble.waves, a.dense,
                                                    c->cube_texels.as<uint32_t>(), c->stream);
         ++launches;
     }
-    if (e == hipSuccess && timed) e = hipEventRecord(raw[4], c->stream);
+    if (e == hipSuccess) e = taps.record(4, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(sums, a.sh_out, sizeof sums, hipMemcpyDeviceToHost, c->stream);
     const hipError_t e2 = hipStreamSynchronize(c->stream);  // `sums` and the table are locals; and the call synchronises, like the cube writes
-    for (int k = 0; k < 4; ++k)
-        if (!timed || e != hipSuccess || e2 != hipSuccess || hipEventElapsedTime(&c->ibl_ms[k], taps[k], taps[k + 1]) != hipSuccess) c->ibl_ms[k] = 0.0f;
+    taps.read(c->ibl_cost.ms, 4, e == hipSuccess && e2 == hipSuccess);
     (void)scratch.reset();
-    if (e != hipSuccess) return fail(c, R3N_ERR_HIP, what + ": " + hipGetErrorString(e));
-    if (e2 != hipSuccess) return fail(c, R3N_ERR_HIP, what + ": " + hipGetErrorString(e2));
-    c->ibl_launches = launches;
+    TRY(first_failure(c, what, {e, e2}));
+    c->ibl_cost.launches = launches;
     c->cubes.push_back(plan.cube);
     std::memset(out, 0, sizeof *out);
     out->cube_id = (uint32_t)c->cubes.size() - 1u;
@@ -3563,19 +3546,13 @@ int r3n_environment_probe(r3n_ctx *c, uint32_t cube, const float sh[9][4], const
     HIP_TRY(c, hipSetDevice(c->device));
     TRY(sync_all(c));
     const r3n_ctx::Cube &cb = c->cubes[cube];
-    const IblCube ic{c->cube_texels.as<uint32_t>() + cb.first_word, c->srgb8_decode.as<float>() + (cb.cls == 1u ? 256 : 0), cb.n, cb.mips};
+    const CubeView view = cube_view(c, cb);
+    const IblCube ic{view.level_ptr(0), view.decode, cb.n, cb.mips};
     IblSh is;
     std::memcpy(is.sh, sh, sizeof is.sh);
-    DeviceBuffer dq, dr;
-    const size_t qb = (size_t)n * sizeof(r3n_env_query32), rb = (size_t)n * sizeof(r3n_env_sample32);
-    hipError_t e = dq.alloc(qb);
-    if (e == hipSuccess) e = dr.alloc(rb);
-    if (e == hipSuccess) e = hipMemcpyAsync(dq.p, queries, qb, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = (hipError_t)r3n_internal_ibl_probe(&ic, &is, cb.cls == 2u ? 1u : 0u, dq.as<const r3n_env_query32>(), n, dr.as<r3n_env_sample32>(), c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(out, dr.p, rb, hipMemcpyDeviceToHost, c->stream);
-    const hipError_t e2 = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess || e2 != hipSuccess) return fail(c, R3N_ERR_HIP, what + ": " + hipGetErrorString(e != hipSuccess ? e : e2));
-    return R3N_OK;
+    return probe_round_trip(c, what, queries, n, out, [&](const r3n_env_query32 *dq, r3n_env_sample32 *dr) {
+        return r3n_internal_ibl_probe(&ic, &is, view.f32_class, dq, n, dr, c->stream);
+    });
 }
 
 int r3n_skybox_set_level(r3n_ctx *c, float level) {
@@ -3596,7 +3573,8 @@ int r3n_skybox(r3n_ctx *c) {
     SkyboxArgs a{};
     a.vis = c->vis.as<unsigned long long>();
     a.fu = c->fu.as<r3n_frame_uniforms496>();
-    a.texels = c->cube_texels.as<uint32_t>() + cube.first_word;
+    const CubeView view = cube_view(c, cube);
+    a.texels = view.level_ptr(0);
     a.decode = c->srgb8_decode.as<float>();
     a.n = cube.n; a.srgb = cube.srgb; a.mips = cube.mips;
     a.width = c->width; a.height = c->height; a.row_begin = r0; a.row_end = r1;
@@ -3617,7 +3595,7 @@ int r3n_skybox(r3n_ctx *c) {
     hipStream_t stream = c->resolve_on_shade ? c->shade : c->stream;
     {
         Timed t(c, R3N_STAGE_SKYBOX, stream);
-        HIP_TRY(c, (hipError_t)r3n_internal_skybox(&a, c->samples, cube.cls == 2u ? 1u : 0u, stream));
+        HIP_TRY(c, (hipError_t)r3n_internal_skybox(&a, c->samples, view.f32_class, stream));
     }
     TRY(check_launch(c, "k_skybox"));
     // whatever waits for the resolve -- the frame that reuses these targets, the read-backs -- waits for the sky as well
@@ -4709,11 +4687,11 @@ int r3n_readback_cube_face(r3n_ctx *c, uint32_t cube, uint32_t level, uint32_t f
     if (!c || !dst) return fail(c, R3N_ERR_INVALID_ARG, "readback_cube_face: null");
     if (cube >= c->cubes.size() || face >= 6u || level >= c->cubes[cube].mips) return fail(c, R3N_ERR_INVALID_ARG, "readback_cube_face: no such cube, level or face");
     const r3n_ctx::Cube &cb = c->cubes[cube];
-    const uint32_t per_texel = cb.cls == 2u ? 4u : 1u, nk = cube_faces::level_extent(cb.n, level);
-    const uint64_t need = cube_faces::face_words(nk, per_texel);
+    const CubeView view = cube_view(c, cb);
+    const uint64_t need = cube_faces::face_words(cube_faces::level_extent(cb.n, level), view.per_texel);
     if (words < need) return fail(c, R3N_ERR_INVALID_ARG, "readback_cube_face: dst is shorter than the bordered face");
     if (pool_class) *pool_class = cb.cls;
-    return d2h(c, dst, c->cube_texels.as<uint32_t>() + cb.first_word + cube_faces::level_start(cb.n, level, per_texel) + face * need, need * 4);
+    return d2h(c, dst, view.level_ptr(level) + face * need, need * 4);
 }
 
 int r3n_readback_texels(r3n_ctx *c, uint64_t first_texel, uint32_t *rgba8, uint64_t n_texels) {

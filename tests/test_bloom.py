@@ -8,20 +8,19 @@ import ctypes
 import math
 import os
 import re
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
 import bloom_reference as B
+import host_check
 import tonemap_reference as T
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 SRC = os.path.join(HERE, "bloom_rule_check.cpp")
 RULES = [os.path.join(ROOT, "rend3_amd", "csrc", f) for f in ("bloom_rule.h", "exposure_rule.h")]
-OUT = os.path.join(HERE, "_build", "bloom_rule_check")
 f32 = np.float32
 ONE = 0x3C00
 
@@ -256,16 +255,7 @@ def test_reference_against_float64(size):
 
 # ------------------------------------------------------------------ 4. the shared rule header, sanitized, stand-alone
 def program():
-    if not (os.path.exists(OUT) and os.path.getmtime(OUT) >= max(os.path.getmtime(f) for f in [SRC] + RULES)):
-        hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-        os.makedirs(os.path.dirname(OUT), exist_ok=True)
-        tmp = OUT + f".{os.getpid()}.tmp"
-        flags = ["-Xarch_host", "-fsanitize=address", "-Xarch_host", "-fsanitize=undefined", "-fno-sanitize-recover=all"]
-        res = subprocess.run([hipcc, "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-Wall", "-Werror"] + flags + ["-o", tmp, "-x", "c++", SRC],
-                             capture_output=True, text=True)  # (host code only: -x c++ makes no device pass)
-        assert res.returncode == 0, "bloom_rule_check build failed:\n" + res.stdout + res.stderr
-        os.replace(tmp, OUT)
-    return OUT
+    return host_check.program(SRC, RULES, fp_contract_off=True)
 
 
 def run(cmd, text=""):

@@ -3,12 +3,12 @@ r3n_texture_cubes_write_sources decide before their first HIP call) on the CPU, 
 program built plain and with the address and undefined-behaviour sanitizers and run as a child process.  The refusals are the rows
 of tests/cube_refusals.py, the list the GPU tests send to the entries themselves."""
 import os
-import shutil
 import subprocess
 
 import pytest
 
 import cube_refusals as R
+import host_check
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.join(HERE, "..")
@@ -16,22 +16,11 @@ SRC = os.path.join(HERE, "cube_plan_check.cpp")
 HEADERS = [os.path.join(ROOT, "rend3_amd", "csrc", h) for h in ("cube_plan.h", "cube_faces.h", "equirect.h", "equirect_rule.h", "texture_jobs.h",
                                                                  "vertex_block.h")]
 HEADERS.append(os.path.join(ROOT, "include", "r3n.h"))
-OUT = os.path.join(HERE, "_build", "cube_plan_check")
 
 
 def program(sanitize):
     """Path of the built check program (built once, when its sources are newer); sanitize=False: a plain build under its own name."""
-    out = OUT if sanitize else OUT + "_plain"
-    if not (os.path.exists(out) and os.path.getmtime(out) >= max(os.path.getmtime(f) for f in [SRC] + HEADERS)):
-        hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-        os.makedirs(os.path.dirname(out), exist_ok=True)
-        tmp = out + f".{os.getpid()}.tmp"
-        flags = ["-Xarch_host", "-fsanitize=address", "-Xarch_host", "-fsanitize=undefined", "-fno-sanitize-recover=all"] if sanitize else []
-        res = subprocess.run([hipcc, "-O1", "-g", "-std=c++17", "-Wall", "-Werror"] + flags + ["-o", tmp, "-x", "c++", SRC],
-                             capture_output=True, text=True)  # (host code only: -x c++ makes no device pass)
-        assert res.returncode == 0, "cube_plan_check build failed:\n" + res.stdout + res.stderr
-        os.replace(tmp, out)
-    return out
+    return host_check.program(SRC, HEADERS, sanitize=sanitize)
 
 
 @pytest.mark.parametrize("sanitize", [False, True], ids=["plain", "sanitized"])

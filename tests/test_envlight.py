@@ -9,7 +9,6 @@ import ctypes
 import math
 import os
 import re
-import shutil
 import subprocess
 from fractions import Fraction
 
@@ -17,28 +16,19 @@ import numpy as np
 import pytest
 
 import envlight_reference as E
+import host_check
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 SRC = os.path.join(HERE, "envlight_rule_check.cpp")
 CSRC = os.path.join(ROOT, "rend3_amd", "csrc")
 RULES = [os.path.join(CSRC, h) for h in ("envlight_rule.h", "equirect_rule.h", "exposure_rule.h")]
-OUT = os.path.join(HERE, "_build", "envlight_rule_check")
 f32 = np.float32
 CONE6 = f32(math.cos(math.radians(6.0)))
 
 
 def program():
-    if not (os.path.exists(OUT) and os.path.getmtime(OUT) >= max(os.path.getmtime(f) for f in [SRC] + RULES)):
-        hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-        os.makedirs(os.path.dirname(OUT), exist_ok=True)
-        tmp = OUT + f".{os.getpid()}.tmp"
-        flags = ["-Xarch_host", "-fsanitize=address", "-Xarch_host", "-fsanitize=undefined", "-fno-sanitize-recover=all"]
-        res = subprocess.run([hipcc, "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-Wall", "-Werror"] + flags + ["-o", tmp, "-x", "c++", SRC],
-                             capture_output=True, text=True)  # (host code only: -x c++ makes no device pass)
-        assert res.returncode == 0, "envlight_rule_check build failed:\n" + res.stdout + res.stderr
-        os.replace(tmp, OUT)
-    return OUT
+    return host_check.program(SRC, RULES, fp_contract_off=True)
 
 
 def run(cmd, text=""):

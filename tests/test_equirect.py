@@ -8,36 +8,26 @@ import ctypes
 import math
 import os
 import re
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
 import equirect_reference as Q
+import host_check
 import skybox_reference as S
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 SRC = os.path.join(HERE, "equirect_rule_check.cpp")
 RULE = os.path.join(ROOT, "rend3_amd", "csrc", "equirect_rule.h")
-OUT = os.path.join(HERE, "_build", "equirect_rule_check")
 f32 = np.float32
 SOURCES = [(1, 1), (2, 1), (4, 2), (7, 5), (64, 32)]
 EXTENTS = [1, 2, 3, 5, 8]
 
 
 def program():
-    if not (os.path.exists(OUT) and os.path.getmtime(OUT) >= max(os.path.getmtime(f) for f in (SRC, RULE))):
-        hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-        os.makedirs(os.path.dirname(OUT), exist_ok=True)
-        tmp = OUT + f".{os.getpid()}.tmp"
-        flags = ["-Xarch_host", "-fsanitize=address", "-Xarch_host", "-fsanitize=undefined", "-fno-sanitize-recover=all"]
-        res = subprocess.run([hipcc, "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-Wall", "-Werror"] + flags + ["-o", tmp, "-x", "c++", SRC],
-                             capture_output=True, text=True)  # (host code only: -x c++ makes no device pass)
-        assert res.returncode == 0, "equirect_rule_check build failed:\n" + res.stdout + res.stderr
-        os.replace(tmp, OUT)
-    return OUT
+    return host_check.program(SRC, [RULE], fp_contract_off=True)
 
 
 def run(cmd, text=""):

@@ -6,19 +6,18 @@ ctypes table, the Python renderer and the viewer.  The GPU side is tests/test_me
 what the allocator hands out."""
 import os
 import re
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
+import host_check
 import mesh_reloc_reference as MR
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.join(HERE, "..")
 SRC = os.path.join(HERE, "mesh_reloc_check.cpp")
 HEADERS = [os.path.join(ROOT, "rend3_amd", "csrc", h) for h in ("mesh_reloc.h", "texel_compact.h", "texel_alloc.h", "vertex_block.h")]
-OUT = os.path.join(HERE, "_build", "mesh_reloc_check")
 INVALID = 0xFFFFFFFF
 
 
@@ -26,17 +25,7 @@ def program(sanitize=True):
     """Path of the built check program (built once, when its sources are newer).  sanitize=True: with the address and
     undefined-behaviour sanitizers, for the CPU tests of this file; sanitize=False: a plain build under a name of its own, which is
     what tests/test_mesh_stream_gpu.py asks for the allocator's answers -- no sanitizer runs beside the GPU."""
-    out = OUT if sanitize else OUT + "_plain"
-    if not (os.path.exists(out) and os.path.getmtime(out) >= max(os.path.getmtime(f) for f in [SRC] + HEADERS)):
-        hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-        os.makedirs(os.path.dirname(out), exist_ok=True)
-        tmp = out + f".{os.getpid()}.tmp"
-        flags = ["-Xarch_host", "-fsanitize=address", "-Xarch_host", "-fsanitize=undefined", "-fno-sanitize-recover=all"] if sanitize else []
-        res = subprocess.run([hipcc, "-O1", "-g", "-std=c++17", "-Wall", "-Werror"] + flags + ["-o", tmp, "-x", "c++", SRC],
-                             capture_output=True, text=True)  # (host code only: -x c++ makes no device pass)
-        assert res.returncode == 0, "mesh_reloc_check build failed:\n" + res.stdout + res.stderr
-        os.replace(tmp, out)
-    return out
+    return host_check.program(SRC, HEADERS, sanitize=sanitize)
 
 
 def pool_ops(ops, sanitize=True):

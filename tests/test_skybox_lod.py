@@ -4,12 +4,12 @@ readers, add_texture_cube_encoded's validation, the ABI tables, and csrc/cube_fa
 stand-alone program built with the address and undefined-behaviour sanitizers and run as a child process.  The GPU side is
 tests/test_skybox_lod_gpu.py."""
 import os
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
+import host_check
 import skybox_lod_cases as cases
 import skybox_lod_reference as lodref
 import skybox_reference as sky
@@ -235,7 +235,6 @@ def test_abi_tables_name_the_new_entries():
 # ------------------------------------------------------------------ csrc/cube_faces.h alone, under the sanitizers
 SRC = os.path.join(HERE, "cube_faces_check.cpp")
 HEADER = os.path.join(ROOT, "rend3_amd", "csrc", "cube_faces.h")
-OUT = os.path.join(HERE, "_build", "cube_faces_check")
 # Every entry's borders come from this table (k_cube_assemble), so this comparison is the one tie between it and resolve_texel:
 # every extent a test sends through the plain entry -- 4 (test_skybox.py's constant cubes, the viewer's PNG faces,
 # test_equirect_gpu.py, test_resources_gpu.py), 1, 2, 7, 8, 16, 64 (test_skybox.py), 7, 2 and 1, 3, 4, 5 (test_skybox_lod_gpu.py)
@@ -255,20 +254,12 @@ def expected_sources(n):
 
 @pytest.fixture(scope="module")
 def printed(tmp_path_factory):
-    if not (os.path.exists(OUT) and os.path.getmtime(OUT) >= max(os.path.getmtime(f) for f in (SRC, HEADER))):
-        hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-        os.makedirs(os.path.dirname(OUT), exist_ok=True)
-        tmp = OUT + f".{os.getpid()}.tmp"
-        res = subprocess.run([hipcc, "-O1", "-g", "-std=c++17", "-Wall", "-Werror", "-Xarch_host", "-fsanitize=address", "-Xarch_host",
-                              "-fsanitize=undefined", "-fno-sanitize-recover=all", "-o", tmp, "-x", "c++", SRC],
-                             capture_output=True, text=True)  # (host code only: -x c++ makes no device pass)
-        assert res.returncode == 0, "cube_faces_check build failed:\n" + res.stdout + res.stderr
-        os.replace(tmp, OUT)
+    exe = host_check.program(SRC, [HEADER])
     table = tmp_path_factory.mktemp("cube_faces") / "table.txt"
     with open(table, "w") as f:
         for n in EXTENTS:
             f.write(f"n {n}\n" + " ".join(str(int(v)) for v in expected_sources(n)) + "\n")
-    res = subprocess.run([OUT, str(table)], capture_output=True, text=True, timeout=120)
+    res = subprocess.run([exe, str(table)], capture_output=True, text=True, timeout=120)
     assert res.returncode == 0, res.stdout[-4000:] + res.stderr[-4000:]
     assert res.stderr == ""  # a sanitizer report goes there
     lines = {}

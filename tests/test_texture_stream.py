@@ -4,31 +4,23 @@ sanitizers and run as a child process -- and the declarations of the new entry p
 Python renderer.  The GPU side is tests/test_texture_stream_gpu.py."""
 import os
 import re
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
+import host_check
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.join(HERE, "..")
 SRC = os.path.join(HERE, "texel_alloc_check.cpp")
 HEADERS = [os.path.join(ROOT, "rend3_amd", "csrc", h) for h in ("texel_alloc.h", "texture_jobs.h", "vertex_block.h")]
-OUT = os.path.join(HERE, "_build", "texel_alloc_check")
 
 
 @pytest.fixture(scope="module")
 def printed():
-    if not (os.path.exists(OUT) and os.path.getmtime(OUT) >= max(os.path.getmtime(f) for f in [SRC] + HEADERS)):
-        hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-        os.makedirs(os.path.dirname(OUT), exist_ok=True)
-        tmp = OUT + f".{os.getpid()}.tmp"
-        res = subprocess.run([hipcc, "-O1", "-g", "-std=c++17", "-Wall", "-Werror", "-Xarch_host", "-fsanitize=address", "-Xarch_host",
-                              "-fsanitize=undefined", "-fno-sanitize-recover=all", "-o", tmp, "-x", "c++", SRC],
-                             capture_output=True, text=True)  # (host code only: -x c++ makes no device pass)
-        assert res.returncode == 0, "texel_alloc_check build failed:\n" + res.stdout + res.stderr
-        os.replace(tmp, OUT)
-    res = subprocess.run([OUT], capture_output=True, text=True, timeout=120)
+    exe = host_check.program(SRC, HEADERS)
+    res = subprocess.run([exe], capture_output=True, text=True, timeout=120)
     assert res.returncode == 0, res.stdout[-4000:] + res.stderr[-4000:]
     assert res.stderr == ""  # a sanitizer report goes there
     lines = {}

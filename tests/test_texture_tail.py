@@ -4,19 +4,19 @@ program built with the address and undefined-behaviour sanitizers and run as a c
 entry point in the header, the ctypes table, the Python renderer, the loader, the viewer and the generated Rust bindings.  The GPU
 side is tests/test_texture_tail_gpu.py, which asks the same program for the tail of a chain."""
 import os
-import shutil
 import subprocess
 import sys
 
 import numpy as np
 import pytest
 
+import host_check
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.join(HERE, "..")
 SRC = os.path.join(HERE, "texel_tail_check.cpp")
 HEADERS = [os.path.join(ROOT, "rend3_amd", "csrc", h) for h in ("texel_tail.h", "texel_alloc.h", "texture_jobs.h", "vertex_block.h")]
 HEADERS.append(os.path.join(ROOT, "include", "r3n.h"))
-OUT = os.path.join(HERE, "_build", "texel_tail_check")
 
 # the chains of texel_tail_check.cpp: (width, height, pool words per texel), each with its full chain
 CHAINS = [(1, 1, 1), (5, 3, 1), (7, 1, 1), (16, 16, 1), (64, 2, 1), (8, 4, 4)]
@@ -26,17 +26,7 @@ def program(sanitize=True):
     """Path of the built check program (built once, when its sources are newer).  sanitize=True: with the address and
     undefined-behaviour sanitizers, for the CPU tests of this file; sanitize=False: a plain build under a name of its own, which is
     what tests/test_texture_tail_gpu.py asks for a chain's tail -- no sanitizer runs beside the GPU."""
-    out = OUT if sanitize else OUT + "_plain"
-    if not (os.path.exists(out) and os.path.getmtime(out) >= max(os.path.getmtime(f) for f in [SRC] + HEADERS)):
-        hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-        os.makedirs(os.path.dirname(out), exist_ok=True)
-        tmp = out + f".{os.getpid()}.tmp"
-        flags = ["-Xarch_host", "-fsanitize=address", "-Xarch_host", "-fsanitize=undefined", "-fno-sanitize-recover=all"] if sanitize else []
-        res = subprocess.run([hipcc, "-O1", "-g", "-std=c++17", "-Wall", "-Werror"] + flags + ["-o", tmp, "-x", "c++", SRC],
-                             capture_output=True, text=True)  # (host code only: -x c++ makes no device pass)
-        assert res.returncode == 0, "texel_tail_check build failed:\n" + res.stdout + res.stderr
-        os.replace(tmp, out)
-    return out
+    return host_check.program(SRC, HEADERS, sanitize=sanitize)
 
 
 def full_chain(w, h):

@@ -7,19 +7,18 @@ import ctypes
 import math
 import os
 import re
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
+import host_check
 import tonemap_reference as T
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 SRC = os.path.join(HERE, "exposure_rule_check.cpp")
 RULE = os.path.join(ROOT, "rend3_amd", "csrc", "exposure_rule.h")
-OUT = os.path.join(HERE, "_build", "exposure_rule_check")
 f32 = np.float32
 ALL_HALVES = np.arange(65536, dtype=np.uint16)
 
@@ -141,16 +140,7 @@ def test_operators_are_monotone_and_finite(op):
 
 # ------------------------------------------------------------------ 7: the shared rule header, sanitized, stand-alone
 def program():
-    if not (os.path.exists(OUT) and os.path.getmtime(OUT) >= max(os.path.getmtime(f) for f in (SRC, RULE))):
-        hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-        os.makedirs(os.path.dirname(OUT), exist_ok=True)
-        tmp = OUT + f".{os.getpid()}.tmp"
-        flags = ["-Xarch_host", "-fsanitize=address", "-Xarch_host", "-fsanitize=undefined", "-fno-sanitize-recover=all"]
-        res = subprocess.run([hipcc, "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-Wall", "-Werror"] + flags + ["-o", tmp, "-x", "c++", SRC],
-                             capture_output=True, text=True)  # (host code only: -x c++ makes no device pass)
-        assert res.returncode == 0, "exposure_rule_check build failed:\n" + res.stdout + res.stderr
-        os.replace(tmp, OUT)
-    return OUT
+    return host_check.program(SRC, [RULE], fp_contract_off=True)
 
 
 def run(cmd, text=""):

@@ -3,30 +3,22 @@ r3n_vertex_normals and r3n_vertex_tangents, at the edges no GPU test reaches (no
 tests/vertex_block_check.cpp is built as a stand-alone program with the address and undefined-behaviour sanitizers, run as a child
 process, and every word it prints is compared with the layout restated here."""
 import os
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
+import host_check
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "vertex_block_check.cpp")
 HEADER = os.path.join(HERE, "..", "rend3_amd", "csrc", "vertex_block.h")
-OUT = os.path.join(HERE, "_build", "vertex_block_check")
 
 
 @pytest.fixture(scope="module")
 def printed():
-    if not (os.path.exists(OUT) and os.path.getmtime(OUT) >= max(os.path.getmtime(SRC), os.path.getmtime(HEADER))):
-        hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-        os.makedirs(os.path.dirname(OUT), exist_ok=True)
-        tmp = OUT + f".{os.getpid()}.tmp"
-        res = subprocess.run([hipcc, "-O1", "-g", "-std=c++17", "-Wall", "-Werror", "-Xarch_host", "-fsanitize=address", "-Xarch_host",
-                              "-fsanitize=undefined", "-fno-sanitize-recover=all", "-o", tmp, "-x", "c++", SRC],
-                             capture_output=True, text=True)  # (host code only: -x c++ makes no device pass, -Xarch_host keeps the sanitizers off any)
-        assert res.returncode == 0, "vertex_block_check build failed:\n" + res.stdout + res.stderr
-        os.replace(tmp, OUT)
-    res = subprocess.run([OUT], capture_output=True, text=True, timeout=60)
+    exe = host_check.program(SRC, [HEADER])
+    res = subprocess.run([exe], capture_output=True, text=True, timeout=60)
     assert res.returncode == 0, res.stdout + res.stderr
     assert res.stderr == ""  # a sanitizer report goes there
     lines = {}
